@@ -27,9 +27,13 @@ Exit code: 0 only if every rank finished every part it started.  A run whose pol
 peer died, or whose closing barrier never completed still prints the (already measured) headline line, then exits 3; a
 rank on which the extra raised exits 4 (it never enters a collective its peers are not in).
 
-Extra objects: ``roofline`` (HIP-event timed launches vs the 8 TB/s HBM peak; algorithmic bytes 678 B/env-step;
-counter traffic and the VALU issue share from the committed rocprofv3 summaries) and ``cpu_baseline`` (the
-upstream-structured scalar NumPy oracle on one host core, bounded sample; rank 0, N = 1 only).
+A plain run does only what the headline needs: set-up, clock ramp, W warm-up and K timed launches, the last launch's
+outputs if ``--dump-outputs DIR`` is given (``dump_outputs``), and the line with its ``roofline`` object (HIP-event timed
+launches vs the 8 TB/s HBM peak; algorithmic bytes 678 B/env-step; counter traffic and the VALU issue share from the
+committed rocprofv3 summaries).  ``--full`` adds everything that takes runs of its own: ``cpu_baseline`` (the
+upstream-structured scalar NumPy oracle on one host core, bounded sample, and the C oracle; rank 0, N = 1 only), the
+policy-in-the-loop extra (``policy_in_loop``), the other BASELINE configurations (``other_configs``) and, at N > 1, the
+K launches once more without the exchange (``multi_gpu``).
 """
 import argparse
 import json
@@ -276,6 +280,38 @@ def _profile_refusals(prefix_filter=None):
     return None if not r else 'refused: %s -- %s' % r[0]
 
 
+DUMP_BYTES = 60e6   # --dump-outputs: payload bound; with the .npy headers the files stay below 64 MB
+
+
+def dump_outputs(dirname, out, seed=12345678):
+    """--dump-outputs: what the last timed launch returned to its caller -- its output tensors [T, B, ...] -- as
+    DIR/<name>.npy in float32 (bool planes as 0 / 1).  Rows are (step, env) pairs: all of them if they fit in DUMP_BYTES,
+    else every env of the launch's last step plus a fixed seeded draw of the earlier rows; step_index.npy and
+    env_index.npy (float64) name the rows kept.  The kernel writes final_obs only where an env reset, so its rows are 0
+    where terminal is not set (elsewhere that buffer holds whatever the allocator left there)."""
+    import numpy as np
+    import torch
+    names = [k for k in ('obs', 'final_obs', 'rew', 'rew_shared', 'done', 'terminal') if k in out]
+    T, B = out['terminal'].shape[:2]
+    n = T * B
+    cap = max(1, int(DUMP_BYTES // (4 * sum(out[k][0, 0].numel() for k in names) + 2 * 8)))
+    if n <= cap:
+        rows = np.arange(n)
+    else:
+        last = np.arange(max(n - B, n - cap), n)
+        rest = np.random.RandomState(seed).randint(0, last[0], size=cap - len(last))
+        rows = np.concatenate([np.unique(rest), last])
+    idx = torch.from_numpy(rows).to(out['terminal'].device)
+    got = {k: out[k].reshape(n, -1).index_select(0, idx).float() for k in names}
+    if 'final_obs' in got:
+        got['final_obs'] = got['final_obs'].masked_fill(got['terminal'] == 0, 0.0)
+    os.makedirs(dirname, exist_ok=True)
+    for k in names:
+        np.save(os.path.join(dirname, k + '.npy'), got[k].cpu().numpy().reshape((len(rows),) + tuple(out[k].shape[2:])))
+    np.save(os.path.join(dirname, 'step_index.npy'), (rows // B).astype(np.float64))
+    np.save(os.path.join(dirname, 'env_index.npy'), (rows % B).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -297,6 +333,11 @@ def main():
     ap.add_argument('--exit-timeout', type=int, default=30, help='seconds the closing barrier may take (N > 1)')
     ap.add_argument('--policy-timeout', type=int, default=240, help='seconds after which the policy-in-the-loop extra is '
                                                                     'abandoned (the line is printed without it)')
+    ap.add_argument('--full', action='store_true', help='also measure what takes runs of its own: CPU baselines, the '
+                                                        'policy-in-the-loop extra, the other BASELINE configurations and, '
+                                                        'at N > 1, the launches without the exchange')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write the outputs of the last timed launch as DIR/<name>.npy '
+                                                          '(float32, a fixed seeded sample of at most 64 MB; rank 0)')
     args = ap.parse_args()
 
     preload = _profiler_preload()
@@ -319,7 +360,7 @@ def main():
 
     # CPU baseline first, on rank 0 at N = 1 only, BEFORE this process touches the GPU (it forks workers)
     cpu_line = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline and args.scenario == 'simple_spread' and not STUB:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline and args.scenario == 'simple_spread' and not STUB:
         cpu_line = cpu_baseline(args.cpu_seconds, args.agents)
         cpu_line['c_oracle_f32_1core_env_steps_per_s'] = c_oracle_rate(args.envs, args.agents)
         if preload:  # the all-core legs fork worker pools: not from a GPU-initialised (profiled) process
@@ -414,10 +455,13 @@ def main():
     # Clock ramp.  A chip that has been idle (the CPU baseline above runs for ~20 s) reaches its sustained clock only
     # after tens of milliseconds of load: with the driver's `--warmup 5` (3 ms of launches) the timed launches ran
     # 6 % slower than after 50 (profiles/README.md).  So the SAME launch runs untimed for --ramp-ms first; the env is
-    # then reset again, so the W warm-up and K timed launches below start from the state they always started from.
+    # then put back into its state from before the ramp, so the W warm-up and K timed launches below always start from
+    # the same state: every reset draws from the env's episode count, which the ramp's own episodes advance by a number
+    # that depends on how long the ramp took.
     ramp = dict(launches=0, ms=0.0)
+    env.reset()
     if not STUB and args.ramp_ms > 0:
-        env.reset()
+        start = env.get_state()
         t_r = time.perf_counter()
         while (time.perf_counter() - t_r) * 1e3 < args.ramp_ms:
             for i in range(8):
@@ -425,7 +469,7 @@ def main():
             sync()
             ramp['launches'] += 8
         ramp['ms'] = (time.perf_counter() - t_r) * 1e3
-    env.reset()
+        env.set_state(**start)
     run(W, 0)
     if shard is not None:
         try:
@@ -452,10 +496,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # N > 1: what the sampled exchange costs the headline -- the same K launches once more WITHOUT it (same bracket);
-    # reported beside `value` in multi_gpu.sampled_exchange, never instead of it
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, slots[(W + K - 1) % RING][1])
+
+    # N > 1, --full: what the sampled exchange costs the headline -- the same K launches once more WITHOUT it (same
+    # bracket); reported beside `value` in multi_gpu.sampled_exchange, never instead of it
     elapsed_plain = None
-    if use_dist:
+    if use_dist and args.full:
         sync()
         dist.barrier()
         sync()
@@ -489,7 +536,7 @@ def main():
     # the last timed launch went to slot (W + K - 1) % RING; an env terminates at its 25th, 50th, ... step, and the
     # W + K launches ran T steps each from a fresh reset: step index s of that launch is global step
     # (W + K - 1) * T + s
-    n_done = W + K + (K if use_dist else 0)   # launches since the reset (the exchange-free repeat included)
+    n_done = W + K + (K if elapsed_plain is not None else 0)   # launches since the reset (the exchange-free repeat included)
     last_view = slots[(n_done - 1) % RING][1]
     s_term = (-((n_done - 1) * T + 1)) % 25
     finite = bool(torch.isfinite(last_view['obs']).all().item())
@@ -515,7 +562,7 @@ def main():
         except Exception:
             store = None
     FAIL_KEY, LINE_KEY = 'pw_bench_failed', 'pw_bench_line_out'
-    if args.scenario == 'simple_spread' and not os.environ.get('PW_BENCH_NO_POLICY'):
+    if args.full and args.scenario == 'simple_spread' and not os.environ.get('PW_BENCH_NO_POLICY'):
         import threading
 
         def _give_up(why):
@@ -566,7 +613,7 @@ def main():
             'config': {'workload': '%s N=%d L=%d, B=%d envs per GPU (global %d), local obs D=%d, episode 25 with '
                                    'auto-reset, uniform int32 action indices; 1 bench step = 1 pw_rollout launch = %d '
                                    'batched env steps; %d launches timed after %d warm-up launches (before those: an '
-                                   'untimed clock ramp of %d of the same launches, %.0f ms, then a reset)'
+                                   'untimed clock ramp of %d of the same launches, %.0f ms, then the state from before it)'
                                    % (args.scenario, N, env.num_landmarks, B, world * B, D, T, K, W, ramp['launches'], ramp['ms']),
                        'clock_ramp': ramp,
                        'env_steps_per_step': world * B * T, 'batched_env_steps_per_launch': T,
@@ -602,7 +649,7 @@ def main():
                                  'the algorithmic bytes; frac_vs_store_ceiling = counter traffic (97 %% stores) against the '
                                  '%.1f TB/s a pure store stream reaches' % (env.bytes_per_env_step, STORE_CEILING_GBPS / 1e3)},
         }
-        if world == 1:
+        if world == 1 and args.full:
             line['cpu_baseline'] = cpu_line
         line_holder['line'] = line
     if watchdog is not None:
@@ -629,31 +676,32 @@ def main():
         watchdog.cancel()
     if rank == 0:
         line = line_holder['line']
-        line['policy_in_loop'] = policy_line
-        # Compact (config -> value, frac) strings where a reader of a truncated record still finds them: short scalars inside
-        # `config` (records keep scalars of config / roofline and cut strings at ~120 characters) and once more as the LAST key
-        # of the line (a tail of the line keeps its end); the long arrays stay under other_configs / policy_in_loop.
-        summ = _compact_summary(line.get('other_configs'), policy_line)
-        line['config'].update(summ)
-        if use_dist:
-            # what matters at N > 1, at the top level of the line: the FULL gather's per-link rate and completeness
-            # (north_star's collective, measured in the policy-in-the-loop extra) and the cost of the sampled exchange
-            g = policy_line.get('gather') if isinstance(policy_line, dict) else None
-            line['multi_gpu'] = dict(
-                full_gather=None if not g else dict(
-                    GBps_per_link=g['GBps_per_link'], GBps_root_ingest=g['GBps_root_ingest'], peers=world - 1,
-                    bytes_per_env_step=g['bytes_per_env_step'], transitions_ingested_root=g['transitions_ingested_root'],
-                    expected_transitions=g['expected_transitions'], complete=g['transitions_ingested_root'] == g['expected_transitions'],
-                    root_receive_bytes=3 * (world - 1) * g['bytes_per_chunk_per_rank'],   # three slots of one block per peer
-                    env_steps_per_s=policy_line.get('value'), error=g['error']),
-                sampled_exchange=dict(value_with_exchange=line['value'],
-                                      value_without_exchange=world * B * T * K / elapsed_plain,
-                                      overhead_frac=1.0 - elapsed_plain / elapsed, launches_timed=K,
-                                      rows_per_exchange=None if shard is None else shard.R * world,
-                                      error=exchange_state['error']),
-                note='value = sharded rollout + sampled exchange (a full gather at this rate would need TB/s per peer: '
-                     'DESIGN.md 6); the full gather is measured with the policy in the loop')
-        line['other_configs_summary'] = summ
+        if args.full:
+            line['policy_in_loop'] = policy_line
+            # Compact (config -> value, frac) strings where a reader of a truncated record still finds them: short scalars inside
+            # `config` (records keep scalars of config / roofline and cut strings at ~120 characters) and once more as the LAST key
+            # of the line (a tail of the line keeps its end); the long arrays stay under other_configs / policy_in_loop.
+            summ = _compact_summary(line.get('other_configs'), policy_line)
+            line['config'].update(summ)
+            if use_dist:
+                # what matters at N > 1, at the top level of the line: the FULL gather's per-link rate and completeness
+                # (north_star's collective, measured in the policy-in-the-loop extra) and the cost of the sampled exchange
+                g = policy_line.get('gather') if isinstance(policy_line, dict) else None
+                line['multi_gpu'] = dict(
+                    full_gather=None if not g else dict(
+                        GBps_per_link=g['GBps_per_link'], GBps_root_ingest=g['GBps_root_ingest'], peers=world - 1,
+                        bytes_per_env_step=g['bytes_per_env_step'], transitions_ingested_root=g['transitions_ingested_root'],
+                        expected_transitions=g['expected_transitions'], complete=g['transitions_ingested_root'] == g['expected_transitions'],
+                        root_receive_bytes=3 * (world - 1) * g['bytes_per_chunk_per_rank'],   # three slots of one block per peer
+                        env_steps_per_s=policy_line.get('value'), error=g['error']),
+                    sampled_exchange=dict(value_with_exchange=line['value'],
+                                          value_without_exchange=world * B * T * K / elapsed_plain,
+                                          overhead_frac=1.0 - elapsed_plain / elapsed, launches_timed=K,
+                                          rows_per_exchange=None if shard is None else shard.R * world,
+                                          error=exchange_state['error']),
+                    note='value = sharded rollout + sampled exchange (a full gather at this rate would need TB/s per peer: '
+                         'DESIGN.md 6); the full gather is measured with the policy in the loop')
+            line['other_configs_summary'] = summ
         # key order of the printed line: everything short first -- multi_gpu (the full gather's per-link rate and completeness)
         # right behind roofline / cpu_baseline -- the long arrays (policy_in_loop, other_configs) after it, the compact summary last:
         # a record that keeps only the head or only the tail of the line still carries the figures that matter

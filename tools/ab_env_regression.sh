@@ -53,13 +53,14 @@ for tag in sorted(set(os.path.basename(f).split('_', 1)[1].rsplit('_', 1)[0] for
         print('%-10s old %.4g (%.4g .. %.4g)   new %.4g (%.4g .. %.4g)   new/old %.4f'
               % (tag, mo, min(v['old']), max(v['old']), mn, min(v['new']), max(v['new']), mn / mo))
 EOF
-# the driver's own view: those figures come from other_configs INSIDE the default run (after the headline and the policy extra)
+# the driver's own view: those figures come from other_configs INSIDE the --full run (after the headline and the policy extra)
 unset PW_BENCH_NO_POLICY
 [ -n "$AB_NO_FULL" ] && exit 0
 for rep in 1 2; do
   for side in old new; do
     D=$R; [ $side = old ] && D=$OLD
-    ( cd $D && python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 ) > $O/full_${side}_$rep.json 2> $O/full_${side}_$rep.err || echo "full $side $rep FAILED"
+    F=; grep -q -- "'--full'" $D/bench.py && F=--full   # trees before the option ran the extras by default
+    ( cd $D && python3 bench.py $F --no-cpu-baseline --steps 20 --warmup 5 ) > $O/full_${side}_$rep.json 2> $O/full_${side}_$rep.err || echo "full $side $rep FAILED"
     python3 - $O/full_${side}_$rep.json $side $rep <<'EOF'
 import json, sys
 try:
