@@ -203,6 +203,15 @@ __device__ __forceinline__ void act_fetch_wait3() { asm volatile("s_waitcnt vmcn
 __device__ __forceinline__ void act_fetch_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 constexpr int kActRingBytes = 4 * kWave * (int)sizeof(int32_t);  // per physics wave
 
+// The uniform of the Gumbel noise from one Philox word: (top 24 bits + 1/2) * 2^-24, strictly inside (0, 1).  The top word
+// (w >> 8 == 2^24 - 1) forms 16777215.5f, which rounds half-to-even to 2^24, i.e. u == 1.0 and log(-log u) == -inf (that logit
+// would win whatever it is); the clamp sends it to the largest float below 1 and leaves every other word's value unchanged.
+// Every actor form draws through this one helper (oracle/actor_oracle.py restates it).
+__device__ __forceinline__ float pw_gumbel_uniform(const uint32_t w)
+{
+    return __builtin_fminf(((float)(w >> 8) + 0.5f) * 5.9604644775390625e-8f, 0x1.fffffep-1f);
+}
+
 // pw_softplus (include/pworld_math.h, contract revision 3): the same operations, so the same bits, but branch-free --
 // the polynomial runs on a clamped argument and the exact-zero cut / NaN pass-through ride on the power-of-two scale
 // factor, which is computed beside the polynomial, not after it.  The dependent chain from x to the result is 15

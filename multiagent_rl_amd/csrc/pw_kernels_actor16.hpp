@@ -281,7 +281,7 @@ __device__ __forceinline__ void actor16_draw_noise(const ActorFusedArgs &A, floa
         float nz[4];
 #pragma unroll
         for (int wq = 0; wq < 4; ++wq) {   // (the words past OUT serve no logit: their values are never looked at)
-            const float uo = ((float)(u[wq] >> 8) + 0.5f) * 5.9604644775390625e-8f;  // (0, 1)
+            const float uo = pw_gumbel_uniform(u[wq]);  // in (0, 1)
             nz[wq] = __logf(-__logf(uo));
         }
         reinterpret_cast<float4 *>(s_noise)[idx] = make_float4(nz[0], nz[1], nz[2], nz[3]);
@@ -475,7 +475,7 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
                                  (uint32_t)A.seed, (uint32_t)(A.seed >> 32), u);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float uo = ((float)(u[i] >> 8) + 0.5f) * 5.9604644775390625e-8f;  // (0, 1)
+                    const float uo = pw_gumbel_uniform(u[i]);  // in (0, 1)
                     p[i] = lg[i] - __logf(-__logf(uo));
                 }
             }

@@ -357,7 +357,7 @@ __global__ void __launch_bounds__(256) pw_actor_head_kernel(const float *__restr
         float bv = 0.0f;
 #pragma unroll
         for (int o = 0; o < 5; ++o) {
-            const float uo = ((float)(u[o] >> 8) + 0.5f) * 5.9604644775390625e-8f;  // (0, 1)
+            const float uo = pw_gumbel_uniform(u[o]);  // in (0, 1)
             const float v = acc[o] - __logf(-__logf(uo));
             if (o == 0 || v > bv) { bv = v; best = o; }
         }
@@ -609,7 +609,7 @@ __device__ __forceinline__ void actor_forward_wg(const ActorFusedArgs &A, const 
                              (uint32_t)A.seed, (uint32_t)(A.seed >> 32), u);
             const int w = o & 3;
             const uint32_t uw = w == 0 ? u[0] : w == 1 ? u[1] : w == 2 ? u[2] : u[3];
-            const float uo = ((float)(uw >> 8) + 0.5f) * 5.9604644775390625e-8f;  // (0, 1)
+            const float uo = pw_gumbel_uniform(uw);  // in (0, 1)
             S.s_lg[idx] = acc - __logf(-__logf(uo));
         }
     }

@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
             for (int wq = 0; wq < 4; ++wq) {
                 const int o = 4 * (int)blk + wq;
                 if (o < OUT) {
-                    const float uo = ((float)(u[wq] >> 8) + 0.5f) * 5.9604644775390625e-8f;  // (0, 1)
+                    const float uo = pw_gumbel_uniform(u[wq]);  // in (0, 1)
                     S.s_noise[rr * OUT + o] = __logf(-__logf(uo));
                 }
             }

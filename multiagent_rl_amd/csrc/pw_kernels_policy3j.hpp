@@ -253,7 +253,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
                              (uint32_t)A.seed, (uint32_t)(A.seed >> 32), u);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const float uo = ((float)(u[i] >> 8) + 0.5f) * 5.9604644775390625e-8f;  // (0, 1)
+                const float uo = pw_gumbel_uniform(u[i]);  // in (0, 1)
                 nz[i] = __logf(-__logf(uo));
             }
         }

@@ -17,6 +17,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 from oracle import c_oracle as co  # noqa: E402  (checker only)
+from tests.test_gpu_actor_reference import assert_rollout_actions_match_f64  # noqa: E402
 from tests.test_gpu_parity import _assert_same_bits, _np  # noqa: E402
 
 FORMS = dict(default=0, v3=3, v3j=4)
@@ -73,7 +74,8 @@ def test_spread_policy_rollout_outputs_equal_the_oracle_on_its_own_actions(B, N,
     cfg = co.make_config('simple_spread', N, max_episode_len=25, auto_reset=True, seed=21)
     o32 = co.COracle(cfg, B, np.float32)
     actor = FusedActor(ActorNetwork(env.obs_dim, 5).cuda().eval(), seed=9)
-    _assert_same_bits(_np(env.reset()), o32.reset(), 'reset obs')
+    obs0 = o32.reset()
+    _assert_same_bits(_np(env.reset()), obs0, 'reset obs')
     got = actor.rollout(env, T)
     if form == 'default':                 # automatic choice: form 3 wherever 16 environments per workgroup fit its LDS,
         assert env.last_kernel() == KERNEL_OF_FORM[3 if N <= 12 else 4], env.last_kernel()   # its just-in-time variant beyond
@@ -85,10 +87,15 @@ def test_spread_policy_rollout_outputs_equal_the_oracle_on_its_own_actions(B, N,
     resets = _replay_through_oracle(o32, got, T)
     assert resets == T // 25
     _assert_final_state(env, o32)
+    # the actions: the float64 actor on the rows the policy saw (the reset rows, then each step's post-reset rows), keyed at step t
+    rows = np.concatenate([obs0[None], _np(got['obs'][:-1])], 0)
+    assert_rollout_actions_match_f64(actor.actor, 9, 0, rows, a, 'spread %s B=%d N=%d' % (form, B, N))
     # a second chunk continues from the stored state (and the oracle from its own)
     got2 = actor.rollout(env, 3)
     _replay_through_oracle(o32, got2, 3)
     _assert_final_state(env, o32)
+    rows2 = np.concatenate([_np(got['obs'][-1:]), _np(got2['obs'][:-1])], 0)
+    assert_rollout_actions_match_f64(actor.actor, 9, T, rows2, _np(got2['act']), 'spread %s B=%d N=%d chunk 2' % (form, B, N))
 
 
 @pytest.mark.parametrize('B,N,T', [(24, 48, 27), (11, 33, 26), (70, 40, 4), (17, 31, 27), (40, 50, 26), (33, 32, 5)],
@@ -125,6 +132,17 @@ def test_spread_policy_rollout_with_rows_longer_than_64_numbers(B, N, T):
     want = lg.argmax(-1).to(torch.int32)
     assert clear.float().mean().item() > 0.8
     assert torch.equal(got['act'][clear], want[clear])
+    assert_rollout_actions_match_f64(net, 9, 0, _np(rows), _np(got['act']), 'spread 3j B=%d N=%d sharpened' % (B, N))
+    # the same on an unsharpened head (the noise decides most rows), from a fresh environment
+    env_u = make_batched_env('simple_spread', B, n=N, auto_reset=True, max_episode_len=25, seed=33)
+    o_u = co.COracle(cfg, B, np.float32)
+    net_u = ActorNetwork(env.obs_dim, 5).cuda().eval()
+    obs0_u = o_u.reset()
+    _assert_same_bits(_np(env_u.reset()), obs0_u, 'reset obs')
+    got_u = FusedActor(net_u, seed=2 ** 32 + 9).rollout(env_u, T)
+    assert _replay_through_oracle(o_u, got_u, T) == T // 25
+    rows_u = np.concatenate([obs0_u[None], _np(got_u['obs'][:-1])], 0)
+    assert_rollout_actions_match_f64(net_u, 2 ** 32 + 9, 0, rows_u, _np(got_u['act']), 'spread 3j B=%d N=%d' % (B, N))
     env.set_dispatch(policy_form=3)                                # the plain third form refuses such rows instead of running something else
     with pytest.raises(Exception, match='longer than 64'):
         actor.rollout(env, 2)
@@ -141,13 +159,16 @@ def test_tag_policy_rollout_outputs_equal_the_oracle_on_its_own_actions(B, adv, 
     cfg = co.make_config('simple_tag', N, num_adversaries=adv, max_episode_len=25, auto_reset=True, seed=31)
     o32 = co.COracle(cfg, B, np.float32)
     actor = FusedActor(ActorNetwork(env.obs_dim, 5).cuda().eval(), seed=9)
-    _assert_same_bits(_np(env.reset()), o32.reset(), 'reset obs')
+    obs0 = o32.reset()
+    _assert_same_bits(_np(env.reset()), obs0, 'reset obs')
     got = actor.rollout(env, T)
     assert 'policy_rollout_tag' in env.last_kernel(), env.last_kernel()
     assert len(np.unique(_np(got['act']))) == 5
     assert _replay_through_oracle(o32, got, T) == T // 25
     assert float(got['rew'].abs().sum()) > 0
     _assert_final_state(env, o32)
+    rows = np.concatenate([obs0[None], _np(got['obs'][:-1])], 0)
+    assert_rollout_actions_match_f64(actor.actor, 9, 0, rows, _np(got['act']), 'tag %d+%d B=%d' % (adv, good, B))
 
 
 @pytest.mark.parametrize('B,T', [(4096, 53), (100, 55), (17, 26)])
@@ -160,13 +181,16 @@ def test_reference_policy_rollout_outputs_equal_the_oracle_on_its_own_actions(B,
     cfg = co.make_config('simple_reference', max_episode_len=25, auto_reset=True, seed=17)
     o32 = co.CRefOracle(cfg, B, np.float32)
     actor = FusedActor(ActorNetwork(env.obs_dim, [5, 10]).cuda().eval(), seed=9)
-    _assert_same_bits(_np(env.reset()), o32.reset(), 'reset obs')
+    obs0 = o32.reset()
+    _assert_same_bits(_np(env.reset()), obs0, 'reset obs')
     got = actor.rollout(env, T)
     assert 'policy_rollout_ref' in env.last_kernel(), env.last_kernel()
     a = _np(got['act'])
     assert a.shape == (T, B, 2, 2) and a[..., 0].max() <= 4 and 4 < a[..., 1].max() <= 9
     assert _replay_through_oracle(o32, got, T, two_head=True) == T // 25
     _assert_final_state(env, o32, extra=('comm', 'goal'))
+    rows = np.concatenate([obs0[None], _np(got['obs'][:-1])], 0)
+    assert_rollout_actions_match_f64(actor.actor, 9, 0, rows, a, 'reference B=%d' % B)
 
 
 def test_bf16x3_policy_rollout_environment_half_is_still_exact():
@@ -180,10 +204,15 @@ def test_bf16x3_policy_rollout_environment_half_is_still_exact():
     env.set_actor_precision('bf16x3')
     cfg = co.make_config('simple_spread', N, max_episode_len=25, auto_reset=True, seed=21)
     o32 = co.COracle(cfg, B, np.float32)
-    _assert_same_bits(_np(env.reset()), o32.reset(), 'reset obs')
-    got = FusedActor(ActorNetwork(env.obs_dim, 5).cuda().eval(), seed=9).rollout(env, T)
+    obs0 = o32.reset()
+    _assert_same_bits(_np(env.reset()), obs0, 'reset obs')
+    net = ActorNetwork(env.obs_dim, 5).cuda().eval()
+    got = FusedActor(net, seed=9).rollout(env, T)
     assert _replay_through_oracle(o32, got, T) == 2
     _assert_final_state(env, o32)
+    # its logits stay within 2e-5 of float32 PyTorch: the actions are the float64 prediction wherever the margin exceeds 1e-4
+    rows = np.concatenate([obs0[None], _np(got['obs'][:-1])], 0)
+    assert_rollout_actions_match_f64(net, 9, 0, rows, _np(got['act']), 'spread bf16x3 B=%d N=%d' % (B, N))
 
 
 def _oracle_transitions(o32, obs0, acts, two_head=False):
@@ -229,13 +258,16 @@ def test_collect_one_launch_ring_rows_equal_oracle_transitions(scenario, B, kw):
     o32 = (co.CRefOracle if two else co.COracle)(cfg, B, np.float32)
     T = 57
     mem = ReplayBuffer(B * 64, N, env.obs_dim, **(dict(act_heads=(5, 10)) if two else {}))
-    ro = BatchedRollout(env, FusedActor(ActorNetwork(env.obs_dim, [5, 10] if two else 5).cuda().eval(), seed=7), mem)
+    net = ActorNetwork(env.obs_dim, [5, 10] if two else 5).cuda().eval()
+    ro = BatchedRollout(env, FusedActor(net, seed=7), mem)
     obs0 = o32.reset()
     _assert_same_bits(_np(ro.obs), obs0, 'reset obs')
     ro.collect_one_launch(T, chunk=20)                                          # chunks of 20, 20, 17
     assert len(mem) == T * B
     acts = _np(mem.act[:T * B]).astype(np.int32).reshape((T, B, N, 2) if two else (T, B, N))
     want_obs, want_next, want_rew = _oracle_transitions(o32, obs0, acts, two)
+    assert_rollout_actions_match_f64(net, 7, 0, want_obs.reshape((T, B) + want_obs.shape[1:]), acts,
+                                     'ring rows %s B=%d N=%d' % (scenario, B, N))
     _assert_same_bits(_np(mem.obs[:T * B]).reshape(want_obs.shape), want_obs, 'ring obs')
     _assert_same_bits(_np(mem.next_obs[:T * B]).reshape(want_next.shape), want_next, 'ring next_obs')
     _assert_same_bits(_np(mem.rew[:T * B]).reshape(-1), want_rew, 'ring rew')
