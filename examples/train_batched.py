@@ -10,7 +10,9 @@ For every scenario and seed count ``cnt`` it does what main.py does -- build the
 (:51-58), build ``ActorNetwork`` / ``CriticNetwork`` (:60-61), hand everything to the rollout-and-learn loop (:65-67) -- with
 ``multiagent_rl_amd.train.train_batched`` in the place of ``experiments.run.run``.  ``--reference`` takes the Trainer and the
 critic from the reference checkout on ``sys.path`` (``rls.agent.multiagent.ddpg_gumbel_fix``); otherwise the small stock-PyTorch
-learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).
+learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).  ``--critic attention`` gives
+it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``), ``--fused-targets`` runs its target networks'
+forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -39,7 +41,15 @@ def main(argv=None):
                     help='process group of a multi-rank run: nccl (= RCCL, one GPU per rank) or gloo (the blocks of the full gather '
                          'travel through pinned host buffers; ranks may share a GPU -- RCCL refuses that)')
     ap.add_argument('--reference', action='store_true', help="use the reference's Trainer / CriticNetwork (rls on sys.path)")
+    ap.add_argument('--critic', default='standin', choices=['standin', 'attention'],
+                    help="standin: madr_learner's mean-pooling critic; attention: multiagent_rl_amd.critic.CriticNetwork, the "
+                         "reference's LSTM + attention architecture (its saved *_critic.pt files load into it)")
+    ap.add_argument('--fused-targets', action='store_true',
+                    help='target actor and target critic of the learner run on the HIP kernels (accelerate_trainer(.., targets=True); '
+                         'needs the attention critic)')
     args = ap.parse_args(argv)
+    if args.fused_targets and args.critic != 'attention' and not args.reference:
+        ap.error('--fused-targets needs --critic attention (the HIP critic is the LSTM + attention architecture)')
 
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')   # dmabuf IPC for multi-process GPU work (read at the first GPU call)
     import torch
@@ -52,6 +62,16 @@ def main(argv=None):
         from rls.model.ac_network_multi_gumbel import CriticNetwork
     else:
         from madr_learner import CriticNetwork, Trainer
+        if args.critic == 'attention':
+            from multiagent_rl_amd.critic import CriticNetwork
+    if args.fused_targets:
+        from multiagent_rl_amd.policy import accelerate_trainer
+        plain_trainer = Trainer
+
+        def Trainer(*a, **k):   # train_batched builds the learner itself: patch the instance it gets
+            learner = plain_trainer(*a, **k)
+            accelerate_trainer(learner, targets=True)
+            return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))

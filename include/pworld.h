@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 106 /* 0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 107 /* 0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -517,6 +517,21 @@ int pw_debug_math(int32_t fn, const float *x, float aux, float *y, int64_t n, vo
  * rounded one, from every 1-ulp-accurate starting value; significand not all ones; inside the division chain's range): the
  * host-side decision behind the K1 kernel instantiations.  The canonical margin 1e-3 qualifies. */
 int pw_margin_one_correction(float contact_margin);
+
+/* The learner's critic (rls/model/ac_network_multi_gumbel.py CriticNetwork) and, optionally, the TD target of
+ * ddpg_gumbel_fix.py:148-154 as ONE launch: q [b] = dense2(relu(attention(LSTM(relu(dense1([obs | action])))))) in float32 --
+ * one-layer LSTM (hidden 64, gates i, f, g, o, zero initial state) over the agent axis, score_t = <out_t, h_N>, softmax over t,
+ * weighted sum.  obs [b,N,obs_dim].  Action, exactly one of: act_idx int32 [b,N] (n_act1 = 0) or [b,N,2] (two heads, widths
+ * n_act0 | n_act1; an index outside its head selects no column) or act_vec float [b,N,n_act0 + n_act1].  An exact one-hot
+ * act_vec and the equal indices give the same bits.  Weights in nn.Module layout: w1 [64, obs_dim + A] / b1 = dense1.module,
+ * w_ih / w_hh [256,64], b_ih / b_hh [256] = lstm.*_l0, w2 [1,64] / b2 [1] = dense2.  With rew [b], done [b] (float) and y [b]
+ * (all three or none): y = rew + gamma * q * (1 - done), evaluated left to right without contraction on the q this launch
+ * writes.  N in [1, 64], obs_dim in [1, 104], n_act0 + n_act1 <= 16, any b >= 1.  All pointers are device memory. */
+int pw_critic_forward(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
+                      const float *w1, const float *b1, const float *w_ih, const float *w_hh, const float *b_ih,
+                      const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
+                      const float *rew /* or NULL */, const float *done /* or NULL */, float gamma, float *q,
+                      float *y /* or NULL */, void *stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pworld_policy.hip')]
+SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pworld_policy.hip'),
+        os.path.join(HERE, 'csrc', 'pworld_critic.hip')]
 OUT = os.path.join(HERE, 'libpworld.so')
 OBJ_DIR = os.path.join(HERE, 'csrc', '_obj')  # git-ignored (*.o); objects are kept so that one unit rebuilds alone
 DEPS = [os.path.join(HERE, 'csrc', f) for f in sorted(os.listdir(os.path.join(HERE, 'csrc'))) if f.endswith(('.hip', '.hpp'))] + \
@@ -55,7 +56,8 @@ def _stale(obj):
 
 
 def unit_sources(unit):
-    """Every file translation unit `unit` ('pworld' = environment / replay / wire, 'pworld_policy' = actor and policy rollouts) is
+    """Every file translation unit `unit` ('pworld' = environment / replay / wire, 'pworld_policy' = actor and policy rollouts,
+    'pworld_critic' = the learner's critic forward) is
     compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
     sources (no compiler, no recorded paths), so it gives the same answer in any copy of the tree."""
     import re
@@ -118,7 +120,7 @@ def build(force=False, verbose=False):
     tag = _flag_tag(flags)
     procs = []
     objs = []
-    for src in SRCS:  # the two units compile in parallel
+    for src in SRCS:  # the units compile in parallel
         obj = os.path.join(OBJ_DIR, '%s.%s.o' % (os.path.basename(src)[:-4], tag))
         objs.append(obj)
         if not force and not _stale(obj):   # an actor experiment leaves the env unit alone and vice versa

@@ -1,0 +1,153 @@
+"""The learner's critic: the reference's architecture as a host module, and its no-gradient forward as one HIP launch.
+
+``CriticNetwork`` has the layer structure AND parameter names of ``rls/model/ac_network_multi_gumbel.py:70-146``
+(``dense1.module``, ``lstm``, ``dense2``), so ``<scenario>_fin_<cnt>_critic.pt`` files saved by the reference's Trainer
+(``ddpg_gumbel_fix.py:221-229``) load unchanged.  It is the autograd path: the learner keeps it for ``critic(s0, a0)`` and the
+actor loss (the gradient path stays stock PyTorch-ROCm).
+
+``FusedCritic`` evaluates the same module with ``pw_critic_forward`` -- dense1, the LSTM over the agent axis, the attention and
+dense2 in ONE launch instead of MIOpen's many-kernel RNN path, two ``bmm``s, a softmax and the glue -- for the half of
+``Trainer.optimize`` that needs no gradient: ``q_next = target_critic(s1, a1)`` and ``y = r + GAMMA * q_next * (1 - d)``
+(``ddpg_gumbel_fix.py:148-154``).  ``accelerate_trainer(trainer, targets=True)`` hands both target networks of an unmodified
+Trainer to the HIP kernels.
+"""
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .policy import FusedActor, TimeDistributed
+from .policy import accelerate_trainer  # noqa: F401  (the one entry point; ``targets=True`` uses the classes below)
+
+
+class CriticNetwork(nn.Module):
+    """Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis -> attention of every step's output against the final
+    hidden state (dot product, softmax over the agents, weighted sum) -> ReLU -> Linear(64, out_dim).
+    ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``[b, out_dim]``."""
+
+    def __init__(self, input_dim, out_dim=1):
+        super().__init__()
+        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
+        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+        self.dense2 = nn.Linear(64, out_dim)
+
+    def forward(self, obs, action):
+        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
+        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
+        steps, (h_n, _) = self.lstm(hid, None)                            # [b,N,64], [1,b,64]
+        score = torch.bmm(steps, h_n[-1].unsqueeze(2)).squeeze(2)         # <out_t, h_N>  [b,N]
+        weight = F.softmax(score, dim=1)
+        ctx = torch.bmm(steps.transpose(1, 2), weight.unsqueeze(2)).squeeze(2)
+        return self.dense2(F.relu(ctx))
+
+
+class FusedCritic(object):
+    """``critic`` (a ``CriticNetwork`` -- this module's or the reference's -- on the GPU) evaluated by ``pw_critic_forward``.
+
+    The kernel reads the parameters where the module keeps them (``nn.Module`` layout, no packed image), so every call computes
+    with the module's CURRENT values: a soft update in place between two calls needs no ``refresh()``.  No gradient flows through
+    it: results have ``requires_grad == False``.  ``heads``: the widths of a two-head (MultiDiscrete) joint action, needed only
+    for index actions of shape ``[b,N,2]``."""
+
+    def __init__(self, critic, heads=None):
+        import ctypes as C
+        from . import _lib
+        self._C, self._lib_mod, self.lib = C, _lib, _lib.load()
+        self.critic = critic
+        self.heads = None if heads is None else tuple(int(h) for h in heads)
+        lin1, lstm, lin2 = critic.dense1.module, critic.lstm, critic.dense2
+        if not (lin1.out_features == 64 and lstm.input_size == 64 and lstm.hidden_size == 64 and lstm.num_layers == 1
+                and not lstm.bidirectional and lstm.batch_first and lin2.in_features == 64 and lin2.out_features == 1):
+            raise ValueError('FusedCritic serves Linear(D + A, 64) -> LSTM(64 -> 64) -> attention -> Linear(64, 1)')
+        self._params()
+
+    def _params(self):
+        c = self.critic
+        lin1, lstm, lin2 = c.dense1.module, c.lstm, c.dense2
+        ps = (lin1.weight, lin1.bias, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, lin2.weight, lin2.bias)
+        dev = ps[0].device
+        if dev.type != 'cuda':
+            raise RuntimeError('FusedCritic needs the critic on the GPU (no CPU fallback)')
+        for p in ps:   # read in place: anything else would be a snapshot that an in-place update leaves behind
+            if p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError('FusedCritic reads contiguous float32 parameters on one GPU')
+        self.device = dev
+        return ps
+
+    @torch.no_grad()
+    def _run(self, obs, act, rew=None, done=None, gamma=0.0):
+        ps = self._params()
+        if obs.dim() != 3:
+            raise ValueError('obs must be [b, N, D]')
+        b, N, D = obs.shape
+        A = ps[0].shape[1] - D
+        f32 = lambda t: t.detach().to(device=self.device, dtype=torch.float32).contiguous()  # noqa: E731
+        x = f32(obs)
+        if isinstance(act, (list, tuple)):
+            act = torch.cat(list(act), dim=-1)
+        idx = vec = None
+        if act.dtype.is_floating_point:
+            if tuple(act.shape) != (b, N, A):
+                raise ValueError('float action must be [b, N, %d], got %r' % (A, tuple(act.shape)))
+            vec, n0, n1 = f32(act), A, 0
+        else:
+            idx = act.detach().to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(idx.shape) == (b, N):
+                n0, n1 = A, 0
+            elif tuple(idx.shape) == (b, N, 2):
+                if self.heads is None or len(self.heads) != 2 or sum(self.heads) != A:
+                    raise ValueError('index actions [b, N, 2] need FusedCritic(critic, heads=(n0, n1)) with n0 + n1 = %d' % A)
+                n0, n1 = self.heads
+            else:
+                raise ValueError('index action must be [b, N] or [b, N, 2], got %r' % (tuple(idx.shape),))
+        q = torch.empty(b, dtype=torch.float32, device=self.device)
+        y = r = d = None
+        if rew is not None:
+            r, d = f32(rew).reshape(-1), f32(done).reshape(-1)
+            if r.numel() != b or d.numel() != b:
+                raise ValueError('rew and done must hold one number per batch row')
+            y = torch.empty(b, dtype=torch.float32, device=self.device)
+        p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
+        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        self._lib_mod.check(self.lib.pw_critic_forward(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D,
+                                                       p(r), p(d), float(gamma), p(q), p(y), stream))
+        return q, y
+
+    def q(self, obs, act):
+        """obs [b,N,D]; act int [b,N] / [b,N,2] (indices) or float [b,N,A] -> q [b]."""
+        return self._run(obs, act)[0]
+
+    def td_target(self, next_obs, act, rew, done, gamma, return_q=False):
+        """-> y [b] = rew + gamma * q(next_obs, act) * (1 - done) from one launch (``return_q``: also that launch's q)."""
+        q, y = self._run(next_obs, act, rew, done, gamma)
+        return (y, q) if return_q else y
+
+    def forward(self, obs, action):
+        """As the module: ``[b, 1]``; a list of action tensors is concatenated along the last axis."""
+        return self._run(obs, action)[0].unsqueeze(1)
+
+    __call__ = forward
+
+
+class _FusedTarget(object):
+    """A target network of a Trainer whose ``forward`` / ``__call__`` run on a HIP kernel; every other attribute
+    (``parameters``, ``state_dict``, ``load_state_dict``, ``eval``, ``train``, ``to``, ...) is the wrapped module's."""
+
+    def __init__(self, module, forward):
+        self.__dict__['module'] = module
+        self.__dict__['forward'] = forward
+
+    def __call__(self, *a, **k):
+        return self.forward(*a, **k)
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__['module'], name)
+
+
+def fuse_targets(trainer):
+    """``trainer.target_actor`` / ``trainer.target_critic`` -> wrappers on ``FusedActor.logits`` / ``FusedCritic``.
+    Returns ``(fused_target_actor, fused_target_critic)``; the caller refreshes the actor's snapshot after the target moves."""
+    fa = FusedActor(trainer.target_actor, seed=0)
+    fc = FusedCritic(trainer.target_critic)
+    trainer.target_actor = _FusedTarget(trainer.target_actor, fa.logits)
+    trainer.target_critic = _FusedTarget(trainer.target_critic, fc.forward)
+    return fa, fc

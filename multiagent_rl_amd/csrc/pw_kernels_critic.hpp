@@ -1,0 +1,256 @@
+// pw_kernels_critic.hpp -- part of libpworld.so (translation unit csrc/pworld_critic.hip includes it).
+// The learner's critic (rls/model/ac_network_multi_gumbel.py CriticNetwork) as ONE launch: dense1 + ReLU on [obs | action], a
+// one-layer LSTM (hidden 64) over the agent axis, dot-product attention of every step's output against the final hidden state,
+// softmax over the agents, weighted sum, ReLU, dense2 -> q [b]; optionally the TD target y = r + gamma q (1 - d) from the same q.
+//
+// Design (the one-launch actor's, pw_kernels_actor16.hpp / pw_kernels_policy3.hpp, restated for a unidirectional 64-unit LSTM):
+//   * a workgroup of 512 threads owns R batch rows (R = 16; 8 when N > 32, see "LDS") = the 16 columns of v_mfma_f32_16x16x4_f32;
+//   * wave w owns hidden units 8 w .. 8 w + 7 as two 16-row tiles, tile row = 4 (unit within tile) + gate: after the matrix
+//     instructions a lane's four accumulator registers ARE the gates i, f, g, o of one unit for one batch row, so the cell update
+//     (lstm_cell of pw_kernels_policy.hpp: fast_sigmoid / fast_tanh) needs no exchange.  W_ih and W_hh of the wave's 32 gate rows
+//     stay in registers for the whole launch (64 per lane; + the wave's W1 tile, up to 30), read straight from the nn.Module layout [256][64];
+//   * dense1 runs just in time as 16 x 16 tiles (hidden quarter x batch rows, K = D + A): waves 0-3 produce timestep t + 2 and
+//     waves 4-7 timestep t + 3 during every even step t, into a ring of four x1 buffers in B-fragment order; the observation row
+//     is requested at the top of the step and consumed after the step's own matrix work.  An action given as indices is fed as
+//     the one-hot B operand built in registers (1.0f where the action column = index): the matrix instruction then adds exactly the weight
+//     column -- the same instruction, operands and order as an exact one-hot act_vec, hence the same bits -- and no one-hot tensor
+//     exists in memory.  The obs part and the action part of K are separate k steps (each zero-padded to a whole number of them);
+//   * the input projection of step t + 1 is issued before the barrier of step t (it does not depend on the recurrence);
+//   * every step's output h_t stays in LDS in the B-fragment order of the recurrence (the buffer of step t - 1 IS the h exchange),
+//     so the attention pass reads it back with conflict-free 16-byte reads: scores by wave (t = wave, wave + 8, ..), softmax
+//     statistics redundantly per wave in registers, the context of a lane's own two units, dense2 as a two-stage reduction.
+// LDS: N R 256 bytes of step outputs + 4 x1 buffers (R KB) + scores: R = 16 serves N <= 32 (146.5 KiB at N = 32), longer agent axes
+// run 8 rows per workgroup (columns 8 .. 15 of the tiles idle; 140.5 KiB at N = 64).  Nothing between the input rows and q touches HBM.
+#pragma once
+
+namespace {
+
+struct CriticArgs {
+    const float *obs;        // [b][N][D]
+    const int32_t *act_idx;  // [b][N][heads] or NULL
+    const float *act_vec;    // [b][N][A] or NULL
+    const float *w1, *b1;    // dense1.module: [64][D + A], [64]
+    const float *w_ih, *w_hh, *b_ih, *b_hh;  // lstm: [256][64] x 2, [256] x 2 (gate order i, f, g, o)
+    const float *w2, *b2;    // dense2: [1][64], [1]
+    const float *rew, *done; // [b] each or NULL
+    float *q, *y;            // [b]; y or NULL
+    long b;
+    int N, D, A, n0, n1, R;
+    float gamma;
+};
+
+__host__ __device__ inline size_t critic_lds_bytes(int N, int R)
+{
+    return (size_t)N * 4 * 4 * R * 16 + (size_t)4 * 4 * 4 * R * 16 + (size_t)N * 16 * 4 + 8 * 16 * 4;
+}
+
+// KO / KA: k steps of dense1 (four k each) the instantiation holds for the observation and the action part: ceil(D / 4) <= KO,
+// ceil(A / 4) <= KA.  (Both compile-time, so that every operand address is one per-lane pointer + an immediate: with the split at
+// a run-time k step the compiler keeps a hoisted address pair per operand across the timestep loop, and spills.)
+template <int KO, int KA>
+__global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs C)
+{
+    constexpr int KS = KO + KA;
+    extern __shared__ __attribute__((aligned(16))) unsigned char critic_smem[];
+    const int tid = threadIdx.x, lane = tid & 63, n16 = lane & 15, kq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int hq = wave & 3, grp = wave >> 2;
+    const int N = C.N, D = C.D, A = C.A, K = D + A, R = C.R, FR = 4 * R;
+    float4 *s_out = reinterpret_cast<float4 *>(critic_smem);  // [N][4 j][FR]: element e of slot (kq, n) = h_t[unit 16 j + 4 e + kq][row n]
+    float4 *s_x = s_out + (size_t)N * 4 * FR;                 // [4 buffers][4 j][FR]: the same order for x1 = relu(dense1)
+    float *s_sc = reinterpret_cast<float *>(s_x + 16 * FR);   // [N][16] attention scores
+    float *s_red = s_sc + N * 16;                             // [8 waves][16] dense2 partial sums
+    const long b0 = (long)blockIdx.x * R;
+    const int rows_here = (int)(C.b - b0 < (long)R ? C.b - b0 : (long)R);
+    const bool col_ok = n16 < rows_here;  // columns past the rows of this workgroup compute on row b0 and store nothing
+    const int nq = col_ok ? n16 : 0;
+    const int slot = kq * R + nq;
+    const int heads = C.n1 > 0 ? 2 : 1;
+
+    // ---- stationary weights: the wave's two LSTM tiles and its dense1 tile
+    float aih[2][16], ahh[2][16], bias[2][4], a1[KS], b1v[4];
+#pragma unroll
+    for (int T = 0; T < 2; ++T) {
+        const int wrow = (n16 & 3) * 64 + wave * 8 + 4 * T + (n16 >> 2);  // gate * 64 + unit
+#pragma unroll
+        for (int sx = 0; sx < 16; ++sx) {
+            aih[T][sx] = C.w_ih[wrow * 64 + 4 * sx + kq];
+            ahh[T][sx] = C.w_hh[wrow * 64 + 4 * sx + kq];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {  // accumulator role: row group = kq = unit within the tile, register = gate
+            const int r = i * 64 + wave * 8 + 4 * T + kq;
+            bias[T][i] = C.b_ih[r] + C.b_hh[r];
+        }
+    }
+    const float *w1o = C.w1 + (16 * hq + n16) * K + kq, *w1a = w1o + D;
+    auto w1_frag = [&](const int sx) {  // k step sx < KO: observation column 4 sx + kq; else action column 4 (sx - KO) + kq
+        if (sx < KO) return 4 * sx + kq < D ? w1o[4 * sx] : 0.0f;
+        return 4 * (sx - KO) + kq < A ? w1a[4 * (sx - KO)] : 0.0f;
+    };
+#pragma unroll
+    for (int sx = 0; sx < KS; ++sx) a1[sx] = w1_frag(sx);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) b1v[i] = C.b1[16 * hq + 4 * kq + i];
+
+    // B operands of one dense1 tile: [obs | action] of row (b0 + nq, ts)
+    auto load_x = [&](const int ts, float (&xb)[KS]) {
+        const size_t row = (size_t)(b0 + nq) * N + ts;
+        const float *xo = C.obs + row * D + kq;
+#pragma unroll
+        for (int sx = 0; sx < KO; ++sx) xb[sx] = 4 * sx + kq < D ? xo[4 * sx] : 0.0f;
+        if (C.act_idx) {
+            int i0 = C.act_idx[row * heads], i1 = -1;
+            i0 = (i0 >= 0 && i0 < C.n0) ? i0 : -1;
+            if (heads == 2) {
+                i1 = C.act_idx[row * heads + 1];
+                i1 = (i1 >= 0 && i1 < C.n1) ? C.n0 + i1 : -1;
+            }
+#pragma unroll
+            for (int sx = 0; sx < KA; ++sx) xb[KO + sx] = (4 * sx + kq == i0 || 4 * sx + kq == i1) ? 1.0f : 0.0f;
+        } else {
+            const float *xa = C.act_vec + row * A + kq;
+#pragma unroll
+            for (int sx = 0; sx < KA; ++sx) xb[KO + sx] = 4 * sx + kq < A ? xa[4 * sx] : 0.0f;
+        }
+    };
+    // relu(W1 x + b1) of the wave's hidden quarter -> x1 buffer ts % 4.  Register i of row group kq is hidden unit
+    // 16 hq + 4 kq + i: fragment j = hq, element kq, slot (i, n)
+    auto dense1 = [&](const int ts, const float (&xb)[KS]) {
+        f32x4 acc1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int sx = 0; sx < KS; ++sx) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[sx], xb[sx], acc1, 0, 0, 0);
+        if (n16 < R) {
+            float *dst = reinterpret_cast<float *>(s_x + ((ts & 3) * 4 + hq) * FR) + kq;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dst[(i * R + n16) * 4] = fmaxf(acc1[i] + b1v[i], 0.0f);
+        }
+    };
+    // bias + W_ih x1(ts) for the wave's two tiles
+    auto inproj = [&](const int ts, f32x4 (&acc)[2]) {
+        const float4 *xf = s_x + ((ts & 3) * 4) * FR + slot;
+        const float4 xq[4] = {xf[0], xf[FR], xf[2 * FR], xf[3 * FR]};
+#pragma unroll
+        for (int T = 0; T < 2; ++T) acc[T] = f32x4{bias[T][0], bias[T][1], bias[T][2], bias[T][3]};
+#pragma unroll
+        for (int jx = 0; jx < 4; ++jx) {
+            const float4 bq = xq[jx];
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[0][4 * jx + 0], bq.x, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[1][4 * jx + 0], bq.x, acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[0][4 * jx + 1], bq.y, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[1][4 * jx + 1], bq.y, acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[0][4 * jx + 2], bq.z, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[1][4 * jx + 2], bq.z, acc[1], 0, 0, 0);
+            acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[0][4 * jx + 3], bq.w, acc[0], 0, 0, 0);
+            acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(aih[1][4 * jx + 3], bq.w, acc[1], 0, 0, 0);
+        }
+    };
+
+    // ---- prologue: x1 of timesteps 0 and 1
+    {
+        float xb[KS];
+        if (grp < N) {
+            load_x(grp, xb);
+            dense1(grp, xb);
+        }
+    }
+    wg_lds_barrier();
+
+    // ---- the LSTM, one timestep per barrier
+    f32x4 acc[2], accn[2];
+    float c0 = 0.f, c1 = 0.f;
+    inproj(0, acc);
+    for (int t = 0; t < N; ++t) {
+        const int ts2 = t + 2 + grp;
+        const bool d1_now = !(t & 1) && ts2 < N;  // wave-uniform
+        float xb[KS];
+        if (d1_now) load_x(ts2, xb);
+        if (t > 0) {
+            const float4 *hx = s_out + ((t - 1) * 4) * FR + slot;
+            const float4 hv[4] = {hx[0], hx[FR], hx[2 * FR], hx[3 * FR]};
+#pragma unroll
+            for (int jx = 0; jx < 4; ++jx) {
+                const float4 bq = hv[jx];
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][4 * jx + 0], bq.x, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][4 * jx + 0], bq.x, acc[1], 0, 0, 0);
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][4 * jx + 1], bq.y, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][4 * jx + 1], bq.y, acc[1], 0, 0, 0);
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][4 * jx + 2], bq.z, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][4 * jx + 2], bq.z, acc[1], 0, 0, 0);
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][4 * jx + 3], bq.w, acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][4 * jx + 3], bq.w, acc[1], 0, 0, 0);
+            }
+        }
+        // the two cells of this lane: accumulator registers = gates i, f, g, o of unit 8 wave + 4 T + kq
+        float h0v, h1v;
+        lstm_cell(acc[0][0], acc[0][1], acc[0][2], acc[0][3], c0, h0v);
+        lstm_cell(acc[1][0], acc[1][1], acc[1][2], acc[1][3], c1, h1v);
+        // unit 8 wave + 4 T + kq is k quarter kq of k step 2 wave + T: fragment wave / 2, elements 2 (wave % 2) + T of this lane's slot
+        if (n16 < R)
+            reinterpret_cast<float2 *>(s_out + (t * 4 + (wave >> 1)) * FR + kq * R + n16)[wave & 1] = make_float2(h0v, h1v);
+        if (d1_now) dense1(ts2, xb);
+        if (t + 1 < N) inproj(t + 1, accn);  // before the barrier: work for the matrix pipe while the workgroup meets
+        wg_lds_barrier();                    // h_t of every unit is in LDS
+        if (t + 1 < N) { acc[0] = accn[0]; acc[1] = accn[1]; }
+    }
+
+    // ---- attention scores <h_t, h_N>: one timestep per wave and round, a lane sums its 16 units, the four k quarters meet
+    {
+        const float4 *hn = s_out + ((N - 1) * 4) * FR + slot;
+        const float4 hN[4] = {hn[0], hn[FR], hn[2 * FR], hn[3 * FR]};
+        for (int t = wave; t < N; t += 8) {
+            const float4 *o = s_out + (t * 4) * FR + slot;
+            float p = 0.0f;
+#pragma unroll
+            for (int jx = 0; jx < 4; ++jx) {
+                const float4 v = o[jx * FR];
+                p += v.x * hN[jx].x;
+                p += v.y * hN[jx].y;
+                p += v.z * hN[jx].z;
+                p += v.w * hN[jx].w;
+            }
+            p += lane_xor16(p);
+            p += lane_xor32(p);
+            if (kq == 0) s_sc[t * 16 + n16] = p;
+        }
+    }
+    wg_lds_barrier();
+
+    // ---- softmax over the agents (maximum subtracted), every wave for itself: a lane scans t = kq, kq + 4, ..
+    float mx = -INFINITY;
+    for (int t = kq; t < N; t += 4) mx = fmaxf(mx, s_sc[t * 16 + n16]);
+    mx = fmaxf(mx, lane_xor16(mx));
+    mx = fmaxf(mx, lane_xor32(mx));
+    float den = 0.0f;
+    for (int t = kq; t < N; t += 4) den += expf(s_sc[t * 16 + n16] - mx);
+    den += lane_xor16(den);
+    den += lane_xor32(den);
+    // ---- context of this lane's two units, ReLU, dense2
+    float ctx0 = 0.0f, ctx1 = 0.0f;
+    for (int t = 0; t < N; ++t) {
+        const float w = expf(s_sc[t * 16 + n16] - mx) / den;
+        const float2 o = reinterpret_cast<const float2 *>(s_out + (t * 4 + (wave >> 1)) * FR + slot)[wave & 1];
+        ctx0 += w * o.x;
+        ctx1 += w * o.y;
+    }
+    float part = C.w2[8 * wave + kq] * fmaxf(ctx0, 0.0f) + C.w2[8 * wave + 4 + kq] * fmaxf(ctx1, 0.0f);
+    part += lane_xor16(part);
+    part += lane_xor32(part);
+    if (kq == 0) s_red[wave * 16 + n16] = part;
+    wg_lds_barrier();
+    if (tid < 16 && col_ok) {
+        float qv = s_red[tid];
+#pragma unroll
+        for (int w = 1; w < 8; ++w) qv += s_red[w * 16 + tid];
+        qv += C.b2[0];
+        C.q[b0 + tid] = qv;
+        if (C.y) {  // r + GAMMA * q_next * (1. - d), left to right, no contraction (the unit is compiled with -ffp-contract=off)
+            const float gq = C.gamma * qv;
+            const float nd = 1.0f - C.done[b0 + tid];
+            const float prod = gq * nd;
+            C.y[b0 + tid] = C.rew[b0 + tid] + prod;
+        }
+    }
+}
+
+}  // namespace

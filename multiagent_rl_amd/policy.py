@@ -315,12 +315,24 @@ class FusedExploration(object):
         return [eye[0][idx[..., 0]], eye[1][idx[..., 1]]]
 
 
-def accelerate_trainer(trainer, seed=0):
+def accelerate_trainer(trainer, seed=0, targets=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
-    else of the learner is untouched.  Returns the ``FusedExploration`` object."""
+    else of the learner is untouched.  Returns the ``FusedExploration`` object.
+
+    ``targets=True`` additionally hands the no-gradient half of ``optimize()`` to the HIP kernels: ``trainer.target_actor`` and
+    ``trainer.target_critic`` become thin wrappers whose ``forward`` / ``__call__`` run on ``FusedActor.logits`` and
+    ``critic.FusedCritic`` (one launch each) and which pass everything else -- ``parameters()``, ``state_dict()``,
+    ``load_state_dict()``, ``eval()``, ``train()``, ``to()`` -- to the wrapped module, so ``soft_update``, ``hard_update``,
+    ``save_models`` and ``load_models`` work on the real networks.  The critic kernel reads the module's parameters in place; the
+    target actor's snapshot is refreshed where the exploration actor's is.  The Gumbel sampling of ``a1`` stays the Trainer's."""
     fx = FusedExploration(trainer.actor, getattr(trainer, 'action_type', 'Discrete'), seed=seed)
     trainer.get_exploration_action = fx.get_exploration_action
+    target_actor = None
+    if targets:
+        from .critic import fuse_targets
+        target_actor, fx.target_critic = fuse_targets(trainer)
+        fx.target_actor = target_actor
 
     def _wrap(name):
         inner = getattr(trainer, name, None)
@@ -330,6 +342,8 @@ def accelerate_trainer(trainer, seed=0):
         def wrapped(*a, **k):
             out = inner(*a, **k)
             fx.refresh()
+            if target_actor is not None:
+                target_actor.refresh()
             return out
         setattr(trainer, name, wrapped)
     _wrap('optimize')
