@@ -6,6 +6,8 @@ stays stock PyTorch-ROCm); inside a checkout of the reference, pass its own
 ``rls.agent.multiagent.ddpg_gumbel_fix.Trainer`` / ``rls.model.ac_network_multi_gumbel.CriticNetwork`` instead (``--reference``).
 What it keeps: DDPG with hard Gumbel-softmax categorical actions, one shared reward per transition, target networks with
 soft updates, Adam, batches drawn through ``memory.make_index`` / ``memory.sample_index``.
+``Trainer(..., fused_optimizer=True)``: each network's clip + Adam step + soft update is one HIP launch
+(``multiagent_rl_amd.optim.FusedAdam``); the default is the stock sequence.
 """
 import copy
 import os
@@ -32,12 +34,17 @@ class CriticNetwork(nn.Module):
 
 
 class Trainer(object):
-    def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None):
+    def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
         self.target_actor, self.target_critic = copy.deepcopy(self.actor).eval(), copy.deepcopy(self.critic).eval()
         self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr)
         self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr)
+        self.fused_optimizer = bool(fused_optimizer)
+        if self.fused_optimizer:   # clip (0.5) + Adam + soft update of the target: one launch per network
+            from multiagent_rl_amd.optim import FusedAdam
+            self.actor_optimizer = FusedAdam(self.actor.parameters(), lr, max_norm=0.5, targets=self.target_actor.parameters(), tau=TAU)
+            self.critic_optimizer = FusedAdam(self.critic.parameters(), lr, max_norm=0.5, targets=self.target_critic.parameters(), tau=TAU)
         self.memory, self.action_type, self.batch_size = memory, action_type, batch_size
         self.iter = 0
 
@@ -64,17 +71,20 @@ class Trainer(object):
         loss_critic = F.smooth_l1_loss(self.critic(s0, a0), y)
         self.critic_optimizer.zero_grad()
         loss_critic.backward()
-        nn.utils.clip_grad_norm_(self.critic.parameters(), 0.5)
+        if not self.fused_optimizer:
+            nn.utils.clip_grad_norm_(self.critic.parameters(), 0.5)
         self.critic_optimizer.step()
         loss_actor = -self.critic(s0, self._sample(self.actor(s0))).mean()
         self.actor_optimizer.zero_grad()
         loss_actor.backward()
-        nn.utils.clip_grad_norm_(self.actor.parameters(), 0.5)
+        if not self.fused_optimizer:
+            nn.utils.clip_grad_norm_(self.actor.parameters(), 0.5)
         self.actor_optimizer.step()
-        with torch.no_grad():
-            for tgt, src in ((self.target_actor, self.actor), (self.target_critic, self.critic)):
-                for pt, ps in zip(tgt.parameters(), src.parameters()):
-                    pt.mul_(1.0 - TAU).add_(ps, alpha=TAU)
+        if not self.fused_optimizer:
+            with torch.no_grad():
+                for tgt, src in ((self.target_actor, self.actor), (self.target_critic, self.critic)):
+                    for pt, ps in zip(tgt.parameters(), src.parameters()):
+                        pt.mul_(1.0 - TAU).add_(ps, alpha=TAU)
         self.iter += 1
         return float(loss_actor.detach()), float(loss_critic.detach())
 

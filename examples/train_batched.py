@@ -12,7 +12,9 @@ For every scenario and seed count ``cnt`` it does what main.py does -- build the
 critic from the reference checkout on ``sys.path`` (``rls.agent.multiagent.ddpg_gumbel_fix``); otherwise the small stock-PyTorch
 learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).  ``--critic attention`` gives
 it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``), ``--fused-targets`` runs its target networks'
-forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``).
+forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
+soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch, or ``accelerate_trainer(.., optimizer=True)`` with
+``--reference``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -47,6 +49,9 @@ def main(argv=None):
     ap.add_argument('--fused-targets', action='store_true',
                     help='target actor and target critic of the learner run on the HIP kernels (accelerate_trainer(.., targets=True); '
                          'needs the attention critic)')
+    ap.add_argument('--fused-optimizer', action='store_true',
+                    help="each network's gradient clip + Adam step + soft update is one HIP launch (madr_learner's fused_optimizer "
+                         'switch; with --reference: accelerate_trainer(.., optimizer=True))')
     args = ap.parse_args(argv)
     if args.fused_targets and args.critic != 'attention' and not args.reference:
         ap.error('--fused-targets needs --critic attention (the HIP critic is the LSTM + attention architecture)')
@@ -64,13 +69,16 @@ def main(argv=None):
         from madr_learner import CriticNetwork, Trainer
         if args.critic == 'attention':
             from multiagent_rl_amd.critic import CriticNetwork
-    if args.fused_targets:
+    if args.fused_targets or args.fused_optimizer:
         from multiagent_rl_amd.policy import accelerate_trainer
         plain_trainer = Trainer
 
         def Trainer(*a, **k):   # train_batched builds the learner itself: patch the instance it gets
+            if args.fused_optimizer and not args.reference:
+                k['fused_optimizer'] = True
             learner = plain_trainer(*a, **k)
-            accelerate_trainer(learner, targets=True)
+            if args.fused_targets or args.reference:
+                accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 107 /* 0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 108 /* 0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -532,6 +532,37 @@ int pw_critic_forward(const float *obs, const int32_t *act_idx, const float *act
                       const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
                       const float *rew /* or NULL */, const float *done /* or NULL */, float gamma, float *q,
                       float *y /* or NULL */, void *stream);
+
+/* The tail of a network's update as ONE launch (csrc/pw_kernels_optim.hpp states the float32 operation order):
+ *   total_norm = sqrt(sum g^2) over ALL tensors of the call; coef = min(1, max_norm / (total_norm + 1e-6))   [torch.nn.utils.clip_grad_norm_]
+ *   g = grad * coef; g += weight_decay * p; Adam (torch.optim.Adam without amsgrad / maximize) on exp_avg, exp_avg_sq, param, in place;
+ *   target = target * (1 - tau) + param * tau on the NEW param, where target != NULL                         [ddpg_gumbel_fix.py:36-47]
+ * `step` is the step this call takes (>= 1); the bias corrections are formed from it in float64 on the host.  Hyper-parameters are
+ * doubles, as torch holds them: 1 - beta1, 1 - beta2 and 1 - tau are formed in float64 and rounded to float32 once.
+ * Gradients are READ, never written (clip_grad_norm_ scales .grad in place; here the scaled gradient lives in registers).
+ * A NaN gradient makes total_norm and coef NaN and so every element of a clipping call, as clip_grad_norm_ does.
+ * The norm is summed in a fixed order without atomics: the same inputs give the same bits, every element of a call sees the
+ * same coef, and no workgroup waits for another.  total_norm (device, may be NULL) receives the norm, also with max_norm <= 0.
+ * The table travels in the kernel arguments: no copy, no allocation, no synchronisation; one launch on `stream`.
+ * Tensors: device float32, any 4-byte aligned address, any numel >= 1; at most PW_OPT_MAX_TENSORS tensors and 2^20 elements
+ * per call.  PW_EINVAL (nothing launched): count outside [1, 32], more than 2^20 elements, a null param / grad / exp_avg /
+ * exp_avg_sq, numel < 1, step < 1, lr < 0, beta outside [0, 1), eps < 0, weight_decay < 0, tau outside [0, 1] with a target. */
+#define PW_OPT_MAX_TENSORS 32
+typedef struct pw_opt_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    float *target; /* may be NULL: no soft update for this tensor */
+    int64_t numel;
+} pw_opt_tensor;
+int pw_adam_step(const pw_opt_tensor *tensors, int32_t count, int64_t step, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, double max_norm /* <= 0: no clipping */, double tau /* used where target != NULL */,
+                 float *total_norm /* device, or NULL */, void *stream);
+/* target[k] = target[k] * (1 - tau) + source[k] * tau for count tensor pairs of numel[k] elements, one launch: both products
+ * rounded to float32 before the sum, bit for bit torch's `t * (1.0 - tau) + s * tau`.  tau == 1 copies (an infinity in the old
+ * target does not become NaN).  The three arrays are HOST arrays of device pointers / sizes; limits as pw_adam_step. */
+int pw_soft_update(float *const *target, const float *const *source, const int64_t *numel, int32_t count, double tau, void *stream);
 
 #ifdef __cplusplus
 }

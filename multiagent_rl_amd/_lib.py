@@ -67,6 +67,14 @@ class PwReplayStore(C.Structure):
                 ('lm', C.c_void_p)]
 
 
+class PwOptTensor(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('param', 'grad', 'exp_avg', 'exp_avg_sq', 'target')] + [('numel', C.c_int64)]
+
+
+PW_OPT_MAX_TENSORS = 32
+PW_OPT_MAX_ELEMENTS = 1 << 20
+
+
 class PwChunkWire(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('T', 'B', 'N', 'D', 'F', 'reserved')] + \
                [(n, C.c_size_t) for n in ('obs0', 'obs', 'final_rows', 'rew_shared', 'act', 'fin_slot', 'total_bytes')]
@@ -157,6 +165,9 @@ SIGNATURES = {
     'pw_critic_forward': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32,
                                                                                           C.c_void_p, C.c_void_p, C.c_float,
                                                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pw_adam_step': (C.c_int, [C.POINTER(PwOptTensor), C.c_int32, C.c_int64] + [C.c_double] * 7 + [C.c_void_p, C.c_void_p]),
+    'pw_soft_update': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_double,
+                                 C.c_void_p]),
 }
 
 

@@ -7,7 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pworld_policy.hip'),
-        os.path.join(HERE, 'csrc', 'pworld_critic.hip')]
+        os.path.join(HERE, 'csrc', 'pworld_critic.hip'), os.path.join(HERE, 'csrc', 'pworld_optim.hip')]
 OUT = os.path.join(HERE, 'libpworld.so')
 OBJ_DIR = os.path.join(HERE, 'csrc', '_obj')  # git-ignored (*.o); objects are kept so that one unit rebuilds alone
 DEPS = [os.path.join(HERE, 'csrc', f) for f in sorted(os.listdir(os.path.join(HERE, 'csrc'))) if f.endswith(('.hip', '.hpp'))] + \
@@ -57,7 +57,7 @@ def _stale(obj):
 
 def unit_sources(unit):
     """Every file translation unit `unit` ('pworld' = environment / replay / wire, 'pworld_policy' = actor and policy rollouts,
-    'pworld_critic' = the learner's critic forward) is
+    'pworld_critic' = the learner's critic forward, 'pworld_optim' = clip + Adam + soft update) is
     compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
     sources (no compiler, no recorded paths), so it gives the same answer in any copy of the tree."""
     import re

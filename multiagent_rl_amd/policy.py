@@ -315,7 +315,7 @@ class FusedExploration(object):
         return [eye[0][idx[..., 0]], eye[1][idx[..., 1]]]
 
 
-def accelerate_trainer(trainer, seed=0, targets=False):
+def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -325,7 +325,13 @@ def accelerate_trainer(trainer, seed=0, targets=False):
     ``critic.FusedCritic`` (one launch each) and which pass everything else -- ``parameters()``, ``state_dict()``,
     ``load_state_dict()``, ``eval()``, ``train()``, ``to()`` -- to the wrapped module, so ``soft_update``, ``hard_update``,
     ``save_models`` and ``load_models`` work on the real networks.  The critic kernel reads the module's parameters in place; the
-    target actor's snapshot is refreshed where the exploration actor's is.  The Gumbel sampling of ``a1`` stays the Trainer's."""
+    target actor's snapshot is refreshed where the exploration actor's is.  The Gumbel sampling of ``a1`` stays the Trainer's.
+
+    ``optimizer=True`` hands the arithmetic after the backward passes to the HIP kernels (``multiagent_rl_amd.optim``):
+    ``trainer.actor_optimizer`` / ``trainer.critic_optimizer`` become ``FusedAdam`` objects with the hyper-parameters and state of
+    the ``torch.optim.Adam`` they replace (one launch per ``step()``), and ``trainer.soft_update`` becomes the one-launch
+    ``optim.soft_update``.  The Trainer's ``clip_grad_norm_`` calls stay torch's.  Works with and without ``targets``; the default
+    leaves optimisers and ``soft_update`` exactly as they are."""
     fx = FusedExploration(trainer.actor, getattr(trainer, 'action_type', 'Discrete'), seed=seed)
     trainer.get_exploration_action = fx.get_exploration_action
     target_actor = None
@@ -333,6 +339,9 @@ def accelerate_trainer(trainer, seed=0, targets=False):
         from .critic import fuse_targets
         target_actor, fx.target_critic = fuse_targets(trainer)
         fx.target_actor = target_actor
+    if optimizer:
+        from .optim import fuse_optimizers
+        fx.optimizers = fuse_optimizers(trainer)
 
     def _wrap(name):
         inner = getattr(trainer, name, None)
