@@ -7,7 +7,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pworld_policy.hip'),
-        os.path.join(HERE, 'csrc', 'pworld_critic.hip'), os.path.join(HERE, 'csrc', 'pworld_optim.hip')]
+        os.path.join(HERE, 'csrc', 'pworld_critic.hip'), os.path.join(HERE, 'csrc', 'pworld_optim.hip'),
+        os.path.join(HERE, 'csrc', 'pworld_replay.hip')]
 OUT = os.path.join(HERE, 'libpworld.so')
 OBJ_DIR = os.path.join(HERE, 'csrc', '_obj')  # git-ignored (*.o); objects are kept so that one unit rebuilds alone
 DEPS = [os.path.join(HERE, 'csrc', f) for f in sorted(os.listdir(os.path.join(HERE, 'csrc'))) if f.endswith(('.hip', '.hpp'))] + \
@@ -56,9 +57,9 @@ def _stale(obj):
 
 
 def unit_sources(unit):
-    """Every file translation unit `unit` ('pworld' = environment / replay / wire, 'pworld_policy' = actor and policy rollouts,
-    'pworld_critic' = the learner's critic forward, 'pworld_optim' = clip + Adam + soft update) is
-    compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
+    """Every file translation unit `unit` ('pworld' = environment, 'pworld_policy' = actor and policy rollouts,
+    'pworld_critic' = the learner's critic forward, 'pworld_optim' = clip + Adam + soft update, 'pworld_replay' = replay ring /
+    wire blocks) is compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
     sources (no compiler, no recorded paths), so it gives the same answer in any copy of the tree."""
     import re
     csrc = os.path.join(HERE, 'csrc')
@@ -78,13 +79,13 @@ def unit_sources(unit):
 
 KERNEL_FAMILIES = {
     # the device code of the environment kernels (pw_spread_* / pw_tag_* / pw_rollout_kernel / pw_reference_*): headers only -- the host
-    # side (pworld.hip: dispatch, entry points) and the replay / wire kernels do not change what these kernels execute, and a
+    # side (pworld.hip: dispatch, entry points; pw_host.hpp) and the replay / wire kernels do not change what these kernels execute, and a
     # different dispatch choice shows up as a different kernel NAME, which bench.py compares as well
-    'env': ['csrc/pw_common.hpp', 'csrc/pw_kernels_spread.hpp', 'csrc/pw_kernels_spread_quad.hpp', 'csrc/pw_kernels_tag.hpp',
+    'env': ['csrc/pw_common.hpp', 'csrc/pw_params.hpp', 'csrc/pw_kernels_spread.hpp', 'csrc/pw_kernels_spread_quad.hpp', 'csrc/pw_kernels_tag.hpp',
             'csrc/pw_kernels_generic.hpp', 'csrc/pw_kernels_reference.hpp', '../include/pworld_math.h'],
     # the one-launch policy rollouts and the fused actor: the environment arithmetic above + the actor headers
-    'policy': ['csrc/pw_common.hpp', 'csrc/pw_kernels_spread.hpp', 'csrc/pw_kernels_tag.hpp', 'csrc/pw_kernels_reference.hpp',
-               '../include/pworld_math.h', 'csrc/pw_kernels_actor16.hpp', 'csrc/pw_kernels_policy.hpp', 'csrc/pw_kernels_policy2.hpp',
+    'policy': ['csrc/pw_common.hpp', 'csrc/pw_params.hpp', 'csrc/pw_kernels_spread.hpp', 'csrc/pw_kernels_tag.hpp', 'csrc/pw_kernels_reference.hpp',
+               '../include/pworld_math.h', 'csrc/pw_lstm_math.hpp', 'csrc/pw_kernels_actor16.hpp', 'csrc/pw_kernels_policy.hpp', 'csrc/pw_policy_shared.hpp',
                'csrc/pw_kernels_policy3.hpp', 'csrc/pw_kernels_policy3j.hpp', 'csrc/pw_kernels_policy_ref.hpp',
                'csrc/pw_kernels_policy_tag.hpp'],
 }

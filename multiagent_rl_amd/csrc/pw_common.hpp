@@ -1,29 +1,15 @@
-// pw_common.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
-// Error plumbing, kernel parameter blocks, lane mapping, the shared device functions (collision force, observation, reward/masks, reset).
+// pw_common.hpp -- part of libpworld.so (the environment, policy and replay kernel headers include it).
+// Lane mapping and the shared device functions (collision force, observation, reward/masks, reset).
 #pragma once
 
-// libpworld.so is two translation units (pworld.hip: environment, replay ring, wire blocks; pworld_policy.hip: actor and
-// policy-in-the-loop rollouts).  The thread-local error text lives in pworld.hip; both reach it through this hook.
-extern "C" __attribute__((visibility("hidden"))) void pw_internal_set_error(const char *msg);
+#include <hip/hip_runtime.h>
 
-namespace {
+#include "pworld.h"
+#include "pworld_math.h"
 
-int fail(int code, const std::string &msg)
-{
-    pw_internal_set_error(msg.c_str());
-    return code;
-}
+#include "pw_host.hpp"
+#include "pw_params.hpp"
 
-#define PW_HIP_CHECK(expr)                                                             \
-    do {                                                                               \
-        hipError_t _e = (expr);                                                        \
-        if (_e != hipSuccess)                                                          \
-            return fail(PW_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));   \
-    } while (0)
-
-constexpr int kWave = 64;
-
-}  // namespace
 // Timing-only overlays (wrong results by design) are NOT product source: tools/experiments/pw_experiments.hpp, reachable only from
 // a tools/ build that passes -DPW_EXPERIMENTS -I tools/experiments.  build_native.py never does; the product sees the defaults below.
 #ifdef PW_EXPERIMENTS
@@ -34,28 +20,14 @@ constexpr int kWave = 64;
 #endif
 namespace {
 
+constexpr int kWave = 64;
+
 // Every workgroup is ONE wave, and a wave's LDS instructions execute in issue order, so the
 // only thing a write -> cross-lane read hand-off through LDS needs is (a) that the compiler
 // keeps the program order of the accesses and (b) that the data has landed before it is
 // consumed.  Unlike __syncthreads() this does NOT drain vmcnt: the step's global stores
 // (16 B x 4 per lane of observations) stay in flight across steps.
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-
-// Everything a kernel needs, passed by value in the kernarg segment.
-struct KParams {
-    int B, N, L, A, D;
-    int epw;          // envs per wave
-    int max_episode_len, auto_reset, force_discrete, landmark_collide;
-    uint64_t seed, env_id_base;
-    float dt, damp, contact_force, contact_margin, mass, landmark_size;
-    float *pos_x, *pos_y, *vel_x, *vel_y, *lm_x, *lm_y;
-    int32_t *ep_step;
-    uint32_t *ep_count;
-    float agent_size[PW_MAX_AGENTS];
-    float agent_sens[PW_MAX_AGENTS];      // accel if set else default_sensitivity (_set_action)
-    float agent_fscale[PW_MAX_AGENTS];    // 1, or mass*accel with the fork knob (apply_action_force)
-    float agent_max_speed[PW_MAX_AGENTS]; // < 0: None
-};
 
 // Per-lane view of "its" env inside the wave.
 struct Lane {
@@ -464,8 +436,5 @@ size_t smem_bytes(const KParams &P)
 {
     return (size_t)P.epw * (2 * P.N + P.L) * sizeof(float2) + (size_t)P.epw * P.L * sizeof(float);
 }
-
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace

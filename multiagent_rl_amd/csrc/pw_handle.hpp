@@ -1,5 +1,11 @@
-// pw_handle.hpp -- part of libpworld.so: the handle and the host-side helpers both translation units use.
+// pw_handle.hpp -- part of libpworld.so: the handle and the host-side helpers of the translation units that take one
+// (pworld.hip, pworld_policy.hip, pworld_replay.hip).
 #pragma once
+
+#include <cstring>
+
+#include "pw_host.hpp"
+#include "pw_params.hpp"
 
 struct pw_handle {
     pw_config cfg;
@@ -33,40 +39,43 @@ RefParams ref_params(const pw_handle *h)
     return R;
 }
 
+// the simple_spread streaming kernels' block from a handle and a step's outputs; act, coll and p_prio stay with the caller
+StreamParams stream_params(const pw_handle *h, const pw_step_io *io)
+{
+    const KParams &kp = h->kp;
+    StreamParams A = {};
+    A.B = kp.B; A.N = kp.N; A.L = kp.L; A.epw = kp.epw;
+    A.max_episode_len = kp.max_episode_len; A.auto_reset = kp.auto_reset;
+    A.seed = kp.seed; A.env_id_base = kp.env_id_base;
+    A.dt = kp.dt; A.damp = kp.damp; A.contact_force = kp.contact_force; A.contact_margin = kp.contact_margin;
+    A.mass = kp.mass;
+    A.dist_min = h->fc.dist_min; A.coll_thr2 = h->fc.coll_thr2; A.near_thr2 = h->fc.near_thr2;
+    A.sens = h->fc.sens; A.fscale = h->fc.fscale;
+    A.pos_x = kp.pos_x; A.pos_y = kp.pos_y; A.vel_x = kp.vel_x; A.vel_y = kp.vel_y;
+    A.lm_x = kp.lm_x; A.lm_y = kp.lm_y; A.ep_step = kp.ep_step; A.ep_count = kp.ep_count;
+    A.obs = io->obs; A.final_obs = io->final_obs; A.rew = io->rew; A.rew_shared = io->rew_shared;
+    A.done = io->done; A.terminal = io->terminal;
+    return A;
+}
+
+// the simple_tag kernels' block: the handle's constant part + state planes and a step's outputs; act, coll, p_prio, obs_block stay with the caller
+TagParams tag_params(const pw_handle *h, const pw_step_io *io)
+{
+    const KParams &kp = h->kp;
+    TagParams A = h->tp;
+    A.pos_x = kp.pos_x; A.pos_y = kp.pos_y; A.vel_x = kp.vel_x; A.vel_y = kp.vel_y;
+    A.lm_x = kp.lm_x; A.lm_y = kp.lm_y; A.ep_step = kp.ep_step; A.ep_count = kp.ep_count;
+    A.obs = io->obs; A.final_obs = io->final_obs; A.rew = io->rew; A.rew_shared = io->rew_shared;
+    A.done = io->done; A.terminal = io->terminal;
+    return A;
+}
+
 int check_ready(const pw_handle *h)
 {
     if (!h) return fail(PW_EINVAL, "null handle");
     if (!h->bound) return fail(PW_ESTATE, "state block not bound: call pw_bind_state first");
     return PW_OK;
 }
-
-// Kernels that ask for more than 64 KB of dynamic LDS need the opt-in once per (kernel, DEVICE): a process driving
-// several GPUs must not skip it on the second one.  The device's bit is set only AFTER hipFuncSetAttribute succeeded
-// (lds_optin_done), atomically: a failed call is retried by the next launch, and two host threads on different devices
-// cannot lose each other's bit.
-bool lds_optin_needed(const unsigned long long *done_mask, int *dev_out)
-{
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { *dev_out = -1; return true; }  // unknown: set it every time (cheap)
-    *dev_out = dev;
-    return !(__atomic_load_n(done_mask, __ATOMIC_ACQUIRE) >> dev & 1ull);
-}
-
-void lds_optin_done(unsigned long long *done_mask, int dev)
-{
-    if (dev >= 0) __atomic_fetch_or(done_mask, 1ull << dev, __ATOMIC_RELEASE);
-}
-
-// hipFuncSetAttribute(kernel, MaxDynamicSharedMemorySize, 160 KB) once per (kernel, device); returns from the caller on failure
-#define PW_LDS_OPTIN(mask_ptr, kernel_expr)                                                                              \
-    do {                                                                                                                 \
-        int optin_dev_;                                                                                                  \
-        if (lds_optin_needed((mask_ptr), &optin_dev_)) {                                                                 \
-            PW_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel_expr),                                \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));                   \
-            lds_optin_done((mask_ptr), optin_dev_);                                                                      \
-        }                                                                                                                \
-    } while (0)
 
 // The chunk / tail / packed / wire entry points and the rollout sink write the plain ring layout only.
 int plain_ring_only(const pw_replay_store *st, const char *who)

@@ -5,9 +5,10 @@
 // pw_actor_fused16_kernel (one pass per launch), the simple_reference and simple_tag one-launch rollouts.
 #pragma once
 
+#include "pw_kernels_policy.hpp"
+
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -133,23 +134,6 @@ __device__ __forceinline__ void actor16_inproj(const float4 *s_xf, const int ts,
 #pragma unroll
         for (int i = 0; i < 4; ++i) acc[T][i] += bias[T][i];
 }
-
-// The value of lane ^ 16 / lane ^ 32 by v_permlane16_swap / v_permlane32_swap (gfx950): the instruction swaps the odd rows (halves) of
-// its first operand with the even rows (halves) of the second, so with both operands the same value the first holds, in every
-// even row (half), its own value and the second its neighbour's -- one VALU instruction and a select instead of a ds_bpermute
-// round trip through the LDS crossbar (~120 cycles, exposed on the head's dependent chain).
-__device__ __forceinline__ uint32_t lane_xor16(const uint32_t v)
-{
-    const auto r = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    return (threadIdx.x & 16) ? r[0] : r[1];
-}
-__device__ __forceinline__ uint32_t lane_xor32(const uint32_t v)
-{
-    const auto r = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return (threadIdx.x & 32) ? r[0] : r[1];
-}
-__device__ __forceinline__ float lane_xor16(const float v) { return __uint_as_float(lane_xor16(__float_as_uint(v))); }
-__device__ __forceinline__ float lane_xor32(const float v) { return __uint_as_float(lane_xor32(__float_as_uint(v))); }
 
 // LDS of the pass (floats from a 16-byte aligned base): dense1 output and head input in B-fragment order, the h exchange,
 // the dense1 constants

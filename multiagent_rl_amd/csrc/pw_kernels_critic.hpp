@@ -7,7 +7,7 @@
 //   * a workgroup of 512 threads owns R batch rows (R = 16; 8 when N > 32, see "LDS") = the 16 columns of v_mfma_f32_16x16x4_f32;
 //   * wave w owns hidden units 8 w .. 8 w + 7 as two 16-row tiles, tile row = 4 (unit within tile) + gate: after the matrix
 //     instructions a lane's four accumulator registers ARE the gates i, f, g, o of one unit for one batch row, so the cell update
-//     (lstm_cell of pw_kernels_policy.hpp: fast_sigmoid / fast_tanh) needs no exchange.  W_ih and W_hh of the wave's 32 gate rows
+//     (lstm_cell of pw_lstm_math.hpp: fast_sigmoid / fast_tanh) needs no exchange.  W_ih and W_hh of the wave's 32 gate rows
 //     stay in registers for the whole launch (64 per lane; + the wave's W1 tile, up to 30), read straight from the nn.Module layout [256][64];
 //   * dense1 runs just in time as 16 x 16 tiles (hidden quarter x batch rows, K = D + A): waves 0-3 produce timestep t + 2 and
 //     waves 4-7 timestep t + 3 during every even step t, into a ring of four x1 buffers in B-fragment order; the observation row
@@ -22,6 +22,8 @@
 // LDS: N R 256 bytes of step outputs + 4 x1 buffers (R KB) + scores: R = 16 serves N <= 32 (146.5 KiB at N = 32), longer agent axes
 // run 8 rows per workgroup (columns 8 .. 15 of the tiles idle; 140.5 KiB at N = 64).  Nothing between the input rows and q touches HBM.
 #pragma once
+
+#include "pw_lstm_math.hpp"
 
 namespace {
 

@@ -1,6 +1,8 @@
-// pw_kernels_generic.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_generic.hpp -- part of libpworld.so (translation unit csrc/pworld.hip includes it).
 // Generic kernels: pw_rollout_kernel (any scenario), pw_aux_kernel (reset/observe/reward), AoS<->SoA state copies.
 #pragma once
+
+#include "pw_common.hpp"
 
 namespace {
 

@@ -34,6 +34,10 @@
 // the old target is not read, so an infinity there cannot turn into NaN through inf * 0.
 #pragma once
 
+#include <hip/hip_runtime.h>
+
+#include "pworld.h"
+
 namespace {
 
 constexpr int kOptThreads = 512;

@@ -1,6 +1,9 @@
-// pw_kernels_policy.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_policy.hpp -- part of libpworld.so (translation unit csrc/pworld_policy.hip includes it).
 // Policy forward (BiLSTM recurrence, head + Gumbel sampling) and episode bookkeeping.
 #pragma once
+
+#include "pw_kernels_spread.hpp"   // StreamParams of the rollout block, the PW_STAMP probe macros
+#include "pw_lstm_math.hpp"
 
 namespace {
 
@@ -15,35 +18,6 @@ namespace {
 // recurrence step is 128 FMAs + 5 activations per lane; h is exchanged through wave-private LDS
 // (one write, eight broadcast ds_read_b128).  G holds x*W_ih^T + b_ih + b_hh for every timestep.
 // ------------------------------------------------------------------------------------------
-// v_exp_f32 / v_rcp_f32 (1 ulp): the policy net is ordinary float32 inference, not part of the
-// bit-exact environment contract; tests compare against PyTorch's float32 LSTM with a 2e-5 bound.
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-// tanh(x) = 2 / (1 + exp(-2x)) - 1: five instructions (mul, exp2, add, rcp, fma) instead of the nine of (1 - e) / (1 + e) on |x| with the
-// sign copied back -- the cell update is vector work that cannot overlap the exact-f32 matrix instructions, so every instruction of it
-// is on the timestep's path (round 5: 2 % of a step).  x -> -inf: exp = inf, rcp = 0, result -1; x -> +inf: exp = 0, result 1; no NaN from
-// finite input.  Same absolute accuracy as the other form (both are limited by the rounding of a number near 1: ~1e-7).
-__device__ __forceinline__ float fast_tanh(float x)
-{
-    return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -2.8853900817779268f)), -1.0f);   // exp(-2x) = 2^(-2 log2(e) x): one multiply
-}
-
-// One LSTM cell (PyTorch's gate order i, f, g, o): pre-activations -> new cell state c and output h.  Every kernel form calls this
-// one function, so the forms agree bit for bit whatever the activations' rounding is.
-// (The four gates' exponent arguments and denominators are formed two at a time -- (i, f) and (g, o) sit in adjacent accumulator registers --
-// so that they compile to packed multiplies / adds; the operations and their bits are those of fast_sigmoid / fast_tanh.)
-__device__ __forceinline__ void lstm_cell(const float gi, const float gf, const float gg, const float go, float &c, float &h)
-{
-    typedef float v2 __attribute__((ext_vector_type(2)));
-    const v2 a = v2{gi, gf} * v2{-1.4426950408889634f, -1.4426950408889634f};   // exp(-x) = 2^(-log2(e) x)
-    const v2 b = v2{gg, go} * v2{-2.8853900817779268f, -1.4426950408889634f};   // tanh's exp(-2x) for g
-    const v2 d1 = v2{__builtin_amdgcn_exp2f(a.x), __builtin_amdgcn_exp2f(a.y)} + v2{1.0f, 1.0f};
-    const v2 d2 = v2{__builtin_amdgcn_exp2f(b.x), __builtin_amdgcn_exp2f(b.y)} + v2{1.0f, 1.0f};
-    const float si = __builtin_amdgcn_rcpf(d1.x), sf = __builtin_amdgcn_rcpf(d1.y), so = __builtin_amdgcn_rcpf(d2.y);
-    const float tg = fmaf(2.0f, __builtin_amdgcn_rcpf(d2.x), -1.0f);
-    c = sf * c + si * tg;
-    h = so * fast_tanh(c);
-}
-
 // One hidden unit's four W_hh rows, gate pairs (i, f) and (g, o) packed so that a recurrence step is 64
 // v_pk_fma_f32 (two gates per instruction, h broadcast through op_sel) instead of 128 scalar FMAs.  Each
 // gate still accumulates over k in ascending order with fused multiply-adds: the same bits either way.
@@ -394,12 +368,6 @@ struct ActorFusedArgs {
 };
 constexpr int kFusedRows = 96, kGs = 129, kHs = 68;  // kHs: 16-byte aligned rows for the head's float4 reads
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also carries a workgroup-scope fence for GLOBAL
-// memory, i.e. an s_waitcnt vmcnt(0): every wave would sit out the full HBM latency of its outstanding stores at
-// each of the ~8 barriers of a pass.  Inside these kernels waves hand data to each other through LDS alone, and
-// what they store to global memory is only read after the kernel (or behind an explicit __threadfence).
-__device__ __forceinline__ void wg_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // LDS of one actor workgroup (carved from dynamic shared memory; kActorLdsFloats(S1) floats in total)
 struct ActorLds {
     float4 *f_wih;  // [4 n][2 m][4 rq][64 lane] float4, one direction
@@ -649,7 +617,7 @@ __global__ void __launch_bounds__(512) pw_actor_fused_kernel(const ActorFusedArg
 // ------------------------------------------------------------------------------------------
 // Policy-in-the-loop rollout as ONE launch: T x (actor forward + Gumbel sampling + environment step) with the
 // observations, the sampled actions and the world state of a workgroup's 16 environments never leaving the
-// CU between steps (pw_kernels_policy2.hpp, pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp hold the kernels).  The
+// CU between steps (pw_policy_shared.hpp, pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp hold the kernels).  The
 // environment lanes advance their envs exactly as pw_spread_stream_kernel does (lane = (env, agent); same expressions,
 // same order, same bits) and write the step's outputs -- and the next observation rows (or states) back into LDS.  HBM
 // sees the outputs of a step once; there is no launch and no kernel boundary between steps.
@@ -672,10 +640,6 @@ struct PolicyRolloutArgs {
     unsigned long long *scratch;    // [2 * gridDim.x + 1] words, zero before first use
     int NP;                         // just-in-time form: row stride of an environment in LDS (>= N; odd: see pw_kernels_policy3j.hpp)
 };
-
-// (The first, phase-by-phase form of the rollout kernel -- pw_policy_rollout_kernel: actor_forward_wg per step, the environment
-// on the first waves -- was retired in round 4: since the third form and its just-in-time variant nothing selected it
-// automatically, and the forms that run are each compared with the CPU oracle directly.)
 
 // Test hook: evaluate one device math primitive element-wise so that tests can compare the exact bits
 // against the CPU contract (include/pworld_math.h, restated in oracle/pworld_oracle.c) over millions of

@@ -3,6 +3,10 @@
 // timestep at a time, every weight resident in registers, no G tile in LDS.
 #pragma once
 
+#include "pw_kernels_spread.hpp"
+#include "pw_kernels_actor16.hpp"
+#include "pw_policy_shared.hpp"
+
 namespace {
 
 // ------------------------------------------------------------------------------------------

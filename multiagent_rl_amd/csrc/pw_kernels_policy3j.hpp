@@ -3,6 +3,8 @@
 // dense1 computed JUST IN TIME, one timestep per direction per loop iteration, and no observation rows in LDS.
 #pragma once
 
+#include "pw_kernels_policy3.hpp"
+
 namespace {
 
 // ------------------------------------------------------------------------------------------

@@ -4,6 +4,10 @@
 // the heads' one-hots into the env action).
 #pragma once
 
+#include "pw_kernels_reference.hpp"
+#include "pw_kernels_actor16.hpp"
+#include "pw_policy_shared.hpp"
+
 namespace {
 
 // ------------------------------------------------------------------------------------------

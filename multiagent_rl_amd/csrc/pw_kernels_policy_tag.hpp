@@ -1,7 +1,11 @@
-// pw_kernels_policy_tag.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_policy_tag.hpp -- part of libpworld.so (translation unit csrc/pworld_policy.hip includes it).
 // Policy-in-the-loop rollout for simple_tag (BASELINE configs[2]): pw_policy_rollout_kernel's structure (actor pass
 // of the whole workgroup, then the first waves advance the environments) with pw_tag_stream_kernel's arithmetic.
 #pragma once
+
+#include "pw_kernels_tag.hpp"
+#include "pw_kernels_actor16.hpp"
+#include "pw_policy_shared.hpp"
 
 namespace {
 

@@ -1,7 +1,9 @@
-// pw_kernels_reference.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_reference.hpp -- part of libpworld.so (translation units csrc/pworld.hip and csrc/pworld_policy.hip include it).
 // simple_reference and simple_speaker_listener: the communication scenarios of the reference's sweep
 // (main.py:24).
 #pragma once
+
+#include "pw_common.hpp"
 
 namespace {
 
@@ -24,15 +26,6 @@ namespace {
 // symbol NOT included.  act_idx = (symbol, movement); act_vec rows are 5 wide (the speaker's 3 first).
 // ------------------------------------------------------------------------------------------
 constexpr int kDimC = 10, kDimCSL = 3;
-
-struct RefParams {
-    int B, L, D, max_episode_len, auto_reset, force_discrete;
-    uint64_t seed, env_id_base;
-    float dt, damp, mass, sens;
-    float *pos_x, *pos_y, *vel_x, *vel_y, *lm_x, *lm_y, *comm;
-    int32_t *goal, *ep_step;
-    uint32_t *ep_count;
-};
 
 template <int DC>
 struct RefLane {

@@ -1,6 +1,8 @@
-// pw_kernels_replay.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_replay.hpp -- part of libpworld.so (translation unit csrc/pworld_replay.hip includes it).
 // Device replay ring, transition packing and the fused multi-GPU exchange launch.
 #pragma once
+
+#include "pw_common.hpp"
 
 namespace {
 

@@ -1,6 +1,8 @@
-// pw_kernels_spread.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_spread.hpp -- part of libpworld.so (translation units csrc/pworld.hip and csrc/pworld_policy.hip include it).
 // simple_spread fast paths: pw_spread_fast_kernel, pw_spread_stream_kernel, pw_spread_duo_kernel.
 #pragma once
+
+#include "pw_common.hpp"
 
 namespace {
 
@@ -16,11 +18,6 @@ namespace {
 //    step t, the near-pair mask of step t+1 and the owned landmark's min distance;
 //  * NT > 0 fixes N at compile time (loops unrolled); the next step's action is prefetched.
 // ------------------------------------------------------------------------------------------
-struct FastConsts {
-    float dist_min, coll_thr2, near_thr2, sens, fscale, size;
-    int k1;  // the contact margin qualifies for the one-correction division (margin_one_correction)
-};
-
 template <int NT>
 __device__ __forceinline__ void partner_pass(const int N, const Lane &ln, const float2 *pp, float px, float py,
                                              bool own_lm, float olx, float oly, const FastConsts &C,
@@ -250,21 +247,6 @@ __device__ __forceinline__ void near_force_loop(MaskT m, const PosT *pp, float p
 // the host knows at launch (UNIT_MASS) -- a runtime select would still pay for the division.
 template <bool UNIT_MASS>
 __device__ __forceinline__ float div_mass(float x, float mass) { return UNIT_MASS ? x : x / mass; }
-
-struct StreamParams {
-    int B, N, L, epw, max_episode_len, auto_reset;
-    int p_prio;  // duo kernel: issue priority per wave, 2 bits each (wave 0 = physics in bits 0-1, ...); set by the launch
-    uint64_t seed, env_id_base;
-    float dt, damp, contact_force, contact_margin, mass;
-    float dist_min, coll_thr2, near_thr2, sens, fscale;
-    float *pos_x, *pos_y, *vel_x, *vel_y, *lm_x, *lm_y;
-    int32_t *ep_step;
-    uint32_t *ep_count;
-    const int32_t *act;
-    float *obs, *final_obs, *rew, *rew_shared;
-    uint8_t *done, *terminal;
-    uint64_t *coll;  // [T,B,N] collision masks; written only by the COLL instantiations
-};
 
 // A store into one of the per-agent / per-env output planes: with the non-temporal hint where the enclosing kernel's
 // kNtPlanes says so (pw_common.hpp, nt_store).  A macro, not a function template: routed through a function the plain

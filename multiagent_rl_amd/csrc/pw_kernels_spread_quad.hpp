@@ -1,6 +1,8 @@
-// pw_kernels_spread_quad.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_spread_quad.hpp -- part of libpworld.so (translation unit csrc/pworld.hip includes it).
 // simple_spread N = L = 6 on small grids (the latency-bound regime of BASELINE configs[1]): four cooperating waves.
 #pragma once
+
+#include "pw_kernels_spread.hpp"
 
 namespace {
 

@@ -1,6 +1,8 @@
-// pw_kernels_tag.hpp -- part of libpworld.so (one translation unit: csrc/pworld.hip includes it).
+// pw_kernels_tag.hpp -- part of libpworld.so (translation units csrc/pworld.hip and csrc/pworld_policy.hip include it).
 // simple_tag (predator-prey) streaming kernel: the "asymmetric collision path" of BASELINE.json configs[2].
 #pragma once
+
+#include "pw_kernels_spread.hpp"
 
 namespace {
 
@@ -19,24 +21,6 @@ namespace {
 //     zero-padded to the adversaries' width D (8-byte stores: every component is an (x, y) pair).
 // Requires each role to be homogeneous (the canonical scenario); otherwise the generic kernel runs.
 // ------------------------------------------------------------------------------------------
-struct TagParams {
-    int B, N, L, A, D, epw, max_episode_len, auto_reset;
-    int p_prio;     // duo kernel: raise the physics wave's issue priority (set by the launch: small and mid-size grids)
-    int obs_block;  // duo kernel: stage the wave's observation rows in LDS and store them as one contiguous block (0 / 2 / 4 = chunk floats)
-    uint64_t seed, env_id_base;
-    float dt, damp, contact_force, contact_margin, mass;
-    float sens[2], fscale[2], max_speed[2];
-    float dist_min[2][2], coll_thr2[2][2], near_thr2[2][2];  // [class_i][class_j]
-    float dist_min_lm[2], near_thr2_lm[2];                   // agent class vs landmark
-    float *pos_x, *pos_y, *vel_x, *vel_y, *lm_x, *lm_y;
-    int32_t *ep_step;
-    uint32_t *ep_count;
-    const int32_t *act;
-    float *obs, *final_obs, *rew, *rew_shared;
-    uint8_t *done, *terminal;
-    uint64_t *coll;  // [T,B,N] collision masks; written only by the COLL instantiations
-};
-
 __device__ __forceinline__ bool bits_near(float d2, float near_thr2)
 {
     // far <=> near_thr2 <= d2 < +inf on the raw bits (d2 is a sum of squares, never -0); NaN/inf stay near

@@ -1,11 +1,10 @@
-// pw_kernels_policy2.hpp -- part of libpworld.so (translation unit csrc/pworld_policy.hip includes it).
+// pw_policy_shared.hpp -- part of libpworld.so (translation unit csrc/pworld_policy.hip includes it).
 // Helpers shared by the one-launch policy rollout kernels (pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp): the LDS observation
-// row writer and the stamp / debug macros of the PW_STAMPS probe builds.
-// (The second form of the rollout -- role-specialised waves: four "matrix" waves keeping W_ih in registers, four LSTM waves running
-// the recurrence on packed vector FMAs beneath them -- lived here in rounds 2 and 3.  It was retired in round 4 together with the
-// first form: with form 3 (N <= 12) and its just-in-time variant (N >= 13) nothing selected it automatically, it was 1.5-5x slower at
-// every N (profiles/r4_policy_forms.txt), and the forms that run are each compared with the CPU oracle directly.)
+// row writer, the ordered shuffles, the ring-sink helpers and the stamp / debug macros of the PW_STAMPS probe builds.
 #pragma once
+
+#include "pw_common.hpp"
+#include "pw_lstm_math.hpp"
 
 namespace {
 

@@ -1,7 +1,7 @@
 // libpworld.so -- batched particle world for MI355X (gfx950, wave64).  This translation unit: the environment (every
-// pw_step / pw_rollout kernel and the dispatcher), the replay ring and the wire blocks; pworld_policy.hip: the actor and
-// the policy-in-the-loop rollouts.  Two units only so that they compile in parallel (and an env-kernel experiment
-// rebuilds one of them).
+// pw_step / pw_rollout kernel and the dispatcher) and the thread-local error text; pworld_replay.hip: replay ring and wire blocks;
+// pworld_policy.hip: the actor and the policy-in-the-loop rollouts; pworld_critic.hip, pworld_optim.hip: the learner's critic forward
+// and optimiser tail.  Separate units so that they compile in parallel (and an experiment rebuilds one of them).
 //
 // One fused kernel advances all B envs: _set_action -> apply_action_force ->
 // apply_environment_force (pairwise get_collision_force) -> integrate_state ->
@@ -20,28 +20,19 @@
 // Arithmetic is IEEE float32 in the upstream operation order, no FMA contraction,
 // with the deterministic softplus/exp of include/pworld_math.h, so a CPU
 // restatement reproduces every output bit (tests/ compare against oracle/).
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
 #include <type_traits>
 
-#include "pworld.h"
-#include "pworld_math.h"
-
-#include "pw_common.hpp"
+#include "pw_handle.hpp"
 #include "pw_kernels_spread.hpp"
 #include "pw_kernels_spread_quad.hpp"
 #include "pw_kernels_tag.hpp"
 #include "pw_kernels_reference.hpp"
 #include "pw_kernels_generic.hpp"
-#include "pw_kernels_replay.hpp"
-
-#include "pw_handle.hpp"
 
 namespace {
 
@@ -294,11 +285,8 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
     if (h->tag_fast && io->act_idx && io->obs && io->rew && io->rew_shared && io->done && io->terminal &&
         (size_t)kp.B * kp.N * kp.D * sizeof(float) < (1ull << 31) && !h->disp.no_stream) {
         const pw_dispatch &dp = h->disp;
-        TagParams A = h->tp;
-        A.pos_x = kp.pos_x; A.pos_y = kp.pos_y; A.vel_x = kp.vel_x; A.vel_y = kp.vel_y;
-        A.lm_x = kp.lm_x; A.lm_y = kp.lm_y; A.ep_step = kp.ep_step; A.ep_count = kp.ep_count;
-        A.act = io->act_idx; A.obs = io->obs; A.final_obs = io->final_obs; A.rew = io->rew;
-        A.rew_shared = io->rew_shared; A.done = io->done; A.terminal = io->terminal; A.coll = io->coll;
+        TagParams A = tag_params(h, io);
+        A.act = io->act_idx; A.coll = io->coll;
         const bool wc = io->coll != nullptr;  // the optional collision-mask output: its own instantiations
         hipStream_t st = static_cast<hipStream_t>(stream);
         const size_t shm = 2 * kWave * sizeof(float2) + 3 * kWave * sizeof(float) + (size_t)kp.epw * kp.L * sizeof(float2);
@@ -353,21 +341,11 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
     if (h->fast && io->act_idx && io->obs && io->rew && io->rew_shared && io->done && io->terminal &&
         (size_t)kp.B * kp.N * kp.D * sizeof(float) < (1ull << 31) && !h->disp.no_stream) {
         const pw_dispatch &dp = h->disp;
-        StreamParams A;
-        A.B = kp.B; A.N = kp.N; A.L = kp.L; A.epw = kp.epw;
+        StreamParams A = stream_params(h, io);
+        A.act = io->act_idx; A.coll = io->coll;
         // issue priority per wave, 2 bits each: the physics wave first where it shares a SIMD with output waves: -2..-4 % step
         // time on grids up to 2048 workgroups (N = 3 / 12, B = 16384), +2..4 % on the larger ones (profiles/r2_priority.txt)
         A.p_prio = dp.p_prio >= 0 ? dp.p_prio : (grid.x <= 2048 ? 3 : 0);
-        A.max_episode_len = kp.max_episode_len; A.auto_reset = kp.auto_reset;
-        A.seed = kp.seed; A.env_id_base = kp.env_id_base;
-        A.dt = kp.dt; A.damp = kp.damp; A.contact_force = kp.contact_force; A.contact_margin = kp.contact_margin;
-        A.mass = kp.mass;
-        A.dist_min = h->fc.dist_min; A.coll_thr2 = h->fc.coll_thr2; A.near_thr2 = h->fc.near_thr2;
-        A.sens = h->fc.sens; A.fscale = h->fc.fscale;
-        A.pos_x = kp.pos_x; A.pos_y = kp.pos_y; A.vel_x = kp.vel_x; A.vel_y = kp.vel_y;
-        A.lm_x = kp.lm_x; A.lm_y = kp.lm_y; A.ep_step = kp.ep_step; A.ep_count = kp.ep_count;
-        A.act = io->act_idx; A.obs = io->obs; A.final_obs = io->final_obs; A.rew = io->rew;
-        A.rew_shared = io->rew_shared; A.done = io->done; A.terminal = io->terminal; A.coll = io->coll;
         hipStream_t st = static_cast<hipStream_t>(stream);
         const size_t shm = (size_t)(kWave + kp.epw * kp.L) * sizeof(float2) + kWave * sizeof(float4);
         const bool um = kp.mass == 1.0f;
@@ -518,12 +496,8 @@ int launch_aux(pw_handle *h, int mode, const uint8_t *env_mask, float *obs, floa
     const KParams &kp = h->kp;
     if (is_comm_scenario(h->cfg.scenario)) {
         if (coll) return fail(PW_EINVAL, "the communication scenarios have no collisions");
-        if (h->cfg.scenario == PW_SIMPLE_REFERENCE)
-            hipLaunchKernelGGL((pw_reference_aux_kernel<kDimC, false>), dim3((kp.B + 31) / 32), dim3(kWave), 0,
-                               static_cast<hipStream_t>(stream), ref_params(h), mode, env_mask, obs, rew);
-        else
-            hipLaunchKernelGGL((pw_reference_aux_kernel<kDimCSL, true>), dim3((kp.B + 31) / 32), dim3(kWave), 0,
-                               static_cast<hipStream_t>(stream), ref_params(h), mode, env_mask, obs, rew);
+        const auto kernel = h->cfg.scenario == PW_SIMPLE_REFERENCE ? pw_reference_aux_kernel<kDimC, false> : pw_reference_aux_kernel<kDimCSL, true>;
+        hipLaunchKernelGGL(kernel, dim3((kp.B + 31) / 32), dim3(kWave), 0, static_cast<hipStream_t>(stream), ref_params(h), mode, env_mask, obs, rew);
         PW_HIP_CHECK(hipGetLastError());
         return PW_OK;
     }
@@ -537,11 +511,30 @@ int launch_aux(pw_handle *h, int mode, const uint8_t *env_mask, float *obs, floa
     });
 }
 
-}  // namespace
-
-namespace {
-thread_local std::string g_last_error;
+// pw_set_state / pw_get_state: one thread per agent, landmark or env, whichever there are most of
+unsigned state_copy_blocks(const KParams &kp)
+{
+    size_t n = (size_t)kp.B * (kp.N > kp.L ? kp.N : kp.L);
+    if (n < (size_t)kp.B) n = kp.B;
+    return (unsigned)((n + 255) / 256);
 }
+
+// pw_set_comm_state (to_state = 1) / pw_get_comm_state (0)
+int copy_comm_state(pw_handle *h, int to_state, float *comm, int32_t *goal, void *stream)
+{
+    if (int rc = check_ready(h)) return rc;
+    if (!is_comm_scenario(h->cfg.scenario)) return fail(PW_EINVAL, "this scenario has no communication state");
+    const int dc = dim_c_of(h->cfg.scenario);
+    const size_t n = (size_t)h->kp.B * 2 * dc;
+    hipLaunchKernelGGL(pw_reference_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), ref_params(h), to_state, dc, comm, goal);
+    PW_HIP_CHECK(hipGetLastError());
+    return PW_OK;
+}
+
+thread_local std::string g_last_error;
+
+}  // namespace
 
 extern "C" {
 
@@ -594,25 +587,16 @@ int pw_config_default(pw_config *cfg, int scenario, int num_envs, int num_agents
             cfg->agent_accel[i] = adv ? 3.0f : 4.0f;
             cfg->agent_max_speed[i] = adv ? 1.0f : 1.3f;
         }
-    } else if (scenario == PW_SIMPLE_REFERENCE) {
-        cfg->num_agents = 2;  // upstream simple_reference.make_world: two agents, three landmarks
+    } else if (is_comm_scenario(scenario)) {
+        // upstream simple_reference / simple_speaker_listener make_world: two agents (speaker + listener in the latter), three landmarks
+        const bool sl = scenario == PW_SIMPLE_SPEAKER_LISTENER;
+        cfg->num_agents = 2;
         cfg->num_landmarks = num_landmarks < 0 ? 3 : num_landmarks;
         cfg->num_adversaries = 0;
         cfg->landmark_collide = 0;
-        cfg->landmark_size = 0.05f;
+        cfg->landmark_size = sl ? 0.04f : 0.05f;
         for (int i = 0; i < 2; ++i) {
-            cfg->agent_size[i] = 0.05f;
-            cfg->agent_accel[i] = -1.0f;
-            cfg->agent_max_speed[i] = -1.0f;
-        }
-    } else if (scenario == PW_SIMPLE_SPEAKER_LISTENER) {
-        cfg->num_agents = 2;  // upstream simple_speaker_listener.make_world: speaker + listener, three landmarks
-        cfg->num_landmarks = num_landmarks < 0 ? 3 : num_landmarks;
-        cfg->num_adversaries = 0;
-        cfg->landmark_collide = 0;
-        cfg->landmark_size = 0.04f;
-        for (int i = 0; i < 2; ++i) {
-            cfg->agent_size[i] = 0.075f;
+            cfg->agent_size[i] = sl ? 0.075f : 0.05f;
             cfg->agent_accel[i] = -1.0f;
             cfg->agent_max_speed[i] = -1.0f;
         }
@@ -781,11 +765,8 @@ int pw_set_state(pw_handle *h, const float *pos, const float *vel, const float *
                  const uint32_t *ep_count, void *stream)
 {
     if (int rc = check_ready(h)) return rc;
-    const KParams &kp = h->kp;
-    size_t n = (size_t)kp.B * (kp.N > kp.L ? kp.N : kp.L);
-    if (n < (size_t)kp.B) n = kp.B;
-    hipLaunchKernelGGL(pw_scatter_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), kp, pos, vel, lm, ep_step, ep_count);
+    hipLaunchKernelGGL(pw_scatter_state_kernel, dim3(state_copy_blocks(h->kp)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), h->kp, pos, vel, lm, ep_step, ep_count);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }
@@ -793,39 +774,18 @@ int pw_set_state(pw_handle *h, const float *pos, const float *vel, const float *
 int pw_get_state(pw_handle *h, float *pos, float *vel, float *lm, int32_t *ep_step, uint32_t *ep_count, void *stream)
 {
     if (int rc = check_ready(h)) return rc;
-    const KParams &kp = h->kp;
-    size_t n = (size_t)kp.B * (kp.N > kp.L ? kp.N : kp.L);
-    if (n < (size_t)kp.B) n = kp.B;
-    hipLaunchKernelGGL(pw_gather_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), kp, pos, vel, lm, ep_step, ep_count);
+    hipLaunchKernelGGL(pw_gather_state_kernel, dim3(state_copy_blocks(h->kp)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), h->kp, pos, vel, lm, ep_step, ep_count);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }
 
 int pw_set_comm_state(pw_handle *h, const float *comm, const int32_t *goal, void *stream)
 {
-    if (int rc = check_ready(h)) return rc;
-    if (!is_comm_scenario(h->cfg.scenario)) return fail(PW_EINVAL, "this scenario has no communication state");
-    const int dc = dim_c_of(h->cfg.scenario);
-    const size_t n = (size_t)h->kp.B * 2 * dc;
-    hipLaunchKernelGGL(pw_reference_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), ref_params(h), 1, dc, const_cast<float *>(comm),
-                       const_cast<int32_t *>(goal));
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
+    return copy_comm_state(h, 1, const_cast<float *>(comm), const_cast<int32_t *>(goal), stream);
 }
 
-int pw_get_comm_state(pw_handle *h, float *comm, int32_t *goal, void *stream)
-{
-    if (int rc = check_ready(h)) return rc;
-    if (!is_comm_scenario(h->cfg.scenario)) return fail(PW_EINVAL, "this scenario has no communication state");
-    const int dc = dim_c_of(h->cfg.scenario);
-    const size_t n = (size_t)h->kp.B * 2 * dc;
-    hipLaunchKernelGGL(pw_reference_state_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), ref_params(h), 0, dc, comm, goal);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
+int pw_get_comm_state(pw_handle *h, float *comm, int32_t *goal, void *stream) { return copy_comm_state(h, 0, comm, goal, stream); }
 
 int pw_reset(pw_handle *h, const uint8_t *env_mask, float *obs, void *stream)
 {
@@ -859,486 +819,6 @@ size_t pw_algorithmic_bytes_per_env_step(const pw_handle *h)
     const size_t N = h->kp.N, L = h->kp.L, D = h->kp.D;
     // read: state 16N + landmarks 8L + action 4N; write: state 16N + obs 4ND + reward 4N + done N
     return 16 * N + 8 * L + 4 * N + 16 * N + 4 * N * D + 4 * N + N;
-}
-
-int pw_counter_add(int64_t *counter, int64_t delta, int64_t modulo, void *stream)
-{
-    if (!counter) return fail(PW_EINVAL, "null counter");
-    hipLaunchKernelGGL(pw_counter_add_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), counter, delta, modulo);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add(const pw_replay_store *st, int64_t start, const int64_t *start_dev, int32_t B, const float *obs,
-                  const int32_t *act_idx, const float *rew_shared, const float *next_obs, const float *final_obs,
-                  const uint8_t *terminal, const float *done, void *stream)
-{
-    if (!st || !obs || !act_idx || !rew_shared || !next_obs) return fail(PW_EINVAL, "null argument");
-    if (st->state_rows) return fail(PW_EINVAL, "pw_replay_add: a STATE ring is filled by pw_replay_add_state_wire only (rows do not determine the landmarks)");
-    if (st->capacity < 1 || B < 1 || B > st->capacity || start < 0) return fail(PW_EINVAL, "bad ring arguments");
-    if (st->obs_dim < 2) return fail(PW_EINVAL, "obs_dim must be >= 2");
-    if (st->act_heads < 0 || st->act_heads > 2 || (st->act_heads == 2 && (st->head_width[0] < 0 || st->head_width[1] < 1)))
-        return fail(PW_EINVAL, "bad act_heads / head_width");
-    const size_t total = (size_t)B * st->num_agents * st->obs_dim;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(pw_replay_add_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *st, start, start_dev, B, obs, act_idx, rew_shared, next_obs, final_obs, terminal, done);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add_tail(const pw_replay_store *st, int64_t start, const int64_t *start_dev, int64_t *next_start_dev,
-                       int32_t B, const float *obs, const int32_t *act_idx, const float *rew_shared,
-                       const float *next_obs, const float *final_obs, const uint8_t *terminal, const float *done,
-                       float *episode_return, double *finished_sum, int64_t *finished_count, int64_t *step_counter,
-                       void *stream)
-{
-    if (!st || !obs || !act_idx || !rew_shared || !next_obs || !terminal || !episode_return || !finished_sum ||
-        !finished_count)
-        return fail(PW_EINVAL, "null argument");
-    if (int rc = plain_ring_only(st, "pw_replay_add_tail")) return rc;
-    if (st->capacity < 1 || B < 1 || B > st->capacity || start < 0) return fail(PW_EINVAL, "bad ring arguments");
-    if (st->obs_dim < 5) return fail(PW_EINVAL, "obs_dim must be >= 5");
-    if (start_dev && next_start_dev == start_dev)
-        return fail(PW_EINVAL, "next_start_dev must not alias start_dev (every workgroup reads start_dev)");
-    const size_t total = (size_t)B * st->num_agents * st->obs_dim;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    ReplayTail tl;
-    tl.episode_return = episode_return; tl.finished_sum = finished_sum; tl.finished_count = finished_count;
-    tl.next_start_dev = next_start_dev; tl.step_counter = step_counter;
-    hipLaunchKernelGGL(pw_replay_add_tail_kernel, dim3((unsigned)blocks + 1), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *st, start, start_dev, B, obs, act_idx, rew_shared, next_obs, final_obs, terminal, done, tl);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add_rollout(const pw_replay_store *st, int64_t start, int32_t B, int32_t T, const float *obs0,
-                          const pw_step_io *io, const int32_t *act, float *episode_return, double *finished_sum,
-                          int64_t *finished_count, void *scratch, void *stream)
-{
-    if (!st || !obs0 || !io || !act || !io->obs || !io->rew_shared || !io->terminal) return fail(PW_EINVAL, "null argument");
-    if (st->per_agent) return fail(PW_EINVAL, "pw_replay_add_rollout: per-agent rings are served by pw_replay_add and pw_replay_gather only");
-    if (st->state_rows) return fail(PW_EINVAL, "pw_replay_add_rollout: a STATE ring is filled by pw_replay_add_state_wire only");
-    if (st->capacity < 1 || B < 1 || T < 1 || (int64_t)B * T > st->capacity || start < 0)
-        return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");
-    if (st->obs_dim < 5) return fail(PW_EINVAL, "obs_dim must be >= 5");
-    if (st->act_heads == 2 && st->num_agents * st->obs_dim < 2 * st->num_agents) return fail(PW_EINVAL, "two-head ring: rows too short");
-    if (episode_return && (!finished_sum || !finished_count || !scratch))
-        return fail(PW_EINVAL, "bookkeeping needs episode_return, finished_sum, finished_count and scratch");
-    const size_t total = (size_t)T * B * st->num_agents * st->obs_dim;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    const unsigned stat_blocks = episode_return ? (unsigned)((B + 255) / 256) : 0;
-    ReplayTail tl;
-    tl.episode_return = episode_return; tl.finished_sum = finished_sum; tl.finished_count = finished_count;
-    tl.next_start_dev = nullptr; tl.step_counter = nullptr;
-    hipLaunchKernelGGL(pw_replay_add_rollout_kernel, dim3((unsigned)blocks + stat_blocks), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), *st, start, B, T, obs0, *io, act, tl, stat_blocks,
-                       static_cast<unsigned long long *>(scratch));
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-size_t pw_policy_rollout_scratch_bytes(const pw_handle *h)
-{
-    if (!h) return 0;
-    return (size_t)(2 * (size_t)h->kp.B + 1) * 8;  // one partial (sum, count) per workgroup; a workgroup holds >= 1 env
-}
-
-size_t pw_replay_add_rollout_scratch_bytes(int32_t B) { return (size_t)(2 * ((B + 255) / 256) + 1) * 8; }
-
-int pw_replay_gather(const pw_replay_store *st, const int64_t *idx, int32_t b, float *out_obs, float *out_act,
-                     float *out_rew, float *out_next_obs, float *out_done, void *stream)
-{
-    if (!st || !idx) return fail(PW_EINVAL, "null argument");
-    if (b < 1) return fail(PW_EINVAL, "batch must be >= 1");
-    if (st->obs_dim < 2) return fail(PW_EINVAL, "obs_dim must be >= 2");
-    if (st->act_heads < 0 || st->act_heads > 2 || (st->act_heads == 2 && (st->head_width[0] < 0 || st->head_width[1] < 1)))
-        return fail(PW_EINVAL, "bad act_heads / head_width");
-    if (st->state_rows) {  // STATE ring: the rows are rebuilt from the slot's states and landmarks
-        if (int rc = state_ring_ok(st, "pw_replay_gather")) return rc;
-        if ((reinterpret_cast<uintptr_t>(out_obs) | reinterpret_cast<uintptr_t>(out_next_obs)) & 7)
-            return fail(PW_EINVAL, "pw_replay_gather (STATE ring): out_obs / out_next_obs must be 8-byte aligned");
-        size_t sblocks = ((size_t)b * st->num_agents * (st->obs_dim / 2) + 255) / 256;
-        if (sblocks > 8192) sblocks = 8192;
-        hipLaunchKernelGGL(pw_replay_gather_state_kernel, dim3((unsigned)sblocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           *st, idx, b, out_obs, out_act, out_rew, out_next_obs, out_done);
-        PW_HIP_CHECK(hipGetLastError());
-        return PW_OK;
-    }
-    const size_t total = (size_t)b * st->num_agents * st->obs_dim;
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(pw_replay_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *st, idx, b, out_obs, out_act, out_rew, out_next_obs, out_done);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_pack_transitions(const pw_step_io *io, int32_t B, int32_t N, int32_t D, const int32_t *sel_t,
-                        const int32_t *sel_e, int32_t R, float *rows, void *stream)
-{
-    if (!io || !sel_t || !sel_e || !rows) return fail(PW_EINVAL, "null argument");
-    if (!io->obs || !io->act_idx || !io->rew_shared) return fail(PW_EINVAL, "chunk needs obs, act_idx and rew_shared");
-    if (B < 1 || N < 1 || D < 1 || R < 1) return fail(PW_EINVAL, "bad sizes");
-    const size_t total = (size_t)R * (2 * (size_t)N * D + N + 2);
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pw_pack_transitions_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *io, B, N, D, sel_t, sel_e, R, rows);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add_packed(const pw_replay_store *st, int64_t start, int32_t R, const float *rows, void *stream)
-{
-    if (!st || !rows) return fail(PW_EINVAL, "null argument");
-    if (int rc = plain_ring_only(st, "pw_replay_add_packed")) return rc;
-    if (st->capacity < 1 || R < 1 || R > st->capacity || start < 0) return fail(PW_EINVAL, "bad ring arguments");
-    const size_t total = (size_t)R * (2 * (size_t)st->num_agents * st->obs_dim + st->num_agents + 2);
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(pw_replay_add_packed_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *st, start, R, rows);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_exchange(const pw_replay_store *st, int64_t start, int32_t R_in, const float *rows_in, const pw_step_io *io,
-                int32_t B, int32_t N, int32_t D, const int32_t *sel_t, const int32_t *sel_e, int32_t R_out,
-                float *rows_out, void *stream)
-{
-    const bool ingest = st && rows_in && R_in > 0;
-    const bool pack = io && rows_out && R_out > 0;
-    if (int rc = plain_ring_only(st, "pw_exchange")) return rc;
-    if (!ingest && !pack) return fail(PW_EINVAL, "nothing to do");
-    if (ingest && (st->capacity < 1 || R_in > st->capacity || start < 0)) return fail(PW_EINVAL, "bad ring arguments");
-    if (pack && (!sel_t || !sel_e || !io->obs || !io->act_idx || !io->rew_shared || B < 1 || N < 1 || D < 1))
-        return fail(PW_EINVAL, "chunk needs obs, act_idx, rew_shared and a selection");
-    if (ingest && pack && (st->num_agents != N || st->obs_dim != D)) return fail(PW_EINVAL, "row width mismatch");
-    const int Nn = pack ? N : st->num_agents, Dd = pack ? D : st->obs_dim;
-    const size_t W = 2 * (size_t)Nn * Dd + Nn + 2;
-    auto blocks_for = [&](int R) { size_t b = ((size_t)R * W + 255) / 256; return (int)(b > 2048 ? 2048 : b); };
-    const int nb_in = ingest ? blocks_for(R_in) : 0, nb_out = pack ? blocks_for(R_out) : 0;
-    pw_replay_store dummy_st;
-    std::memset(&dummy_st, 0, sizeof(dummy_st));
-    pw_step_io dummy_io;
-    std::memset(&dummy_io, 0, sizeof(dummy_io));
-    hipLaunchKernelGGL(pw_exchange_kernel, dim3((unsigned)(nb_in + nb_out)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       ingest ? *st : dummy_st, start, ingest ? R_in : 0, rows_in, nb_in, pack ? *io : dummy_io, B, Nn, Dd,
-                       sel_t, sel_e, pack ? R_out : 0, rows_out);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-namespace {
-void fill_wire(int32_t T, int32_t B, int32_t N, int32_t D, int32_t F, pw_chunk_wire *out)
-{
-    std::memset(out, 0, sizeof(*out));
-    out->T = T; out->B = B; out->N = N; out->D = D; out->F = F;
-    const size_t row = (size_t)B * N * D * sizeof(float);
-    size_t off = 0;
-    auto plane = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    out->obs0 = plane(row);
-    out->obs = plane((size_t)T * row);
-    out->final_rows = plane((size_t)F * row);
-    out->rew_shared = plane((size_t)T * B * sizeof(float));
-    out->act = plane((size_t)T * B * N);
-    out->fin_slot = plane((size_t)T * B);
-    out->total_bytes = off;
-}
-
-int check_wire(const pw_chunk_wire *w, const void *wire)
-{
-    if (!w || !wire) return fail(PW_EINVAL, "null argument");
-    if (w->T < 1 || w->B < 1 || w->N < 1 || w->D < 1 || w->F < 0 || w->F > 254) return fail(PW_EINVAL, "bad wire layout");
-    pw_chunk_wire ref;  // offsets are not trusted blindly: they must be the ones pw_chunk_wire_layout produces
-    fill_wire(w->T, w->B, w->N, w->D, w->F, &ref);
-    if (ref.obs0 != w->obs0 || ref.obs != w->obs || ref.final_rows != w->final_rows || ref.rew_shared != w->rew_shared ||
-        ref.act != w->act || ref.fin_slot != w->fin_slot || ref.total_bytes != w->total_bytes)
-        return fail(PW_EINVAL, "wire layout was not produced by pw_chunk_wire_layout");
-    if (reinterpret_cast<uintptr_t>(wire) & 255) return fail(PW_EINVAL, "wire block must be 256-byte aligned");
-    return PW_OK;
-}
-}  // namespace
-
-int pw_chunk_wire_layout(int32_t T, int32_t B, int32_t N, int32_t D, int32_t max_episode_len, pw_chunk_wire *out)
-{
-    if (!out) return fail(PW_EINVAL, "null argument");
-    if (T < 1 || B < 1 || N < 1 || D < 1 || max_episode_len < 0) return fail(PW_EINVAL, "bad sizes");
-    const int64_t F = max_episode_len > 0 ? ((int64_t)T + max_episode_len - 1) / max_episode_len : 0;
-    if (F > 254) return fail(PW_EINVAL, "more than 254 episode ends per env and chunk: use shorter chunks");
-    fill_wire(T, B, N, D, (int32_t)F, out);
-    return PW_OK;
-}
-
-int pw_chunk_wire_finalize(const pw_chunk_wire *w, void *wire, const float *obs0, const float *final_obs,
-                           const uint8_t *terminal, const int32_t *act, void *stream)
-{
-    if (int rc = check_wire(w, wire)) return rc;
-    if (!obs0 || !terminal || !act) return fail(PW_EINVAL, "null argument");
-    const size_t per_step = (size_t)w->B * w->N * w->D;
-    const unsigned row_blocks = (unsigned)((per_step + 255) / 256);
-    size_t act_blocks = ((size_t)w->T * w->B * w->N + 255) / 256;
-    if (act_blocks > 2048) act_blocks = 2048;
-    hipLaunchKernelGGL(pw_chunk_wire_finalize_kernel, dim3(row_blocks + (unsigned)act_blocks), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), *w, wire, obs0, final_obs, terminal, act, row_blocks);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add_wire(const pw_replay_store *st, int64_t start, const pw_chunk_wire *w, const void *wire, void *stream)
-{
-    if (!st) return fail(PW_EINVAL, "null argument");
-    if (int rc = plain_ring_only(st, "pw_replay_add_wire")) return rc;
-    if (int rc = check_wire(w, wire)) return rc;
-    if (st->num_agents != w->N || st->obs_dim != w->D) return fail(PW_EINVAL, "ring / wire shape mismatch");
-    if (st->capacity < 1 || (int64_t)w->T * w->B > st->capacity || start < 0)
-        return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");
-    const int ND = w->N * w->D;
-    const bool vec = ND % 4 == 0 && ((reinterpret_cast<uintptr_t>(st->obs) | reinterpret_cast<uintptr_t>(st->next_obs)) & 15) == 0;
-    const size_t total = (size_t)w->T * w->B * (vec ? ND / 4 : ND);
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    if (vec)
-        hipLaunchKernelGGL(pw_replay_add_wire_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           *st, start, *w, wire);
-    else
-        hipLaunchKernelGGL(pw_replay_add_wire_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
-                           *st, start, *w, wire);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-namespace {
-int state_wire_row_dim(int scenario, int N, int L, int A)
-{
-    if (scenario == PW_SIMPLE_SPREAD) return 4 + 2 * L;
-    if (scenario == PW_SIMPLE_TAG) return 4 + 2 * L + 2 * (N - 1) + 2 * (N - A);
-    return -1;
-}
-
-void fill_state_wire(int32_t scenario, int32_t T, int32_t B, int32_t N, int32_t L, int32_t A, int32_t F, pw_state_wire *out)
-{
-    std::memset(out, 0, sizeof(*out));
-    out->T = T; out->B = B; out->N = N; out->L = L; out->D = state_wire_row_dim(scenario, N, L, A); out->F = F;
-    out->scenario = scenario; out->num_adversaries = A;
-    const size_t st = (size_t)B * N * sizeof(float4);
-    size_t off = 0;
-    auto plane = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    out->state0 = plane(st);
-    out->state = plane((size_t)T * st);
-    out->final_state = plane((size_t)F * st);
-    out->lm = plane((size_t)(F + 1) * B * L * sizeof(float2));
-    out->ep0 = plane((size_t)B * sizeof(uint32_t));
-    out->rew_shared = plane((size_t)T * B * sizeof(float));
-    out->act = plane((size_t)T * B * N);
-    out->epi = plane((size_t)T * B);
-    out->total_bytes = off;
-}
-
-int check_state_wire(const pw_state_wire *w, const void *wire)
-{
-    if (!w || !wire) return fail(PW_EINVAL, "null argument");
-    if (w->T < 1 || w->B < 1 || w->N < 1 || w->L < 0 || w->F < 0 || w->F > 126 || w->num_adversaries < 0 || w->num_adversaries > w->N ||
-        w->D < 4 || w->D != state_wire_row_dim(w->scenario, w->N, w->L, w->num_adversaries))
-        return fail(PW_EINVAL, "bad state-wire layout");
-    pw_state_wire ref;  // offsets must be the ones pw_state_wire_layout produces
-    fill_state_wire(w->scenario, w->T, w->B, w->N, w->L, w->num_adversaries, w->F, &ref);
-    if (std::memcmp(&ref, w, sizeof(ref)) != 0) return fail(PW_EINVAL, "wire layout was not produced by pw_state_wire_layout");
-    if (reinterpret_cast<uintptr_t>(wire) & 255) return fail(PW_EINVAL, "wire block must be 256-byte aligned");
-    return PW_OK;
-}
-
-int state_wire_handle_ok(const pw_handle *h, const pw_state_wire *w)
-{
-    if (!h) return fail(PW_EINVAL, "null handle");
-    const bool spread = h->cfg.scenario == PW_SIMPLE_SPREAD && h->cfg.obs_mode == PW_OBS_LOCAL;
-    const bool tag = h->cfg.scenario == PW_SIMPLE_TAG;
-    if (!(spread || tag) || h->kp.D != state_wire_row_dim(h->cfg.scenario, h->kp.N, h->kp.L, h->kp.A))
-        return fail(PW_EINVAL, "state-only wire blocks serve simple_spread with the local observation and simple_tag (rows that are a "
-                               "function of {vel, pos} and the landmarks); use pw_chunk_wire_* elsewhere");
-    if (w && (w->scenario != h->cfg.scenario || w->B != h->kp.B || w->N != h->kp.N || w->L != h->kp.L ||
-              (tag && w->num_adversaries != h->kp.A)))
-        return fail(PW_EINVAL, "wire / handle shape mismatch");
-    return PW_OK;
-}
-}  // namespace
-
-int pw_state_wire_layout_scn(int32_t scenario, int32_t T, int32_t B, int32_t N, int32_t L, int32_t num_adversaries,
-                             int32_t max_episode_len, pw_state_wire *out)
-{
-    if (!out) return fail(PW_EINVAL, "null argument");
-    if (scenario != PW_SIMPLE_SPREAD && scenario != PW_SIMPLE_TAG)
-        return fail(PW_EINVAL, "state-only wire blocks serve simple_spread (local observation) and simple_tag");
-    if (scenario == PW_SIMPLE_SPREAD) num_adversaries = 0;
-    if (T < 1 || B < 1 || N < 1 || L < 0 || max_episode_len < 0 || num_adversaries < 0 || num_adversaries > N) return fail(PW_EINVAL, "bad sizes");
-    const int64_t F = max_episode_len > 0 ? ((int64_t)T + max_episode_len - 1) / max_episode_len : 0;
-    if (F > 126) return fail(PW_EINVAL, "more than 126 episode ends per env and chunk: use shorter chunks");
-    fill_state_wire(scenario, T, B, N, L, num_adversaries, (int32_t)F, out);
-    return PW_OK;
-}
-
-int pw_state_wire_layout(int32_t T, int32_t B, int32_t N, int32_t L, int32_t max_episode_len, pw_state_wire *out)
-{
-    return pw_state_wire_layout_scn(PW_SIMPLE_SPREAD, T, B, N, L, 0, max_episode_len, out);
-}
-
-int pw_state_wire_begin(const pw_handle *h, const pw_state_wire *w, void *wire, void *stream)
-{
-    if (int rc = check_ready(h)) return rc;
-    if (int rc = check_state_wire(w, wire)) return rc;
-    if (int rc = state_wire_handle_ok(h, w)) return rc;
-    const KParams &kp = h->kp;
-    const size_t n = (size_t)w->B * (w->N > w->L ? w->N : w->L);
-    hipLaunchKernelGGL(pw_state_wire_begin_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *w, wire, kp.pos_x, kp.pos_y, kp.vel_x, kp.vel_y, kp.lm_x, kp.lm_y, kp.ep_count);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_state_wire_finalize(const pw_handle *h, const pw_state_wire *w, void *wire, const float *obs, const float *final_obs,
-                           const uint8_t *terminal, const int32_t *act, void *stream)
-{
-    if (int rc = check_state_wire(w, wire)) return rc;
-    if (int rc = state_wire_handle_ok(h, w)) return rc;
-    if (!obs || !terminal || !act) return fail(PW_EINVAL, "null argument");
-    if ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(final_obs)) & 7)
-        return fail(PW_EINVAL, "obs and final_obs must be 8-byte aligned");
-    const size_t BN = (size_t)w->B * w->N, total = (size_t)w->T * BN;
-    size_t copy_blocks = (total + 255) / 256;
-    if (copy_blocks > 8192) copy_blocks = 8192;
-    const unsigned env_blocks = (unsigned)((BN + 255) / 256);
-    size_t act_blocks = (total + 255) / 256;
-    if (act_blocks > 2048) act_blocks = 2048;
-    // the landmarks an in-chunk reset drew: simple_spread U(-1, 1), simple_tag U(-0.9, 0.9) (upstream reset_world)
-    const float lm_lo = w->scenario == PW_SIMPLE_TAG ? -0.9f : -1.0f, lm_hi = w->scenario == PW_SIMPLE_TAG ? 0.9f : 1.0f;
-    hipLaunchKernelGGL(pw_state_wire_finalize_kernel, dim3((unsigned)(copy_blocks + env_blocks + act_blocks)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), *w, wire, obs, final_obs, terminal, act, (uint64_t)h->kp.seed,
-                       (uint64_t)h->kp.env_id_base, lm_lo, lm_hi, (unsigned)copy_blocks, env_blocks);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add_state_wire(const pw_replay_store *st, int64_t start, const pw_state_wire *w, const void *wire, void *stream)
-{
-    if (!st) return fail(PW_EINVAL, "null argument");
-    if (int rc = check_state_wire(w, wire)) return rc;
-    if (st->num_agents != w->N || st->obs_dim != w->D) return fail(PW_EINVAL, "ring / wire shape mismatch");
-    if (st->capacity < 1 || (int64_t)w->T * w->B > st->capacity || start < 0)
-        return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if (st->state_rows) {  // STATE ring: copy what the block carries; pw_replay_gather rebuilds the rows
-        if (int rc = state_ring_ok(st, "pw_replay_add_state_wire")) return rc;
-        if (st->scenario != w->scenario || st->num_landmarks != w->L || st->num_adversaries != w->num_adversaries)
-            return fail(PW_EINVAL, "STATE ring / wire scenario mismatch");
-        size_t blocks = ((size_t)w->T * w->B * w->N + 255) / 256;
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(pw_replay_add_state_wire_to_state_ring_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *st, start, *w, wire);
-        PW_HIP_CHECK(hipGetLastError());
-        return PW_OK;
-    }
-    if (int rc = plain_ring_only(st, "pw_replay_add_state_wire")) return rc;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(st->obs) | reinterpret_cast<uintptr_t>(st->next_obs);
-    if (al & 7) return fail(PW_EINVAL, "ring observation planes must be 8-byte aligned");
-    if (w->scenario != PW_SIMPLE_SPREAD) {  // simple_tag: 8-byte units (other agents' states feed every row)
-        size_t blocks = ((size_t)w->T * w->B * w->N * (w->D / 2) + 255) / 256;
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(pw_replay_add_state_wire_units_kernel, dim3((unsigned)blocks), dim3(256), 0, s, *st, start, *w, wire);
-        PW_HIP_CHECK(hipGetLastError());
-        return PW_OK;
-    }
-    const bool v4 = w->L % 2 == 0 && (al & 15) == 0;
-    const size_t total = (size_t)w->T * w->B * w->N * (v4 ? w->D / 4 : w->D / 2);
-    size_t blocks = (total + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    if (v4)
-        hipLaunchKernelGGL(pw_replay_add_state_wire_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, s, *st, start, *w, wire);
-    else
-        hipLaunchKernelGGL(pw_replay_add_state_wire_kernel<2>, dim3((unsigned)blocks), dim3(256), 0, s, *st, start, *w, wire);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-}  // extern "C"
-
-namespace {
-void fill_ref_wire(int32_t T, int32_t B, int32_t F, pw_ref_wire *out)
-{
-    std::memset(out, 0, sizeof(*out));
-    out->T = T; out->B = B; out->F = F;
-    const size_t hd = (size_t)B * kRefN * kRefHead * sizeof(float);
-    size_t off = 0;
-    auto plane = [&](size_t bytes) { const size_t o = off; off = align_up(off + bytes, 256); return o; };
-    out->head0 = plane(hd);
-    out->head = plane((size_t)T * hd);
-    out->final_head = plane((size_t)F * hd);
-    out->goal = plane((size_t)(F + 1) * B * kRefN);
-    out->comm0 = plane((size_t)B * kRefN);
-    out->rew_shared = plane((size_t)T * B * sizeof(float));
-    out->act = plane((size_t)T * B * kRefN * 2);
-    out->epi = plane((size_t)T * B);
-    out->total_bytes = off;
-}
-
-int check_ref_wire(const pw_ref_wire *w, const void *wire)
-{
-    if (!w || !wire) return fail(PW_EINVAL, "null argument");
-    if (w->T < 1 || w->B < 1 || w->F < 0 || w->F > 126) return fail(PW_EINVAL, "bad ref-wire layout");
-    pw_ref_wire ref;
-    fill_ref_wire(w->T, w->B, w->F, &ref);
-    if (std::memcmp(&ref, w, sizeof(ref)) != 0) return fail(PW_EINVAL, "wire layout was not produced by pw_ref_wire_layout");
-    if (reinterpret_cast<uintptr_t>(wire) & 255) return fail(PW_EINVAL, "wire block must be 256-byte aligned");
-    return PW_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int pw_ref_wire_layout(int32_t T, int32_t B, int32_t max_episode_len, pw_ref_wire *out)
-{
-    if (!out) return fail(PW_EINVAL, "null argument");
-    if (T < 1 || B < 1 || max_episode_len < 0) return fail(PW_EINVAL, "bad sizes");
-    const int64_t F = max_episode_len > 0 ? ((int64_t)T + max_episode_len - 1) / max_episode_len : 0;
-    if (F > 126) return fail(PW_EINVAL, "more than 126 episode ends per env and chunk: use shorter chunks");
-    fill_ref_wire(T, B, (int32_t)F, out);
-    return PW_OK;
-}
-
-int pw_ref_wire_finalize(const pw_ref_wire *w, void *wire, const float *obs0, const float *obs, const float *final_obs,
-                         const uint8_t *terminal, const int32_t *act, void *stream)
-{
-    if (int rc = check_ref_wire(w, wire)) return rc;
-    if (!obs0 || !obs || !terminal || !act) return fail(PW_EINVAL, "null argument");
-    if (w->F > 0 && !final_obs) return fail(PW_EINVAL, "final_obs is needed when episodes end inside the chunk");
-    const size_t BN = (size_t)w->B * kRefN;
-    size_t copy_blocks = ((size_t)w->T * BN * kRefHead + 255) / 256;
-    if (copy_blocks > 8192) copy_blocks = 8192;
-    const unsigned env_blocks = (unsigned)((BN + 255) / 256);
-    size_t act_blocks = ((size_t)w->T * BN * 2 + 255) / 256;
-    if (act_blocks > 2048) act_blocks = 2048;
-    hipLaunchKernelGGL(pw_ref_wire_finalize_kernel, dim3((unsigned)(copy_blocks + env_blocks + act_blocks)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), *w, wire, obs0, obs, final_obs, terminal, act, (unsigned)copy_blocks, env_blocks);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
-}
-
-int pw_replay_add_ref_wire(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire, void *stream)
-{
-    if (!st) return fail(PW_EINVAL, "null argument");
-    if (int rc = check_ref_wire(w, wire)) return rc;
-    if (st->state_rows || st->per_agent || st->act_heads != 2 || st->head_width[1] != PW_DIM_C || (st->head_width[0] != 0 && st->head_width[0] != 5))
-        return fail(PW_EINVAL, "pw_replay_add_ref_wire: the ring must be the two-head ring of simple_reference (act_heads = 2, head widths 5 | dim_c)");
-    if (st->num_agents != kRefN || st->obs_dim != kRefD) return fail(PW_EINVAL, "ring / wire shape mismatch (simple_reference: N = 2, D = 21)");
-    if (st->capacity < 1 || (int64_t)w->T * w->B > st->capacity || start < 0)
-        return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");
-    size_t blocks = ((size_t)w->T * w->B * kRefN * kRefD + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(pw_replay_add_ref_wire_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), *st, start, *w, wire);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
 }
 
 }  // extern "C"

@@ -1,28 +1,9 @@
 // libpworld.so, third translation unit -- the learner's critic forward and TD target (rls/model/ac_network_multi_gumbel.py
-// CriticNetwork, ddpg_gumbel_fix.py:148-154): pw_critic_forward.  The kernel is csrc/pw_kernels_critic.hpp; the gate functions,
-// the LDS barrier and the lane exchanges are the actor's (included, not copied: the environment headers come along because
-// the actor's headers and pw_handle.hpp name their types; none of their kernels is instantiated here).  Declared in include/pworld.h; the error text
+// CriticNetwork, ddpg_gumbel_fix.py:148-154): pw_critic_forward.  The kernel is csrc/pw_kernels_critic.hpp; the gate functions
+// and the LDS barrier are the actor's (pw_lstm_math.hpp: included, not copied).  Declared in include/pworld.h; the error text
 // is shared with pworld.hip.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-#include <string>
-#include <type_traits>
-
-#include "pworld.h"
-#include "pworld_math.h"
-
-#include "pw_common.hpp"
-#include "pw_kernels_spread.hpp"
-#include "pw_kernels_tag.hpp"
-#include "pw_kernels_reference.hpp"
-#include "pw_handle.hpp"
-#include "pw_kernels_policy.hpp"
-#include "pw_kernels_actor16.hpp"
+#include "pw_host.hpp"
+#include "pw_lstm_math.hpp"
 #include "pw_kernels_critic.hpp"
 
 namespace {

@@ -2,16 +2,9 @@
 // update of the target network, ddpg_gumbel_fix.py:172-173,208-213) and pw_soft_update (:36-47), one launch each.  The kernels
 // and their arithmetic order are csrc/pw_kernels_optim.hpp.  Declared in include/pworld.h; the error text is shared with
 // pworld.hip.
-#include <hip/hip_runtime.h>
-
 #include <cmath>
-#include <cstdint>
-#include <string>
 
-#include "pworld.h"
-#include "pworld_math.h"
-
-#include "pw_common.hpp"   // fail(), PW_HIP_CHECK (none of its device functions is used here)
+#include "pw_host.hpp"
 #include "pw_kernels_optim.hpp"
 
 namespace {

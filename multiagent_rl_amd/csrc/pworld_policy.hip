@@ -3,31 +3,58 @@
 // pw_actor_head / pw_actor_fused, pw_policy_rollout (the env step inside it is pw_kernels_spread.hpp's /
 // pw_kernels_tag.hpp's arithmetic), the rollout bookkeeping launches and the device-math test hook.
 // Entry points are declared in include/pworld.h; the handle and the error text are shared with pworld.hip.
-#include <hip/hip_runtime.h>
-
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-#include <string>
-#include <type_traits>
-
-#include "pworld.h"
-#include "pworld_math.h"
-
-#include "pw_common.hpp"
-#include "pw_kernels_spread.hpp"
-#include "pw_kernels_tag.hpp"
-#include "pw_kernels_reference.hpp"
 #include "pw_handle.hpp"
 #include "pw_kernels_policy.hpp"
 #include "pw_kernels_actor16.hpp"
-#include "pw_kernels_policy2.hpp"
 #include "pw_kernels_policy3.hpp"
 #include "pw_kernels_policy3j.hpp"
 #include "pw_kernels_policy_tag.hpp"
 #include "pw_kernels_policy_ref.hpp"
+
+namespace {
+
+int g_actor_bf16x3 = 0;  // process-wide, off unless pw_actor_set_bf16x3 turns it on (no environment reads)
+
+// The part of ActorFusedArgs every launch form fills the same way: weights, sizes, heads, Philox seed / step and the
+// environments per 96-row workgroup (the 16x16x4-core kernels override E).  X, H, logits, act and bf16x3 stay with the caller.
+ActorFusedArgs actor_args(const float *frag, const float *b1, const float *b_ih, const float *w_hh_fw, const float *w_hh_bw,
+                          const float *w2, const float *b2, int B, int N, int D, int relu_out, int n_out0, int n_out1,
+                          uint64_t seed, uint64_t step, const int64_t *step_dev)
+{
+    ActorFusedArgs a = {};
+    a.frag = frag; a.b1 = b1; a.bih = b_ih; a.whh_f = w_hh_fw; a.whh_r = w_hh_bw; a.w2 = w2; a.b2 = b2;
+    a.B = B; a.N = N; a.D = D; a.relu_out = relu_out; a.n_out0 = n_out0; a.n_out1 = n_out1;
+    a.E = 96 / N < 16 ? 96 / N : 16;
+    a.seed = seed; a.step = step; a.step_dev = step_dev;
+    return a;
+}
+
+// A rollout sink's ring has the rollout's row shape and room for the chunk of `rows` transitions from a valid cursor, and its
+// bookkeeping pointers come together.
+int sink_fits(const pw_rollout_sink *sink, int N, int D, int64_t rows)
+{
+    const pw_replay_store *ring = sink->ring;
+    if (ring && (ring->num_agents != N || ring->obs_dim != D || ring->capacity < 1 || sink->ring_start < 0 ||
+                 sink->ring_start >= ring->capacity || rows > ring->capacity))
+        return fail(PW_EINVAL, "ring sink: shape mismatch or the chunk does not fit the ring");
+    if (sink->episode_return && (!sink->finished_sum || !sink->finished_count || !sink->scratch))
+        return fail(PW_EINVAL, "bookkeeping needs episode_return, finished_sum, finished_count and scratch");
+    return PW_OK;
+}
+
+// The sink into the argument block of a one-launch rollout (PolicyRolloutArgs / PolicyRolloutTagArgs / PolicyRolloutRefArgs: the
+// same fields under the same names; the block is zeroed, so without a sink nothing is set).
+template <typename Args>
+void sink_into(Args &P, const pw_rollout_sink *sink)
+{
+    if (sink && sink->ring) { P.ring = *sink->ring; P.has_ring = 1; P.ring_start = sink->ring_start; }
+    if (sink && sink->episode_return) {
+        P.episode_return = sink->episode_return; P.finished_sum = sink->finished_sum;
+        P.finished_count = sink->finished_count; P.scratch = static_cast<unsigned long long *>(sink->scratch);
+    }
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -57,10 +84,6 @@ int pw_actor_head(const float *H, const float *w2, const float *b2, int64_t rows
     return PW_OK;
 }
 
-namespace {
-int g_actor_bf16x3 = 0;  // process-wide, off unless pw_actor_set_bf16x3 turns it on (no environment reads)
-}  // namespace
-
 int pw_actor_set_bf16x3(int32_t on)
 {
     const int prev = g_actor_bf16x3;
@@ -80,11 +103,8 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
     if (in_dim < 1 || in_dim > 64) return fail(PW_EINVAL, "in_dim must be in [1, 64]");
     if ((reinterpret_cast<uintptr_t>(frag) | reinterpret_cast<uintptr_t>(w_hh_fw) | reinterpret_cast<uintptr_t>(w_hh_bw)) & 15)
         return fail(PW_EINVAL, "frag and w_hh must be 16-byte aligned");
-    ActorFusedArgs a;
-    a.X = X; a.frag = frag; a.b1 = b1; a.bih = b_ih; a.whh_f = w_hh_fw; a.whh_r = w_hh_bw; a.w2 = w2; a.b2 = b2;
-    a.B = (int)B; a.N = N; a.D = in_dim; a.relu_out = relu_out; a.n_out0 = n_out0; a.n_out1 = n_out1;
-    a.E = 96 / N < 16 ? 96 / N : 16;
-    a.seed = seed; a.step = step; a.step_dev = step_dev; a.H = H; a.logits = logits; a.act = act;
+    ActorFusedArgs a = actor_args(frag, b1, b_ih, w_hh_fw, w_hh_bw, w2, b2, (int)B, N, in_dim, relu_out, n_out0, n_out1, seed, step, step_dev);
+    a.X = X; a.H = H; a.logits = logits; a.act = act;
     a.bf16x3 = g_actor_bf16x3;  // honoured by the 16x16x4-core kernel (N <= 16) only
     const int S1C = (in_dim + 7) / 8, S1 = 4 * S1C;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -137,31 +157,22 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     const KParams &kp = h->kp;
     if (h->cfg.scenario == PW_SIMPLE_REFERENCE) {
         // the MultiDiscrete scenario: two-head actor [5 | PW_DIM_C] (w2 [15,64], b2 [15]), act_out [T,B,N,2]
-        const bool rsink = sink && sink->ring;
         if (sink) {
             if (sink->ring && (sink->ring->act_heads != 2 || sink->ring->per_agent || sink->ring->head_width[1] != PW_DIM_C ||
                                (sink->ring->head_width[0] != 0 && sink->ring->head_width[0] != 5)))
                 return fail(PW_EINVAL, "pw_policy_rollout sink on simple_reference: the ring must be the two-head ring (act_heads = 2, widths 5 | dim_c)");
-            if (sink->ring && (sink->ring->num_agents != 2 || sink->ring->obs_dim != kp.D || sink->ring->capacity < 1 ||
-                               sink->ring_start < 0 || sink->ring_start >= sink->ring->capacity || (int64_t)num_steps * kp.B > sink->ring->capacity))
-                return fail(PW_EINVAL, "ring sink: shape mismatch or the chunk does not fit the ring");
-            if (sink->episode_return && (!sink->finished_sum || !sink->finished_count || !sink->scratch))
-                return fail(PW_EINVAL, "bookkeeping needs episode_return, finished_sum, finished_count and scratch");
+            if (int rc = sink_fits(sink, 2, kp.D, (int64_t)num_steps * kp.B)) return rc;
         }
         if (io->act_idx || io->act_vec || io->act_comm || io->coll)
             return fail(PW_EINVAL, "pw_policy_rollout produces the actions itself (act_out) and has no coll output");
-        if (!rsink && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
+        if (!(sink && sink->ring) && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
             return fail(PW_EINVAL, "without a ring sink, act_out and the obs, rew, rew_shared, done, terminal outputs are required");
         if ((reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(frag) |
              reinterpret_cast<uintptr_t>(w_hh_fw) | reinterpret_cast<uintptr_t>(w_hh_bw)) & 15)
             return fail(PW_EINVAL, "obs, final_obs, frag and w_hh must be 16-byte aligned");
         PolicyRolloutRefArgs R;
         std::memset(&R, 0, sizeof(R));
-        ActorFusedArgs &ra = R.A;
-        ra.frag = frag; ra.b1 = b1; ra.bih = b_ih; ra.whh_f = w_hh_fw; ra.whh_r = w_hh_bw; ra.w2 = w2; ra.b2 = b2;
-        ra.B = kp.B; ra.N = 2; ra.D = kp.D; ra.relu_out = relu_out; ra.n_out0 = 5; ra.n_out1 = PW_DIM_C;
-        ra.E = 16;
-        ra.seed = seed; ra.step = step; ra.step_dev = step_dev;
+        R.A = actor_args(frag, b1, b_ih, w_hh_fw, w_hh_bw, w2, b2, kp.B, 2, kp.D, relu_out, 5, PW_DIM_C, seed, step, step_dev);  // E = 16
         if (h->actor_bf16x3) return fail(PW_EINVAL, "PW_ACTOR_BF16X3 serves the simple_spread rollout (and pw_actor_fused) only");
         R.V = ref_params(h);
         R.T = num_steps; R.act_out = act_out;
@@ -171,11 +182,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         if (rS1C != 3) return fail(PW_EINVAL, "simple_reference one-launch rollout: the observation is 21 numbers (3 landmarks)");
         const size_t rshm = actor16_lds_floats(2, 32, 4 * rS1C) * sizeof(float) + (size_t)2 * kFusedRows * kp.D * sizeof(float) + 2 * kFusedRows * sizeof(int32_t) +
                             16 * (sizeof(double) + sizeof(int)) + (size_t)actor16_noise_floats(32, 5 + PW_DIM_C) * sizeof(float);
-        if (rsink) { R.ring = *sink->ring; R.has_ring = 1; R.ring_start = sink->ring_start; }
-        if (sink && sink->episode_return) {
-            R.episode_return = sink->episode_return; R.finished_sum = sink->finished_sum;
-            R.finished_count = sink->finished_count; R.scratch = static_cast<unsigned long long *>(sink->scratch);
-        }
+        sink_into(R, sink);
         if (sink) {
             static unsigned long long attr_sets = 0; /* bit = device */
             PW_LDS_OPTIN(&attr_sets, (pw_policy_rollout_ref_kernel<3, true>));
@@ -209,11 +216,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
             if (sink->ring->scenario != h->cfg.scenario || sink->ring->num_landmarks != kp.L || sink->ring->num_adversaries != (tag ? kp.A : 0))
                 return fail(PW_EINVAL, "pw_policy_rollout sink: the STATE ring belongs to another scenario / shape");
         } else if (int rc = plain_ring_only(sink->ring, "pw_policy_rollout sink")) return rc;
-        if (sink->ring && (sink->ring->num_agents != kp.N || sink->ring->obs_dim != kp.D || sink->ring->capacity < 1 ||
-                           sink->ring_start < 0 || sink->ring_start >= sink->ring->capacity || (int64_t)num_steps * kp.B > sink->ring->capacity))
-            return fail(PW_EINVAL, "ring sink: shape mismatch or the chunk does not fit the ring");
-        if (sink->episode_return && (!sink->finished_sum || !sink->finished_count || !sink->scratch))
-            return fail(PW_EINVAL, "bookkeeping needs episode_return, finished_sum, finished_count and scratch");
+        if (int rc = sink_fits(sink, kp.N, kp.D, (int64_t)num_steps * kp.B)) return rc;
     }
     if ((reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(frag) |
          reinterpret_cast<uintptr_t>(w_hh_fw) | reinterpret_cast<uintptr_t>(w_hh_bw) |
@@ -223,23 +226,11 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         PolicyRolloutTagArgs Q;
         std::memset(&Q, 0, sizeof(Q));
         ActorFusedArgs &qa = Q.A;
-        qa.frag = frag; qa.b1 = b1; qa.bih = b_ih; qa.whh_f = w_hh_fw; qa.whh_r = w_hh_bw; qa.w2 = w2; qa.b2 = b2;
-        qa.B = kp.B; qa.N = kp.N; qa.D = kp.D; qa.relu_out = relu_out; qa.n_out0 = 5; qa.n_out1 = 0;
-        qa.E = 96 / kp.N < 16 ? 96 / kp.N : 16;
-        qa.seed = seed; qa.step = step; qa.step_dev = step_dev;
+        qa = actor_args(frag, b1, b_ih, w_hh_fw, w_hh_bw, w2, b2, kp.B, kp.N, kp.D, relu_out, 5, 0, seed, step, step_dev);
         if (h->actor_bf16x3) return fail(PW_EINVAL, "PW_ACTOR_BF16X3 serves the simple_spread rollout (and pw_actor_fused) only");
-        Q.V = h->tp;
-        TagParams &tv = Q.V;
-        tv.pos_x = kp.pos_x; tv.pos_y = kp.pos_y; tv.vel_x = kp.vel_x; tv.vel_y = kp.vel_y;
-        tv.lm_x = kp.lm_x; tv.lm_y = kp.lm_y; tv.ep_step = kp.ep_step; tv.ep_count = kp.ep_count;
-        tv.obs = io->obs; tv.final_obs = io->final_obs; tv.rew = io->rew; tv.rew_shared = io->rew_shared;
-        tv.done = io->done; tv.terminal = io->terminal;
+        Q.V = tag_params(h, io);
         Q.T = num_steps; Q.act_out = act_out;
-        if (have_sink) { Q.ring = *sink->ring; Q.has_ring = 1; Q.ring_start = sink->ring_start; }
-        if (sink && sink->episode_return) {
-            Q.episode_return = sink->episode_return; Q.finished_sum = sink->finished_sum;
-            Q.finished_count = sink->finished_count; Q.scratch = static_cast<unsigned long long *>(sink->scratch);
-        }
+        sink_into(Q, sink);
         const int tS1C = (kp.D + 7) / 8;
         const size_t tshm = policy_tag_lds_bytes(4 * tS1C, kp.D, qa.E, kp.L, kp.N);
         if (tshm > 160 * 1024 || tS1C < 2 || tS1C > 6)
@@ -263,28 +254,11 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     PolicyRolloutArgs P;
     std::memset(&P, 0, sizeof(P));
     ActorFusedArgs &a = P.A;
-    a.frag = frag; a.b1 = b1; a.bih = b_ih; a.whh_f = w_hh_fw; a.whh_r = w_hh_bw; a.w2 = w2; a.b2 = b2;
-    a.B = kp.B; a.N = kp.N; a.D = kp.D; a.relu_out = relu_out; a.n_out0 = 5; a.n_out1 = 0;
-    a.E = 96 / kp.N < 16 ? 96 / kp.N : 16;
-    a.seed = seed; a.step = step; a.step_dev = step_dev; a.bf16x3 = h->actor_bf16x3;
-    StreamParams &A = P.V;
-    A.B = kp.B; A.N = kp.N; A.L = kp.L; A.epw = kp.epw;
-    A.max_episode_len = kp.max_episode_len; A.auto_reset = kp.auto_reset;
-    A.seed = kp.seed; A.env_id_base = kp.env_id_base;
-    A.dt = kp.dt; A.damp = kp.damp; A.contact_force = kp.contact_force; A.contact_margin = kp.contact_margin;
-    A.mass = kp.mass;
-    A.dist_min = h->fc.dist_min; A.coll_thr2 = h->fc.coll_thr2; A.near_thr2 = h->fc.near_thr2;
-    A.sens = h->fc.sens; A.fscale = h->fc.fscale;
-    A.pos_x = kp.pos_x; A.pos_y = kp.pos_y; A.vel_x = kp.vel_x; A.vel_y = kp.vel_y;
-    A.lm_x = kp.lm_x; A.lm_y = kp.lm_y; A.ep_step = kp.ep_step; A.ep_count = kp.ep_count;
-    A.obs = io->obs; A.final_obs = io->final_obs; A.rew = io->rew; A.rew_shared = io->rew_shared;
-    A.done = io->done; A.terminal = io->terminal;
+    a = actor_args(frag, b1, b_ih, w_hh_fw, w_hh_bw, w2, b2, kp.B, kp.N, kp.D, relu_out, 5, 0, seed, step, step_dev);
+    a.bf16x3 = h->actor_bf16x3;
+    P.V = stream_params(h, io);
     P.T = num_steps; P.act_out = act_out;
-    if (have_sink) { P.ring = *sink->ring; P.has_ring = 1; P.ring_start = sink->ring_start; }
-    if (sink && sink->episode_return) {
-        P.episode_return = sink->episode_return; P.finished_sum = sink->finished_sum;
-        P.finished_count = sink->finished_count; P.scratch = static_cast<unsigned long long *>(sink->scratch);
-    }
+    sink_into(P, sink);
     const int S1C = (kp.D + 7) / 8, S1 = 4 * S1C;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // Kernel forms.  pw_policy_rollout3_kernel (pw_kernels_policy3.hpp): the whole BiLSTM on v_mfma_f32_16x16x4_f32, one timestep
@@ -384,6 +358,12 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     }
 }
 
+size_t pw_policy_rollout_scratch_bytes(const pw_handle *h)
+{
+    if (!h) return 0;
+    return (size_t)(2 * (size_t)h->kp.B + 1) * 8;  // one partial (sum, count) per workgroup; a workgroup holds >= 1 env
+}
+
 int pw_rollout_tail(const float *rew_shared, const uint8_t *terminal, int32_t B, float *episode_return,
                     double *finished_sum, int64_t *finished_count, int64_t *counter0, int64_t delta0, int64_t modulo0,
                     int64_t *counter1, int64_t delta1, int64_t modulo1, void *stream)
@@ -391,9 +371,7 @@ int pw_rollout_tail(const float *rew_shared, const uint8_t *terminal, int32_t B,
     if (!rew_shared || !terminal || !episode_return || !finished_sum || !finished_count)
         return fail(PW_EINVAL, "null argument");
     if (B < 1) return fail(PW_EINVAL, "bad sizes");
-    TailCounters tc;
-    tc.c0 = counter0; tc.d0 = delta0; tc.m0 = modulo0;
-    tc.c1 = counter1; tc.d1 = delta1; tc.m1 = modulo1;
+    const TailCounters tc = {counter0, counter1, delta0, modulo0, delta1, modulo1};
     hipLaunchKernelGGL(pw_episode_stats_kernel, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), rew_shared,
                        terminal, B, episode_return, finished_sum, finished_count, tc);
     PW_HIP_CHECK(hipGetLastError());

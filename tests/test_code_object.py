@@ -1,13 +1,14 @@
 """CPU: what the compiler made of every kernel in libpworld.so ("no scratch in a rollout kernel's step loop").
 
 Read from the built objects with tools/code_object.py: the AMDGPU metadata notes of the gfx950 code objects (registers, spills,
-private segment) and their disassembly (scratch-memory instructions).  The rule, for EVERY kernel of both translation units:
+private segment) and their disassembly (scratch-memory instructions).  The rule, for EVERY kernel of every translation unit:
   * no VGPR is spilled (.vgpr_spill_count == 0) -- SGPR spills are fine, they go to lanes of a VGPR, not to memory;
   * no scratch-memory instruction exists anywhere in the kernel (so none can sit in a step loop).
 A kernel may still carry a small private segment that nothing accesses (the compiler reserves 36 bytes for some instantiations of the
 one-launch policy rollouts and then never touches them): allowed, and bounded here so that a real stack object does not hide there.
 """
 import os
+import re
 import sys
 
 import pytest
@@ -27,13 +28,29 @@ def kernels():
     return code_object.all_kernels()
 
 
-def test_both_units_are_there(kernels):
+def test_all_units_are_there(kernels):
     names = ' '.join(kernels)
     for family in ('pw_spread_quad_kernel', 'pw_spread_duo_kernel', 'pw_tag_duo_kernel', 'pw_rollout_kernel', 'pw_reference_rollout_kernel',
                    'pw_policy_rollout3_kernel', 'pw_policy_rollout3j_kernel', 'pw_policy_rollout_tag_kernel',
                    'pw_policy_rollout_ref_kernel', 'pw_actor_fused16_kernel', 'pw_replay_gather_kernel'):
         assert family in names, family
     assert len(kernels) > 150
+
+
+def _kernels_defined_in(header):
+    src = open(os.path.join(ROOT, 'multiagent_rl_amd', 'csrc', header)).read()
+    return set(re.findall(r'__global__ void (?:__launch_bounds__\(\w+\) )?(pw_\w+_kernel)\(', src))
+
+
+def test_small_units_carry_only_their_own_kernels(kernels):
+    """A unit that includes a header for its device functions compiles that header's non-template kernels too (all_kernels merges
+    the units by name and hides it): the critic, optimiser and replay units include no such header."""
+    per_unit = code_object.per_unit_kernels()
+    family = lambda name: re.match(r'(?:void )?(\w+)', name).group(1)  # noqa: E731
+    assert per_unit['pworld_critic'] and {family(n) for n in per_unit['pworld_critic']} == {'pw_critic_forward_kernel'}
+    assert {family(n) for n in per_unit['pworld_optim']} == _kernels_defined_in('pw_kernels_optim.hpp') == {'pw_adam_step_kernel', 'pw_soft_update_kernel'}
+    replay = _kernels_defined_in('pw_kernels_replay.hpp')
+    assert len(replay) >= 18 and {family(n) for n in per_unit['pworld_replay']} == replay
 
 
 def test_no_kernel_spills_vector_registers(kernels):

@@ -5,8 +5,11 @@ registers / spills / private segment per kernel, its disassembly the number of s
 
     python3 tools/code_object.py            # table of every kernel that spills, has a private segment or touches scratch
     python3 tools/code_object.py --all
+    python3 tools/code_object.py --compare DIR   # DIR: the csrc/_obj of another build at the same flags (e.g. the parent commit's)
 
-tests/test_code_object.py holds the rule: no kernel spills a VGPR and no kernel executes a scratch instruction."""
+tests/test_code_object.py holds the rule: no kernel spills a VGPR and no kernel executes a scratch instruction.  --compare is the
+proof a host-side refactor owes: per kernel, matched by mangled name, the metadata FIELDS and the disassembly are those of DIR."""
+import glob
 import os
 import re
 import subprocess
@@ -38,7 +41,7 @@ def code_object(obj, workdir):
 
 
 def kernels(co):
-    """-> {mangled kernel name: {field: int, 'scratch_insts': int}}"""
+    """-> {mangled kernel name: {field: int, 'scratch_insts': int, 'asm': [instruction lines without the // address comments]}}"""
     notes = subprocess.run([os.path.join(LLVM, 'llvm-readelf'), '--notes', co], capture_output=True, text=True, check=True).stdout
     out = {}
     # one block per kernel: from its '.agpr_count' (first key of the sorted map after .args) to the next
@@ -46,7 +49,7 @@ def kernels(co):
         blk = '\n    .agpr_count:' + blk
         name = re.search(r'\n\s+\.name:\s+(\S+)', blk).group(1)
         out[name] = {f: int(re.search(r'\n\s+%s:\s+(\d+)' % re.escape(f), blk).group(1)) for f in FIELDS}
-        out[name]['scratch_insts'] = 0
+        out[name]['asm'] = []
     dis = subprocess.run([os.path.join(LLVM, 'llvm-objdump'), '-d', '--no-show-raw-insn', co], capture_output=True, text=True,
                          check=True).stdout
     cur = None
@@ -54,24 +57,69 @@ def kernels(co):
         m = re.match(r'^[0-9a-f]+ <(\S+)>:', line)
         if m:
             cur = m.group(1) if m.group(1) in out else None
-        elif cur and ('scratch_' in line):
-            out[cur]['scratch_insts'] += 1
+        elif cur and line.strip() not in ('', '...'):   # '...': objdump's mark for a run of zero padding behind a kernel, no instruction
+            out[cur]['asm'].append(line.split('//')[0].rstrip())
+    for d in out.values():
+        d['scratch_insts'] = sum('scratch_' in line for line in d['asm'])
     return out
+
+
+def units(objs):
+    """-> {translation unit: kernels() of its object}"""
+    with tempfile.TemporaryDirectory() as wd:
+        return {os.path.basename(o).split('.')[0]: kernels(code_object(o, wd)) for o in objs}
+
+
+def _plain(names):
+    dm = _demangle(list(names))
+    return {k: dm[k].replace('(anonymous namespace)::', '') for k in names}
+
+
+def per_unit_kernels():
+    """-> {translation unit: sorted demangled kernel names}: what each unit's code object really carries (all_kernels merges the
+    units by name and cannot see a kernel that one unit compiles for nothing)."""
+    from multiagent_rl_amd import build_native
+    return {u: sorted(_plain(ks).values()) for u, ks in units(build_native.objects()).items()}
+
+
+def compare(parent_dir):
+    """Prints the kernels that sit in other units than in the build under parent_dir and the kernels whose metadata or
+    disassembly differ; -> exit status (non-zero: a kernel differs, or one the parent had is in no unit any more)."""
+    from multiagent_rl_amd import build_native
+    old, new = units(sorted(glob.glob(os.path.join(parent_dir, '*.o')))), units(build_native.objects())
+    if not old:
+        sys.exit('no objects (*.o) in %s' % parent_dir)
+    where = lambda tree, k: sorted(u for u, ks in tree.items() if k in ks)  # noqa: E731
+    names = _plain({k for ks in list(old.values()) + list(new.values()) for k in ks})
+    differ, gone = [], []
+    for k in sorted(names, key=names.get):
+        uo, un = where(old, k), where(new, k)
+        if uo != un:
+            print('%-40s -> %-40s %s' % (' '.join(uo) or '(new)', ' '.join(un) or '(GONE)', names[k].split('(')[0]))
+        if uo and not un:
+            gone.append(k)
+        copies = [tree[u][k] for tree, us in ((old, uo), (new, un)) for u in us]
+        if uo and un and any(c != copies[0] for c in copies):
+            differ.append(k)
+            print('DIFFERS: %s' % names[k])
+    print('%d kernels in the parent, %d here; %d differ, %d gone' % (sum(bool(where(old, k)) for k in names),
+                                                                      sum(bool(where(new, k)) for k in names), len(differ), len(gone)))
+    return 1 if differ or gone else 0
 
 
 def all_kernels():
     from multiagent_rl_amd import build_native
-    objs = build_native.objects()
     res = {}
-    with tempfile.TemporaryDirectory() as wd:
-        for o in objs:
-            res.update(kernels(code_object(o, wd)))
-    names = _demangle(list(res))
-    return {names[k].replace('(anonymous namespace)::', ''): v for k, v in res.items()}
+    for ks in units(build_native.objects()).values():
+        res.update(ks)
+    names = _plain(res)
+    return {names[k]: v for k, v in res.items()}
 
 
 if __name__ == '__main__':
     sys.path.insert(0, ROOT)
+    if '--compare' in sys.argv:
+        sys.exit(compare(sys.argv[sys.argv.index('--compare') + 1]))
     ks = all_kernels()
     print('%-86s %5s %5s %6s %6s %5s %7s' % ('kernel', 'vgpr', 'vspill', 'sspill', 'priv B', 'LDS', 'scratch'))
     for n, d in sorted(ks.items()):
