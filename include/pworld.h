@@ -76,7 +76,11 @@ enum pw_error {
 typedef struct pw_handle pw_handle;
 
 /* Mirrors what make_env()/make_world() fix for one env (experiments/scenarios.py:124-192)
- * plus the World constants (upstream core.py World.__init__). */
+ * plus the World constants (upstream core.py World.__init__).
+ * simple_spread and simple_tag honour every field.  The communication scenarios (simple_reference,
+ * simple_speaker_listener) scale both agents' actions by default_sensitivity and have neither a force scale nor a
+ * speed clamp: pw_create returns PW_EINVAL when any agent_accel[i] >= 0, any agent_max_speed[i] >= 0 or
+ * action_force_uses_accel != 0 (dt, damping, mass and default_sensitivity stay free). */
 typedef struct pw_config {
     uint32_t struct_size;            /* = sizeof(pw_config); checked */
     int32_t scenario;                /* pw_scenario */

@@ -614,6 +614,19 @@ int pw_create(const pw_config *cfg, pw_handle **out)
         return fail(PW_EINVAL, "unknown scenario");
     if (is_comm_scenario(cfg->scenario) && (cfg->num_agents != 2 || cfg->num_landmarks < 1 || cfg->num_landmarks > 3))
         return fail(PW_EINVAL, "simple_reference / simple_speaker_listener are two agents and 1..3 landmarks");
+    if (is_comm_scenario(cfg->scenario)) {
+        // the communication kernels (and the oracle's po_ref_step) scale both agents' actions by default_sensitivity and know
+        // neither a force scale nor a speed clamp: a configuration that asks for one is refused, not silently ignored
+        if (cfg->action_force_uses_accel)
+            return fail(PW_EINVAL, "simple_reference / simple_speaker_listener: action_force_uses_accel must be 0");
+        for (int i = 0; i < 2; ++i) {
+            if (cfg->agent_accel[i] >= 0.0f)
+                return fail(PW_EINVAL, "simple_reference / simple_speaker_listener: agent_accel must be < 0 (None); "
+                                       "default_sensitivity scales both agents' actions");
+            if (cfg->agent_max_speed[i] >= 0.0f)
+                return fail(PW_EINVAL, "simple_reference / simple_speaker_listener: agent_max_speed must be < 0 (None)");
+        }
+    }
     if (cfg->num_envs < 1) return fail(PW_EINVAL, "num_envs must be >= 1");
     if (cfg->num_agents < 1 || cfg->num_agents > PW_MAX_AGENTS) return fail(PW_EINVAL, "num_agents out of range [1, 64]");
     if (cfg->num_landmarks < 0 || cfg->num_landmarks > PW_MAX_LANDMARKS) return fail(PW_EINVAL, "num_landmarks out of range [0, 64]");

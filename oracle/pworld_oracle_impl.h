@@ -370,6 +370,16 @@ static void SUFFIX(po_ref_reset_env)(const po_config *c, uint64_t env_id, uint32
     }
 }
 
+/* The communication worlds scale both agents' actions by default_sensitivity and have neither a force scale nor a
+ * speed clamp (as libpworld's kernels): a per-agent accel, a max_speed or the fork knob is outside their domain. */
+static int SUFFIX(po_ref_outside_domain)(const po_config *c)
+{
+    if (c->action_force_uses_accel) return 1;
+    for (int i = 0; i < 2; ++i)
+        if (c->agent_accel[i] >= 0 || c->agent_max_speed[i] >= 0) return 1;
+    return 0;
+}
+
 PO_EXPORT int SUFFIX(po_ref_step)(const po_config *c, int B, REAL *pos, REAL *vel, REAL *lm, REAL *comm,
                                   int32_t *goal, int32_t *ep_step, uint32_t *ep_count, const int32_t *act_idx,
                                   const int32_t *act_comm, const REAL *act_vec, REAL *obs, REAL *final_obs,
@@ -378,6 +388,7 @@ PO_EXPORT int SUFFIX(po_ref_step)(const po_config *c, int B, REAL *pos, REAL *ve
     const int N = c->num_agents, L = c->num_landmarks, D = po_obs_dim(c);
     const int sl = c->scenario == PO_SIMPLE_SPEAKER_LISTENER, DC = po_dim_c(c);
     if (N != 2 || L < 1 || L > 3 || DC == 0) return -1;
+    if (SUFFIX(po_ref_outside_domain)(c)) return -2;
     const REAL damp = (REAL)1 - (REAL)c->damping, dt = (REAL)c->dt, mass = (REAL)c->mass;
     for (int e = 0; e < B; ++e) {
         REAL *p = pos + (size_t)e * N * 2, *v = vel + (size_t)e * N * 2, *l = lm + (size_t)e * L * 2;
@@ -445,6 +456,7 @@ PO_EXPORT int SUFFIX(po_ref_reset)(const po_config *c, int B, REAL *pos, REAL *v
                                    int32_t *goal, int32_t *ep_step, uint32_t *ep_count, REAL *obs)
 {
     const int N = c->num_agents, L = c->num_landmarks, D = po_obs_dim(c);
+    if (N != 2 || SUFFIX(po_ref_outside_domain)(c)) return -2;
     for (int e = 0; e < B; ++e) {
         REAL *p = pos + (size_t)e * N * 2, *v = vel + (size_t)e * N * 2, *l = lm + (size_t)e * L * 2;
         REAL *cm = comm + (size_t)e * N * po_dim_c(c);

@@ -77,6 +77,54 @@ def test_handle_geometry_and_errors():
     assert lib.pw_config_default(C.byref(cfg), 7, 16, 6, -1, 0) == -1 and b'scenario' in lib.pw_last_error()
 
 
+@pytest.mark.parametrize('scenario', ['simple_reference', 'simple_speaker_listener'])
+def test_communication_scenarios_refuse_what_their_kernels_cannot_honour(scenario):
+    """The communication kernels scale both agents' actions by default_sensitivity and know neither a force scale nor a speed
+    clamp.  pw_create refuses a per-agent accel, a max_speed and the fork knob by name instead of ignoring them, and the C
+    oracle's communication entry points refuse the same configurations: library and oracle have one domain.  dt, damping, mass
+    and default_sensitivity stay free."""
+    import numpy as np
+    from oracle import c_oracle as co
+    lib = _lib.load()
+    scen = _lib.SCENARIOS[scenario]
+
+    def attempt(edit):
+        cfg = _lib.PwConfig()
+        assert lib.pw_config_default(C.byref(cfg), scen, 16, 2, -1, 0) == 0
+        ocfg = co.make_config(scenario)
+        for c in (cfg, ocfg):
+            edit(c)
+        h = C.c_void_p()
+        rc = lib.pw_create(C.byref(cfg), C.byref(h))
+        msg = lib.pw_last_error().decode() if rc else ''
+        if rc == 0:
+            lib.pw_destroy(h)
+        o = co.CRefOracle(ocfg, 4, np.float32)
+        accepted = []
+        for call in (o.reset, lambda: o.step(act_idx=np.zeros((4, 2), np.int32), act_comm=np.zeros((4, 2), np.int32))):
+            try:
+                call()
+                accepted.append(True)
+            except AssertionError:
+                accepted.append(False)
+        assert accepted in ([True, True], [False, False])
+        return rc, msg, accepted[0]
+
+    assert attempt(lambda c: None) == (0, '', True)                                   # the canonical configuration
+    for field, edit in (('agent_accel', lambda c: c.agent_accel.__setitem__(0, 3.0)),
+                        ('agent_accel', lambda c: c.agent_accel.__setitem__(1, 0.0)),
+                        ('agent_max_speed', lambda c: c.agent_max_speed.__setitem__(1, 1.3)),
+                        ('agent_max_speed', lambda c: c.agent_max_speed.__setitem__(0, 0.0)),
+                        ('action_force_uses_accel', lambda c: setattr(c, 'action_force_uses_accel', 1))):
+        rc, msg, oracle_ok = attempt(edit)
+        assert rc == -1 and field in msg and scenario in msg, (field, rc, msg)
+        assert not oracle_ok, field
+
+    def free(c):
+        c.dt, c.damping, c.mass, c.default_sensitivity = 0.07, 0.4, 3.0, 3.5
+    assert attempt(free) == (0, '', True)
+
+
 def test_actor_precision_is_a_handle_property_outside_the_dispatch(monkeypatch):
     """pw_set_actor_precision / pw_get_actor_precision: exact float32 by default, the opt-in bf16x3 mode by call ONLY (no
     environment variable may change results: PW_ACTOR_BF16X3=1 in the creating process is ignored), other values refused -- and
