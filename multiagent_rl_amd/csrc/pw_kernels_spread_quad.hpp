@@ -42,6 +42,60 @@ __device__ __forceinline__ void quad_pair_of(const int q, int &i, int &j)
     j = q - (i == 0 ? 0 : i == 1 ? 5 : i == 2 ? 9 : i == 3 ? 12 : 14) + i + 1;
 }
 
+// The physics waves' action fetch (pw_common.hpp act_fetch_issue, which the duo / tag kernels keep): the same LDS-direct load in
+// its scalar-base form -- `row` is the workgroup-uniform pointer to the step's action plane, a running pointer of the caller's,
+// `lane_off` the lane's constant byte offset in it -- so a step pays one scalar add for the address instead of a 64-bit product
+// and a vector add.  The wait for the slot's previous content is the compiler's own: `slot_read`, the value the caller has just read
+// from that slot, is an operand.  M0 is still saved and restored inside the statement: the compiler takes "m0" in a clobber list
+// only with the remark that a reserved register "may not be preserved across the asm statement".
+__device__ __forceinline__ void quad_act_fetch(const int32_t *row, const uint32_t lane_off, const uint32_t lds_slot, const uint32_t slot_read)
+{
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(lane_off), "s"(row), "s"(lds_slot), "v"(slot_read) : "memory");
+}
+
+// The pair force of a physics lane: pw_common.hpp collision_force_pair<true, K1> behind the near test, with the two tests folded
+// into ONE exec region -- fast = near & in_range runs the range-restricted expressions; a near pair out of their range (coincident
+// agents, NaN / inf, an exotic margin) is rare enough for a wave-uniform test that falls through, and takes collision_force_pair
+// itself in a cold block.  The operations and their operands are collision_force_pair's, so the bits are; only the ORDER differs:
+// the division by dist (its reciprocal, its two quotient chains) starts right behind the square root and runs beside the margin
+// division and the softplus instead of after them -- it needs nothing of theirs but the final product.
+template <bool K1>
+__device__ __forceinline__ void quad_pair_force(const float2 qi, const float2 qj, const uint32_t near_lo, const uint32_t near_span,
+                                                const float dist_min, const float k, const float cf, float &Fx, float &Fy)
+{
+    // the near test on (p_i - p_j)^2, the force's own delta, so that the two share their first operations (the other
+    // kernels test (p_j - p_i)^2: the same value -- a difference and its negation have the same square): -1.7 % step time
+    const float dx = qi.x - qj.x, dy = qi.y - qj.y;
+    const float d2 = dx * dx + dy * dy;
+    const f32x2 a = {cf * dx, cf * dy};
+    const bool near = __float_as_uint(d2) - near_lo >= near_span;  // not provably far (NaN / inf included)
+    const bool uni = (k >= 9.094947017729282e-13f) & (k <= 1099511627776.0f) & (cf >= 9.5367431640625e-07f) & (cf <= 128.0f);
+    const bool c1 = (__float_as_uint(d2) - 0x12800000u) < (0x6C800000u - 0x12800000u);
+    const bool c2 = fminf(fabsf(a.x), fabsf(a.y)) >= 8.673617379884035e-19f;
+    const bool fast = near & c1 & c2 & uni;
+    // (taken here, beside the compares, the wave's mask is theirs, combined in scalar registers)
+    const bool any_cold = __builtin_amdgcn_ballot_w64(near & !fast) != 0;
+    Fx = 0.0f; Fy = 0.0f;
+    if (fast) {
+        const float dist = sqrt_rn_core(d2);
+        const float y0 = __builtin_amdgcn_rcpf(dist);
+        __builtin_amdgcn_sched_barrier(0);  // the reciprocal is in flight before anything of the softplus chain issues
+        const float yd = __builtin_fmaf(__builtin_fmaf(-dist, y0, 1.0f), y0, y0);   // div_refined_rcp(dist)
+        const f32x2 Q = div_chain2(a, dist, yd);
+        const float xarg = K1 ? div_chain1(-(dist - dist_min), k, div_refined_rcp(k))
+                              : div_chain(-(dist - dist_min), k, div_refined_rcp(k));
+        const float pen = softplus_branchless(xarg) * k;
+        const f32x2 F = Q * f32x2{pen, pen};
+        Fx = F.x;
+        Fy = F.y;
+    }
+    if (__builtin_expect(any_cold, 0)) {
+        if (near & !fast) collision_force_pair<true, K1>(qi.x, qi.y, qj.x, qj.y, dist_min, k, cf, Fx, Fy);
+    }
+}
+
 // COLL: wave OA also stores the step's collision masks (pw_step_io.coll) -- it holds the six threshold tests anyway, so
 // the instantiation differs by one mask accumulation and one 8-byte store per lane and step; every other output is
 // bit-identical to the plain form (tests: the `quad+coll` path, and the bench-path test at C2 full size).
@@ -52,6 +106,12 @@ __device__ __forceinline__ void quad_pair_of(const int q, int &i, int &j)
 #endif
 #ifndef PW_QUAD_ACT_AHEAD
 #define PW_QUAD_ACT_AHEAD 4   // steps the physics waves' action indices are fetched ahead (a power of two; LDS ring slots per wave)
+#endif
+#ifndef PW_QUAD_PAD_P   // timing experiments only (tools/experiments/pw_experiments.hpp): padding of a wave's step loop
+#define PW_QUAD_PAD_P()
+#endif
+#ifndef PW_QUAD_PAD_OB
+#define PW_QUAD_PAD_OB()
 #endif
 constexpr int kQuadActAhead = PW_QUAD_ACT_AHEAD;
 constexpr int kQuadActRingBytes = kQuadActAhead * kWave * (int)sizeof(int32_t);  // per physics wave
@@ -157,16 +217,21 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         const uint32_t near_lo = __float_as_uint(A.near_thr2), near_span = 0x7F800000u - near_lo;
         // Action indices: fetched four steps ahead by LDS-direct loads (pw_common.hpp, act_fetch_issue: under a full chip
         // a load issued one step ahead cost 385 cycles of every step)
-        const int32_t *act_g = A.act + g;
+        const unsigned char *act_row = reinterpret_cast<const unsigned char *>(A.act);   // the action plane of the next step to fetch: workgroup-uniform, a running pointer
+        const size_t act_stride = BN * sizeof(int32_t);
+        const uint32_t act_off = g * (uint32_t)sizeof(int32_t);
         int32_t *act_ring = s_act + wave * (kQuadActAhead * kWave);
         const uint32_t act_lds = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(act_ring));
-        auto fetch_act = [&](int t) {  // indices of step t (clamped: the tail re-fetches the last step) -> slot t & 3
-            act_fetch_issue(act_g + (size_t)(t < T ? t : T - 1) * BN, act_lds + (uint32_t)(t & (kQuadActAhead - 1)) * (kWave * 4));
+        // indices of step t -> slot t & 3; called for t = 0, 1, 2, ... in turn.  The tail re-fetches the last step: the pointer's
+        // stride turns 0 there (also from the start, if T is below the fetch depth)
+        auto fetch_act = [&](int t, uint32_t slot_read) {
+            quad_act_fetch(reinterpret_cast<const int32_t *>(act_row), act_off, act_lds + (uint32_t)(t & (kQuadActAhead - 1)) * (kWave * 4), slot_read);
+            act_row += t + 1 < T ? act_stride : (size_t)0;
         };
         // every load the compiler counts is consumed before the first uncounted one is issued: a counted wait inside the
         // loop (for a value first used there) would be short by the fetches in flight, i.e. drain them
         asm volatile("" :: "v"(ep_off), "v"(ep_count), "v"(offs_all), "v"(px), "v"(py), "v"(vx), "v"(vy), "s"(t_reset));
-        for (int t0 = 0; t0 < kQuadActAhead; ++t0) fetch_act(t0);
+        for (int t0 = 0; t0 < kQuadActAhead; ++t0) fetch_act(t0, 0u);
         // the pair lanes' operands of the coming step are fetched right after the publish, before the barrier (this
         // wave only reads its own envs' entries, and a wave's LDS operations execute in issue order): the read's latency
         // hides behind the barrier
@@ -178,19 +243,12 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kQuadActAhead - 1) : "memory");  // step t's indices are in LDS (the later fetches stay in flight)
             PW_STAMP(3);
             const uint32_t ai = (uint32_t)act_ring[(t & (kQuadActAhead - 1)) * kWave + lane];
-            fetch_act(t + kQuadActAhead);  // into the slot just read (its wait for the read above is the one the table lookup needs anyway)
+            fetch_act(t + kQuadActAhead, ai);  // into the slot just read (its wait for the read above is the one the table lookup needs anyway)
             const float2 u0 = utab[ai < 5u ? ai : 5u];  // {u_x + 0, u_y + 0}: the accumulators' starting values
             const bool two_slots = t == t_reset;        // workgroup-uniform: some env of the workgroup resets in this step
             // ---- pair phase: every unordered pair of the wave's envs at once
-            float Fx = 0.0f, Fy = 0.0f;
-            {
-                // the near test on (p_i - p_j)^2, the force's own delta, so that the two share their first operations (the other
-                // kernels test (p_j - p_i)^2: the same value -- a difference and its negation have the same square): -1.7 % step time
-                const float dx = qi.x - qj.x, dy = qi.y - qj.y;
-                const float d2 = dx * dx + dy * dy;
-                if (__float_as_uint(d2) - near_lo >= near_span)  // not provably far (NaN / inf included)
-                    collision_force_pair<true, K1>(qi.x, qi.y, qj.x, qj.y, A.dist_min, k, cf, Fx, Fy);
-            }
+            float Fx, Fy;
+            quad_pair_force<K1>(qi, qj, near_lo, near_span, A.dist_min, k, cf, Fx, Fy);
             *f_ij = make_float2(Fx, Fy);
             *f_ji = make_float2(-Fx, -Fy);
             PW_STAMP(0);
@@ -211,7 +269,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             py = py + vy * dt;
             int nxt = (cur + 1) & 3;
             s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
-            if (two_slots) {  // rare (once per episode): the envs at their episode's end restart, EVERY env publishes a second slot
+            if (__builtin_expect(two_slots, 0)) {  // rare (once per episode): the envs at their episode's end restart, EVERY env publishes a second slot
                 if (t + 1 + ep_off >= A.max_episode_len) {
                     ep_count += 1;
                     ep_off = -(t + 1);
@@ -227,6 +285,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             qi = *reinterpret_cast<const float2 *>(s_ring + cur * kWave + ri);
             qj = *reinterpret_cast<const float2 *>(s_ring + cur * kWave + rj);
             PW_STAMP(1);
+            PW_QUAD_PAD_P();
             PW_QUAD_BARRIER(t);
             PW_STAMP(2);
         }
@@ -303,7 +362,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             return sqrtf(b);  // branch-free expansion: the guarded fast form (a vector compare feeding exec) measured 8 % slower on this chain
         };
         auto a_clock = [&](const int t, int nxt) __attribute__((always_inline)) {  // episode clocks; the slot A(t + 1) reads
-            if (t == t_reset) {  // workgroup-uniform, once per episode
+            if (__builtin_expect(t == t_reset, 0)) {  // workgroup-uniform, once per episode
                 if (t + 1 + ep_off >= A.max_episode_len) {
                     ep_count += 1;
                     ep_off = -(t + 1);
@@ -331,14 +390,18 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
 #pragma unroll
             for (int i = 0; i < N; ++i) sh_r[i] = __shfl(r, base + i, kWave);
         };
-        auto b_store = [&](const int tb) __attribute__((always_inline)) {
-            const size_t tBN = (size_t)tb * BN;
+        // the planes of step tb: workgroup-uniform running pointers (b_store is called for tb = 0, 1, 2, ... in turn)
+        float *rew_t = A.rew, *rsh_t = A.rew_shared;
+        uint64_t *coll_t = A.coll;
+        auto b_store = [&]() __attribute__((always_inline)) {
             float acc = 0.0f;
 #pragma unroll
             for (int i = 0; i < N; ++i) acc += sh_r[i];
-            nt_store(A.rew + tBN + g, r);
-            nt_store(A.rew_shared + (size_t)tb * A.B + env, acc);   // (done / terminal: wave OB, which has the slack)
-            if (COLL) nt_store(A.coll + tBN + g, (uint64_t)cmask_p);  // is_collision bits of the state step tb produced (pre-reset)
+            nt_store(rew_t + g, r);
+            nt_store(rsh_t + env, acc);   // (done / terminal: wave OB, which has the slack)
+            if (COLL) nt_store(coll_t + g, (uint64_t)cmask_p);  // is_collision bits of the state step tb produced (pre-reset)
+            rew_t += BN; rsh_t += A.B;
+            if (COLL) coll_t += BN;
         };
         PW_STAMP_DECL;
         // prologue: A(0)
@@ -363,14 +426,14 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             a_dist();
             b_reward();
             const float own = a_sqrt();
-            b_store(t - 1);
+            b_store();
             own_p = own; cnt_p = cnt; cmask_p = cmask;
             a_clock(t, nxt);
             PW_STAMP(1);
         }
         b_shfl_own();  // epilogue: B(T - 1)
         b_reward();
-        b_store(T - 1);
+        b_store();
 #ifdef PW_STAMPS
         if (blockIdx.x == 0 && lane == 0)
             for (int i_ = 0; i_ < 2; ++i_) g_pw_stamps[4 + i_] = st_acc[i_];
@@ -386,15 +449,23 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
     // the storing lane differs).  The rows' {pos, vel} are read STRAIGHT from the ring slot (its index is the row index),
     // and a lane's three landmark pairs live in registers for the whole episode (they change in reset steps only): a
     // step is three 16-byte LDS reads, the subtractions and three stores.
+    // A step's loop body is straight-line code (counted: profiles/r6_quad_loop_census.txt): the three ring reads go out back to
+    // back behind ONE wait, column group 0 is composed by selects (no exec-masked region), and no store carries a predicate --
+    // in the last, partial workgroup a chunk past the block re-stores chunk `column group` of row 0 instead: the lane reads
+    // row 0 and env 0's landmarks, i.e. it computes that chunk's very value, and writes it to that chunk's address (the idiom
+    // of the idle lanes' done / terminal / reward stores: a second store of the same bytes).  The output planes are walked by
+    // running workgroup-uniform pointers (one 64-bit scalar add per plane and step), the lanes' parts are constant offsets.
     const int rows_here = envs_here * N;
     const int cgrp = lane & 3;
+    const bool col0 = cgrp == 0;
     int row_u[3];
-    bool ok_u[3];
+    uint32_t off_u[3];  // byte offset of the lane's chunk u in the workgroup's block of a step
 #pragma unroll
     for (int u = 0; u < 3; ++u) {
         const int r = (lane >> 2) + 16 * u;
-        ok_u[u] = r < rows_here;
-        row_u[u] = ok_u[u] ? r : 0;  // chunks past the block read row 0 (and store nothing)
+        const bool ok = r < rows_here;
+        row_u[u] = ok ? r : 0;
+        off_u[u] = (uint32_t)(ok ? lane + 64 * u : cgrp) * 16u;
     }
     float4 lm_u[3];
     auto load_landmarks = [&]() {  // the two landmarks of this lane's column group, per row's env
@@ -405,25 +476,31 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
     s_lmB[me] = make_float2(olx, oly);
     wave_lds_sync();
     load_landmarks();
-    float4 *const blk4 = reinterpret_cast<float4 *>(A.obs + ((size_t)env0 * N) * D) + lane;
+    // workgroup-uniform plane pointers of step t (the compiler keeps them in scalar registers: every term is uniform)
+    unsigned char *obs_t = reinterpret_cast<unsigned char *>(A.obs + ((size_t)env0 * N) * D);
+    uint8_t *done_t = A.done, *term_t = A.terminal;
+    const size_t obs_stride = BN * D * sizeof(float);
+    // the terminal flag of step t is "t >= t_term": t + 1 + ep_off >= max_episode_len, solved for t (changes in reset steps only)
+    const bool has_len = A.max_episode_len > 0;
+    int t_term = has_len ? A.max_episode_len - 1 - ep_off : 0x7fffffff;
     PW_STAMP_DECL;
     for (int t = 0; t < T; ++t) {
-        const size_t tBN = (size_t)t * BN;
         PW_STAMP_START;
-        nt_store(A.done + tBN + g, (uint8_t)0);
+        nt_store(done_t + g, (uint8_t)0);
         PW_QUAD_BARRIER(t);
         PW_STAMP(0);
         int nxt = (cur + 1) & 3;
-        nt_store(A.terminal + (size_t)t * A.B + env, (uint8_t)(A.max_episode_len > 0 && t + 1 + ep_off >= A.max_episode_len ? 1 : 0));
+        nt_store(term_t + env, (uint8_t)(t >= t_term ? 1 : 0));
         if (t == t_reset) {  // workgroup-uniform, once per episode
-            const bool rst = t + 1 + ep_off >= A.max_episode_len;
+            const bool rst = t >= t_term;
             if (rst) {
                 if (A.final_obs) {
                     const float4 st = s_ring[nxt * kWave + me];  // this lane's own (env, agent) row, pre-reset
-                    stream_write_obs<L>(A.final_obs + (tBN + g) * D, L, s_lmB + base, st.x, st.y, st.z, st.w);
+                    stream_write_obs<L>(A.final_obs + ((size_t)t * BN + g) * D, L, s_lmB + base, st.x, st.y, st.z, st.w);
                 }
                 ep_count += 1;
                 ep_off = -(t + 1);
+                t_term = A.max_episode_len - 1 - ep_off;
                 pw_reset_xy(A.seed, env_id, ep_count, (uint32_t)(N + a), -1.0f, 1.0f, &olx, &oly);
             }
             reset_step_update(t);
@@ -435,14 +512,21 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         }
         cur = nxt;
         const float4 *slot = s_ring + nxt * kWave;
-        float4 *const out4 = blk4 + tBN * (D / 4);
+        float4 st[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) st[u] = slot[row_u[u]];
+        // anchor: the rows arrive whole behind one wait (otherwise the compiler splits row 0's read between the two sides of an
+        // exec-masked region it makes of the selects)
+        asm volatile("" :: "v"(st[0].x), "v"(st[0].y), "v"(st[0].z), "v"(st[0].w), "v"(st[1].x), "v"(st[1].y), "v"(st[1].z),
+                           "v"(st[1].w), "v"(st[2].x), "v"(st[2].y), "v"(st[2].z), "v"(st[2].w));
 #pragma unroll
         for (int u = 0; u < 3; ++u) {
-            const float4 st = slot[row_u[u]];
-            const float4 o = cgrp == 0 ? make_float4(st.z, st.w, st.x, st.y)
-                                       : make_float4(lm_u[u].x - st.x, lm_u[u].y - st.y, lm_u[u].z - st.x, lm_u[u].w - st.y);
-            if (ok_u[u]) nt_store(out4 + 64 * u, o);
+            const float4 d = make_float4(lm_u[u].x - st[u].x, lm_u[u].y - st[u].y, lm_u[u].z - st[u].x, lm_u[u].w - st[u].y);
+            const float4 o = make_float4(col0 ? st[u].z : d.x, col0 ? st[u].w : d.y, col0 ? st[u].x : d.z, col0 ? st[u].y : d.w);
+            nt_store(reinterpret_cast<float4 *>(obs_t + off_u[u]), o);
         }
+        obs_t += obs_stride; done_t += BN; term_t += A.B;
+        PW_QUAD_PAD_OB();
         PW_STAMP(1);
     }
 #ifdef PW_STAMPS

@@ -10,6 +10,9 @@
 //   PW_EXP_NO_FORCE       near_force_loop sees an empty near mask: a step without any contact force
 //   PW_EXP_ONE_PARTNER    ... with at most ONE evaluation per lane (the bound of a pair-parallel form's gain)
 //   PW_EXP_BARRIER2 / 0   the quad kernel's workgroup meets every SECOND step only / never
+//   PW_EXP_PAD_OB=<n>     n x `s_nop 0` in the step loop of the quad kernel's wave OB (the results stay right; an experiment build all the
+//   PW_EXP_PAD_P=<n>      same) / of its physics waves: does a step pay for every instruction a SIMD issues, or only for the physics
+//                         wave's dependent chain?  (profiles/r6_quad_issue_budget.txt)
 //   (PW_QUAD_ACT_AHEAD=8|16 is a plain parameter of pw_kernels_spread_quad.hpp, not an experiment: results stay exact)
 #pragma once
 #ifndef PW_EXPERIMENTS
@@ -45,4 +48,13 @@ __device__ __forceinline__ void nt_store(float2 *p, const float2 v) { asm volati
 #define PW_QUAD_BARRIER(t) do { if (!((t) & 1)) duo_barrier(); else wave_lds_sync(); } while (0)
 #elif defined(PW_EXP_BARRIER0)
 #define PW_QUAD_BARRIER(t) wave_lds_sync()
+#endif
+
+#define PW_EXP_STR_(x) #x
+#define PW_EXP_STR(x) PW_EXP_STR_(x)
+#if defined(PW_EXP_PAD_OB) && PW_EXP_PAD_OB > 0
+#define PW_QUAD_PAD_OB() asm volatile(".rept " PW_EXP_STR(PW_EXP_PAD_OB) "\n\ts_nop 0\n\t.endr")
+#endif
+#if defined(PW_EXP_PAD_P) && PW_EXP_PAD_P > 0
+#define PW_QUAD_PAD_P() asm volatile(".rept " PW_EXP_STR(PW_EXP_PAD_P) "\n\ts_nop 0\n\t.endr")
 #endif
