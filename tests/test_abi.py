@@ -224,29 +224,55 @@ def test_product_never_imports_the_oracle():
     assert seen >= 8
 
 
+def _build_c_host(out):
+    """examples/c_host.c compiled warning-free as C11 and linked against libpworld.so -> ``out`` (skips without gcc / ROCm headers)."""
+    import shutil
+    import subprocess
+    if shutil.which('gcc') is None or not os.path.isdir('/opt/rocm/include'):
+        pytest.skip('needs gcc and the ROCm headers')
+    assert os.path.exists(_lib.LIB_PATH)
+    cmd = ['gcc', '-std=c11', '-Wall', '-Wextra', '-Werror', '-D__HIP_PLATFORM_AMD__', '-I', os.path.join(ROOT, 'include'),
+           '-I', '/opt/rocm/include', os.path.join(ROOT, 'examples', 'c_host.c'), '-L', os.path.dirname(_lib.LIB_PATH),
+           '-lpworld', '-L', '/opt/rocm/lib', '-lamdhip64', '-o', out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return out
+
+
 def test_header_is_plain_c_and_the_c_host_example_links(tmp_path):
     """include/pworld.h must be consumable by a C compiler (it is the FFI surface), and examples/c_host.c -- a
     caller with no Python and no PyTorch -- must compile warning-free as C11 and link against libpworld.so.
     (Run on a GPU box: ./examples/c_host.bin > out.txt && python tools/check_c_host.py out.txt -- the checker
     compares every printed value with the CPU oracle, bit for bit.)"""
-    import shutil
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    if shutil.which('gcc') is None or not os.path.isdir('/opt/rocm/include'):
-        pytest.skip('needs gcc and the ROCm headers')
-    from multiagent_rl_amd import _lib
-    assert os.path.exists(_lib.LIB_PATH)
-    out = str(tmp_path / 'c_host')
-    cmd = ['gcc', '-std=c11', '-Wall', '-Wextra', '-Werror', '-D__HIP_PLATFORM_AMD__', '-I', os.path.join(root, 'include'),
-           '-I', '/opt/rocm/include', os.path.join(root, 'examples', 'c_host.c'), '-L', os.path.dirname(_lib.LIB_PATH),
-           '-lpworld', '-L', '/opt/rocm/lib', '-lamdhip64', '-o', out]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    _build_c_host(str(tmp_path / 'c_host'))
     hdr = str(tmp_path / 'only_header.c')
     open(hdr, 'w').write('#include "pworld.h"\n#include "pworld_math.h"\nint main(void) { return pw_exp(0.0f) == 1.0f ? 0 : 1; }\n')
     r = subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(root, 'include'),
                         '-c', hdr, '-o', str(tmp_path / 'h.o')], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
+
+
+@pytest.mark.gpu
+def test_c_host_example_runs_and_matches_the_oracle_bitwise(tmp_path):
+    """The plain-C caller of the ABI (no Python, no PyTorch in the process) built as above and RUN once, as a fresh child
+    process under its own time limit: every value it prints -- observations, rewards, shared rewards of the last of 30 steps across
+    an auto-reset, its own bitwise check of the state-only wire block -> STATE ring -> pw_replay_gather path -- against the float32
+    oracle through tools/check_c_host.py.  A non-zero exit status fails with the child's stderr; nothing is retried."""
+    import importlib.util
+    import subprocess
+    exe = _build_c_host(str(tmp_path / 'c_host'))
+    env = dict(os.environ)
+    env['LD_LIBRARY_PATH'] = os.pathsep.join([os.path.dirname(_lib.LIB_PATH)] + [p for p in (env.get('LD_LIBRARY_PATH'),) if p])
+    out = tmp_path / 'c_host.txt'
+    with open(out, 'w') as f:
+        r = subprocess.run([exe], stdout=f, stderr=subprocess.PIPE, text=True, env=env, timeout=120)
+    assert r.returncode == 0, 'c_host exited with %d: %s' % (r.returncode, r.stderr)
+    spec = importlib.util.spec_from_file_location('check_c_host', os.path.join(ROOT, 'tools', 'check_c_host.py'))
+    checker = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(checker)
+    assert checker.main(str(out)).startswith('c_host ok')
 
 
 def test_integration_doc_stub_matches_the_abi_structs():

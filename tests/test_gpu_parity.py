@@ -182,7 +182,9 @@ def test_single_step_from_injected_states(case, kernel_path):
     _assert_same_bits(_np(info['rew_shared']), want_shared, 'rew_shared')
     # float64 reference semantics: float32 STATE within 1e-5 (north_star tolerance) -- positions, velocities and the
     # observation rows built from them, even in the crowded half of the batch (measured maxima per configuration:
-    # profiles/r2_parity_error.txt, <= 4.5e-6 at N = 48 under this stress, <= 2.3e-6 along real episodes)
+    # profiles/r2_parity_error.txt, <= 4.5e-6 at N = 48 under this stress, <= 2.3e-6 for single steps taken from the states of
+    # real episodes -- a per-step figure: FREE-RUNNING trajectories leave 1e-5 within an episode from N = 6 upwards,
+    # tests/test_gpu_trajectory.py and profiles/trajectory_drift.txt)
     o64 = co.COracle(cfg, B, np.float64)
     o64.set_state(pos, vel, lm)
     w64 = o64.step(act_idx=act)
