@@ -22,6 +22,35 @@ namespace {
 
 constexpr int kWave = 64;
 
+// ---- LDS layouts ----------------------------------------------------------------------------------------------------
+// Every kernel that takes dynamic LDS has ONE __host__ __device__ layout function beside it: a struct with a typed pointer to every
+// region and the total `bytes`, from the shape.  The kernel passes smem_raw; the host passes no base and takes `bytes` (launch size,
+// "how many environments fit"); tests/test_lds_layout.py passes a buffer and checks alignment, overlap and extent of every shape.
+// No pointer <-> integer casts (the LDS address space is kept); indices signed, in 4-byte words.  take(): align, take, advance; an
+// alignment is named only where the carve-up the function replaced padded.  `pad`: words of padding, so 4 * (at - pad) is the sum
+// of the regions, to which a layout whose launch has always reserved more adds its trailing slack.
+struct LdsCursor {
+    float *base;
+    bool chain = true;     // a region starts where the one before ends (typed increment from `end`), else base + index: whichever the
+    int at = 0, pad = 0;   // replaced carve-up did -- a kernel's whole schedule follows from these few instructions (profiles/lds_layout_codegen.txt);
+    float *end = base;     // a region with a named alignment is always base + index
+    // continues behind a block laid out by another function (its bytes, the end of its last region)
+    __host__ __device__ static LdsCursor after(unsigned char *raw, uint32_t bytes, float *end) { return {reinterpret_cast<float *>(raw), true, (int)bytes / 4, 0, end}; }
+    template <typename T>
+    __host__ __device__ T *take(int count, int align = 4)   // `count` elements of T
+    {
+        const int o = (at + align / 4 - 1) & ~(align / 4 - 1);
+        pad += o - at;
+        at = o + (sizeof(T) >= 4 ? count * (int)(sizeof(T) / 4) : count * (int)sizeof(T) / 4);
+#ifndef __HIP_DEVICE_COMPILE__
+        if (!base) return nullptr;
+#endif
+        T *r = reinterpret_cast<T *>(chain && align == 4 ? end : base + o);
+        end = reinterpret_cast<float *>(r + count);
+        return r;
+    }
+};
+
 // Every workgroup is ONE wave, and a wave's LDS instructions execute in issue order, so the
 // only thing a write -> cross-lane read hand-off through LDS needs is (a) that the compiler
 // keeps the program order of the accesses and (b) that the data has landed before it is
@@ -173,7 +202,6 @@ __device__ __forceinline__ void act_fetch_issue(const int32_t *src_lane, const u
 }
 __device__ __forceinline__ void act_fetch_wait3() { asm volatile("s_waitcnt vmcnt(3)" ::: "memory"); }
 __device__ __forceinline__ void act_fetch_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-constexpr int kActRingBytes = 4 * kWave * (int)sizeof(int32_t);  // per physics wave
 
 // The uniform of the Gumbel noise from one Philox word: (top 24 bits + 1/2) * 2^-24, strictly inside (0, 1).  The top word
 // (w >> 8 == 2^24 - 1) forms 16777215.5f, which rounds half-to-even to 2^24, i.e. u == 1.0 and log(-log u) == -inf (that logit
@@ -417,24 +445,14 @@ __device__ __forceinline__ void reset_lane(const KParams &P, const Lane &ln, uin
     }
 }
 
-// LDS carve-up of one (single-wave) workgroup
-struct Smem {
-    float2 *pos, *vel, *lm;
-    float *red;
-};
-__device__ __forceinline__ Smem carve(const KParams &P, unsigned char *raw)
+// LDS of one (single-wave) workgroup: pw_rollout_kernel, pw_spread_fast_kernel, pw_aux_kernel
+struct Smem { float2 *pos, *vel, *lm; float *red; uint32_t bytes; };
+__host__ __device__ inline Smem smem_lds(int epw, int N, int L, unsigned char *raw = nullptr)
 {
-    Smem s;
-    const int nl = P.epw * P.N, ll = P.epw * P.L;
-    s.pos = reinterpret_cast<float2 *>(raw);
-    s.vel = s.pos + nl;
-    s.lm = s.vel + nl;
-    s.red = reinterpret_cast<float *>(s.lm + ll);
-    return s;
-}
-size_t smem_bytes(const KParams &P)
-{
-    return (size_t)P.epw * (2 * P.N + P.L) * sizeof(float2) + (size_t)P.epw * P.L * sizeof(float);
+    LdsCursor c{reinterpret_cast<float *>(raw)}; Smem s;
+    s.pos = c.take<float2>(epw * N); s.vel = c.take<float2>(epw * N);
+    s.lm = c.take<float2>(epw * L); s.red = c.take<float>(epw * L);
+    s.bytes = 4 * c.at; return s;
 }
 
 }  // namespace

@@ -135,8 +135,8 @@ __device__ __forceinline__ void actor16_inproj(const float4 *s_xf, const int ts,
         for (int i = 0; i < 4; ++i) acc[T][i] += bias[T][i];
 }
 
-// LDS of the pass (floats from a 16-byte aligned base): dense1 output and head input in B-fragment order, the h exchange,
-// the dense1 constants
+// LDS of the pass: dense1 output and head input in B-fragment order, the h exchange, the dense1 constants.  The rollouts that
+// are built around the pass (pw_kernels_policy_tag.hpp, pw_kernels_policy_ref.hpp) continue their own layout from `bytes`.
 struct Actor16Lds {
     float4 *s_xf;  // [N timesteps][4 j][64 lane]: element e of (j, lane (n, kq)) = x1[row (ts, n)][x1_kpos(16 j + 4 e + kq)]
     float4 *s_hx;  // [2 buffers][2 dir][2 j][64 lane]: element e = h[seq n][16 j + 4 e + kq]
@@ -144,22 +144,16 @@ struct Actor16Lds {
     float *f_w1;   // [2 m][S1][64 lane]
     float *s_b1;   // [64]
     float *end;
+    uint32_t bytes;
 };
-__host__ __device__ inline size_t actor16_lds_floats(int N, int rows, int S1)
+__host__ __device__ inline Actor16Lds actor16_lds(int N, int rows, int S1, unsigned char *raw = nullptr)
 {
-    return (size_t)N * 1024 + 2048 + (size_t)((rows + 15) / 16) * 1024 + (size_t)2 * S1 * 64 + 64;
-}
-__device__ __forceinline__ Actor16Lds actor16_carve(float *base, int N, int rows, int S1)
-{
-    Actor16Lds S;
-    int o = 0;
-    S.s_xf = reinterpret_cast<float4 *>(base + o); o += N * 1024;
-    S.s_hx = reinterpret_cast<float4 *>(base + o); o += 2048;
-    S.s_hf = reinterpret_cast<float4 *>(base + o); o += ((rows + 15) / 16) * 1024;
-    S.f_w1 = base + o; o += 2 * S1 * 64;
-    S.s_b1 = base + o; o += 64;
-    S.end = base + o;
-    return S;
+    LdsCursor c{reinterpret_cast<float *>(raw), false}; Actor16Lds S;
+    S.s_xf = c.take<float4>(N * 4 * 64); S.s_hx = c.take<float4>(2 * 2 * 2 * 64);
+    S.s_hf = c.take<float4>(((rows + 15) / 16) * 4 * 64);
+    S.f_w1 = c.take<float>(2 * S1 * 64); S.s_b1 = c.take<float>(64);
+    S.end = c.take<float>(0);
+    S.bytes = 4 * c.at; return S;
 }
 
 // A wave's resident weights (wave = (direction wave / 4, hidden quarter wave % 4) of a 512-thread workgroup).  MFMA 16x16x4
@@ -250,7 +244,7 @@ struct Actor16NoHook {
 // per (row, block); called by `nthr` threads with indices t0 = 0 .. nthr - 1.  A rollout kernel runs it for step t + 1 on the waves
 // that wait while the environment waves advance step t: ten Philox rounds and two logarithms per logit leave the head's dependent
 // chain (stamps, simple_reference: 3.8 k of a step's 16 k cycles sat there).
-__host__ __device__ inline int actor16_noise_floats(int rows, int out) { return rows * 4 * ((out + 3) >> 2) + 4; }   // + alignment slack
+__host__ __device__ constexpr int actor16_noise_blocks(int rows, int out) { return rows * ((out + 3) >> 2); }   // float4 each
 __device__ __forceinline__ void actor16_draw_noise(const ActorFusedArgs &A, float *s_noise, const int rows_here, const long row_base,
                                                    const uint64_t step, const int t0, const int nthr)
 {
@@ -505,7 +499,7 @@ __global__ void __launch_bounds__(512) pw_actor_fused16_kernel(const ActorFusedA
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int N = A.N, E = A.E;
-    const Actor16Lds S = actor16_carve(reinterpret_cast<float *>(smem_raw), N, E * N, 4 * S1C);
+    const Actor16Lds S = actor16_lds(N, E * N, 4 * S1C, smem_raw);
     const long env0 = (long)blockIdx.x * E;
     const int envs_here = (int)((long)A.B - env0 < (long)E ? (long)A.B - env0 : (long)E);
     const long row_base = env0 * N;

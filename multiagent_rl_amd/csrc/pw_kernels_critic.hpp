@@ -23,6 +23,7 @@
 // run 8 rows per workgroup (columns 8 .. 15 of the tiles idle; 140.5 KiB at N = 64).  Nothing between the input rows and q touches HBM.
 #pragma once
 
+#include "pw_common.hpp"
 #include "pw_lstm_math.hpp"
 
 namespace {
@@ -41,9 +42,14 @@ struct CriticArgs {
     float gamma;
 };
 
-__host__ __device__ inline size_t critic_lds_bytes(int N, int R)
+struct CriticLds { float4 *s_out, *s_x; float *s_sc, *s_red; uint32_t bytes; };
+__host__ __device__ inline CriticLds critic_lds(int N, int R, unsigned char *raw = nullptr)
 {
-    return (size_t)N * 4 * 4 * R * 16 + (size_t)4 * 4 * 4 * R * 16 + (size_t)N * 16 * 4 + 8 * 16 * 4;
+    LdsCursor c{reinterpret_cast<float *>(raw)}; CriticLds o;
+    // [N][4 j][FR = 4 R]: element e of slot (kq, n) = h_t[unit 16 j + 4 e + kq][row n]; [4 buffers][4 j][FR]: the same order for x1 = relu(dense1)
+    o.s_out = c.take<float4>(N * 4 * 4 * R); o.s_x = c.take<float4>(4 * 4 * 4 * R);
+    o.s_sc = c.take<float>(N * 16); o.s_red = c.take<float>(8 * 16);   // [N][16] attention scores, [8 waves][16] dense2 partial sums
+    o.bytes = 4 * c.at; return o;
 }
 
 // KO / KA: k steps of dense1 (four k each) the instantiation holds for the observation and the action part: ceil(D / 4) <= KO,
@@ -58,10 +64,7 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hq = wave & 3, grp = wave >> 2;
     const int N = C.N, D = C.D, A = C.A, K = D + A, R = C.R, FR = 4 * R;
-    float4 *s_out = reinterpret_cast<float4 *>(critic_smem);  // [N][4 j][FR]: element e of slot (kq, n) = h_t[unit 16 j + 4 e + kq][row n]
-    float4 *s_x = s_out + (size_t)N * 4 * FR;                 // [4 buffers][4 j][FR]: the same order for x1 = relu(dense1)
-    float *s_sc = reinterpret_cast<float *>(s_x + 16 * FR);   // [N][16] attention scores
-    float *s_red = s_sc + N * 16;                             // [8 waves][16] dense2 partial sums
+    const CriticLds Y = critic_lds(N, R, critic_smem);
     const long b0 = (long)blockIdx.x * R;
     const int rows_here = (int)(C.b - b0 < (long)R ? C.b - b0 : (long)R);
     const bool col_ok = n16 < rows_here;  // columns past the rows of this workgroup compute on row b0 and store nothing
@@ -123,14 +126,14 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
 #pragma unroll
         for (int sx = 0; sx < KS; ++sx) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[sx], xb[sx], acc1, 0, 0, 0);
         if (n16 < R) {
-            float *dst = reinterpret_cast<float *>(s_x + ((ts & 3) * 4 + hq) * FR) + kq;
+            float *dst = reinterpret_cast<float *>(Y.s_x + ((ts & 3) * 4 + hq) * FR) + kq;
 #pragma unroll
             for (int i = 0; i < 4; ++i) dst[(i * R + n16) * 4] = fmaxf(acc1[i] + b1v[i], 0.0f);
         }
     };
     // bias + W_ih x1(ts) for the wave's two tiles
     auto inproj = [&](const int ts, f32x4 (&acc)[2]) {
-        const float4 *xf = s_x + ((ts & 3) * 4) * FR + slot;
+        const float4 *xf = Y.s_x + ((ts & 3) * 4) * FR + slot;
         const float4 xq[4] = {xf[0], xf[FR], xf[2 * FR], xf[3 * FR]};
 #pragma unroll
         for (int T = 0; T < 2; ++T) acc[T] = f32x4{bias[T][0], bias[T][1], bias[T][2], bias[T][3]};
@@ -168,7 +171,7 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
         float xb[KS];
         if (d1_now) load_x(ts2, xb);
         if (t > 0) {
-            const float4 *hx = s_out + ((t - 1) * 4) * FR + slot;
+            const float4 *hx = Y.s_out + ((t - 1) * 4) * FR + slot;
             const float4 hv[4] = {hx[0], hx[FR], hx[2 * FR], hx[3 * FR]};
 #pragma unroll
             for (int jx = 0; jx < 4; ++jx) {
@@ -189,7 +192,7 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
         lstm_cell(acc[1][0], acc[1][1], acc[1][2], acc[1][3], c1, h1v);
         // unit 8 wave + 4 T + kq is k quarter kq of k step 2 wave + T: fragment wave / 2, elements 2 (wave % 2) + T of this lane's slot
         if (n16 < R)
-            reinterpret_cast<float2 *>(s_out + (t * 4 + (wave >> 1)) * FR + kq * R + n16)[wave & 1] = make_float2(h0v, h1v);
+            reinterpret_cast<float2 *>(Y.s_out + (t * 4 + (wave >> 1)) * FR + kq * R + n16)[wave & 1] = make_float2(h0v, h1v);
         if (d1_now) dense1(ts2, xb);
         if (t + 1 < N) inproj(t + 1, accn);  // before the barrier: work for the matrix pipe while the workgroup meets
         wg_lds_barrier();                    // h_t of every unit is in LDS
@@ -198,10 +201,10 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
 
     // ---- attention scores <h_t, h_N>: one timestep per wave and round, a lane sums its 16 units, the four k quarters meet
     {
-        const float4 *hn = s_out + ((N - 1) * 4) * FR + slot;
+        const float4 *hn = Y.s_out + ((N - 1) * 4) * FR + slot;
         const float4 hN[4] = {hn[0], hn[FR], hn[2 * FR], hn[3 * FR]};
         for (int t = wave; t < N; t += 8) {
-            const float4 *o = s_out + (t * 4) * FR + slot;
+            const float4 *o = Y.s_out + (t * 4) * FR + slot;
             float p = 0.0f;
 #pragma unroll
             for (int jx = 0; jx < 4; ++jx) {
@@ -213,37 +216,37 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
             }
             p += lane_xor16(p);
             p += lane_xor32(p);
-            if (kq == 0) s_sc[t * 16 + n16] = p;
+            if (kq == 0) Y.s_sc[t * 16 + n16] = p;
         }
     }
     wg_lds_barrier();
 
     // ---- softmax over the agents (maximum subtracted), every wave for itself: a lane scans t = kq, kq + 4, ..
     float mx = -INFINITY;
-    for (int t = kq; t < N; t += 4) mx = fmaxf(mx, s_sc[t * 16 + n16]);
+    for (int t = kq; t < N; t += 4) mx = fmaxf(mx, Y.s_sc[t * 16 + n16]);
     mx = fmaxf(mx, lane_xor16(mx));
     mx = fmaxf(mx, lane_xor32(mx));
     float den = 0.0f;
-    for (int t = kq; t < N; t += 4) den += expf(s_sc[t * 16 + n16] - mx);
+    for (int t = kq; t < N; t += 4) den += expf(Y.s_sc[t * 16 + n16] - mx);
     den += lane_xor16(den);
     den += lane_xor32(den);
     // ---- context of this lane's two units, ReLU, dense2
     float ctx0 = 0.0f, ctx1 = 0.0f;
     for (int t = 0; t < N; ++t) {
-        const float w = expf(s_sc[t * 16 + n16] - mx) / den;
-        const float2 o = reinterpret_cast<const float2 *>(s_out + (t * 4 + (wave >> 1)) * FR + slot)[wave & 1];
+        const float w = expf(Y.s_sc[t * 16 + n16] - mx) / den;
+        const float2 o = reinterpret_cast<const float2 *>(Y.s_out + (t * 4 + (wave >> 1)) * FR + slot)[wave & 1];
         ctx0 += w * o.x;
         ctx1 += w * o.y;
     }
     float part = C.w2[8 * wave + kq] * fmaxf(ctx0, 0.0f) + C.w2[8 * wave + 4 + kq] * fmaxf(ctx1, 0.0f);
     part += lane_xor16(part);
     part += lane_xor32(part);
-    if (kq == 0) s_red[wave * 16 + n16] = part;
+    if (kq == 0) Y.s_red[wave * 16 + n16] = part;
     wg_lds_barrier();
     if (tid < 16 && col_ok) {
-        float qv = s_red[tid];
+        float qv = Y.s_red[tid];
 #pragma unroll
-        for (int w = 1; w < 8; ++w) qv += s_red[w * 16 + tid];
+        for (int w = 1; w < 8; ++w) qv += Y.s_red[w * 16 + tid];
         qv += C.b2[0];
         C.q[b0 + tid] = qv;
         if (C.y) {  // r + GAMMA * q_next * (1. - d), left to right, no contraction (the unit is compiled with -ffp-contract=off)

@@ -13,7 +13,7 @@ template <int SCEN, int OBS>
 __global__ void __launch_bounds__(kWave) pw_rollout_kernel(const KParams P, const pw_step_io io, const int T)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const Smem S = carve(P, smem_raw);
+    const Smem S = smem_lds(P.epw, P.N, P.L, smem_raw);
     const Lane ln = make_lane(P);
     const int N = P.N, L = P.L, D = P.D;
     const size_t BN = (size_t)P.B * N;
@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(kWave) pw_aux_kernel(const KParams P, const in
                                                        float *obs, float *rew, uint64_t *coll)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const Smem S = carve(P, smem_raw);
+    const Smem S = smem_lds(P.epw, P.N, P.L, smem_raw);
     const Lane ln = make_lane(P);
     const int N = P.N, L = P.L;
     float px = 0.f, py = 0.f, vx = 0.f, vy = 0.f, my_size = 0.f;

@@ -197,28 +197,34 @@ __global__ void pw_actor_front_pack_kernel(const float *__restrict__ w1, const f
     }
 }
 
+struct ActorFrontLds { float4 *f_wih; float *f_w1, *s_b1, *s_bih, *s_t; uint32_t bytes; };
+__host__ __device__ inline ActorFrontLds actor_front_lds(int S1, unsigned char *raw = nullptr)   // S1: stage-1 k-steps (K = 2 each), zero padded
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; ActorFrontLds o;
+    o.f_wih = c.take<float4>(8 * 2 * 4 * 64);   // [8 n][2 m][4 rq][64 lane] float4 (e = reg & 3)
+    o.f_w1 = c.take<float>(2 * S1 * 64);        // [2 m][S1][64 lane]; filled as float4 right behind f_wih
+    o.s_b1 = c.take<float>(64); o.s_bih = c.take<float>(256); o.s_t = c.take<float>(4 * 32 * 33);   // [64], [256], [4 waves][32][33] transpose patches
+    o.bytes = 4 * c.at; return o;
+}
+
 template <int S1C>
 __global__ void __launch_bounds__(256) pw_actor_front_kernel(const float *__restrict__ X, const float *__restrict__ frag,
                                                              const float *__restrict__ b1, const float *__restrict__ bih,
                                                              const long rows, const int D, float *__restrict__ G)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    constexpr int S1 = 4 * S1C;                                      // stage-1 k-steps (K = 2 each), zero padded
-    float4 *f_wih = reinterpret_cast<float4 *>(smem_raw);            // [8 n][2 m][4 rq][64 lane] float4 (e = reg & 3)
-    float *f_w1 = reinterpret_cast<float *>(f_wih + 8 * 2 * 4 * 64);  // [2 m][S1][64 lane]
-    float *s_b1 = f_w1 + 2 * S1 * 64;                                // [64]
-    float *s_bih = s_b1 + 64;                                        // [256]
-    float *s_t = s_bih + 256;                                        // [4 waves][32][33] transpose patches
+    constexpr int S1 = 4 * S1C;
+    const ActorFrontLds Y = actor_front_lds(S1, smem_raw);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, col = lane & 31;
     // ---- weight fragments -> LDS (once per workgroup): a linear, fully coalesced copy of the packed image
     {
         const float4 *src = reinterpret_cast<const float4 *>(frag);
-        const int n4 = 8 * 2 * 4 * 64 + (2 * S1 * 64) / 4;  // f_w1 follows f_wih contiguously, (2*S1*64) % 4 == 0
-        for (int f = tid; f < n4; f += 256) f_wih[f] = src[f];
+        const int n4 = 8 * 2 * 4 * 64 + (2 * S1 * 64) / 4;  // Y.f_w1 follows Y.f_wih contiguously, (2*S1*64) % 4 == 0
+        for (int f = tid; f < n4; f += 256) Y.f_wih[f] = src[f];
     }
-    if (tid < 64) s_b1[tid] = b1[tid];
-    s_bih[tid] = bih[tid];
+    if (tid < 64) Y.s_b1[tid] = b1[tid];
+    Y.s_bih[tid] = bih[tid];
     __syncthreads();
 
     const long row0 = ((long)blockIdx.x * 4 + wave) * 32;
@@ -243,15 +249,15 @@ __global__ void __launch_bounds__(256) pw_actor_front_kernel(const float *__rest
     for (int sidx = 0; sidx < S1; ++sidx) {
 #pragma unroll
         for (int m = 0; m < 2; ++m)
-            acc1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(f_w1[(m * S1 + sidx) * 64 + lane], xb[sidx], acc1[m], 0, 0, 0);
+            acc1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(Y.f_w1[(m * S1 + sidx) * 64 + lane], xb[sidx], acc1[m], 0, 0, 0);
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc1[m][r] = fmaxf(acc1[m][r] + s_b1[m * 32 + mfma_row(r, half)], 0.0f);
+        for (int r = 0; r < 16; ++r) acc1[m][r] = fmaxf(acc1[m][r] + Y.s_b1[m * 32 + mfma_row(r, half)], 0.0f);
 
     // ---- stage 2: eight 32x32 tiles of G^T, one at a time (acc1 stays resident as the B operands)
-    float *patch = s_t + wave * 32 * 33;
+    float *patch = Y.s_t + wave * 32 * 33;
 #pragma unroll 1
     for (int n = 0; n < 8; ++n) {
         f32x16 acc;
@@ -261,7 +267,7 @@ __global__ void __launch_bounds__(256) pw_actor_front_kernel(const float *__rest
         for (int m = 0; m < 2; ++m) {
 #pragma unroll
             for (int rq = 0; rq < 4; ++rq) {
-                const float4 a = f_wih[((n * 2 + m) * 4 + rq) * 64 + lane];
+                const float4 a = Y.f_wih[((n * 2 + m) * 4 + rq) * 64 + lane];
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, acc1[m][4 * rq + 0], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, acc1[m][4 * rq + 1], acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, acc1[m][4 * rq + 2], acc, 0, 0, 0);
@@ -281,7 +287,7 @@ __global__ void __launch_bounds__(256) pw_actor_front_kernel(const float *__rest
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float *src = patch + rr * 33 + u0 + 4 * q;
-                    const float *bb = s_bih + n * 32 + u0 + 4 * q;
+                    const float *bb = Y.s_bih + n * 32 + u0 + 4 * q;
                     dst[q] = make_float4(src[0] + bb[0], src[1] + bb[1], src[2] + bb[2], src[3] + bb[3]);
                 }
             }
@@ -368,7 +374,7 @@ struct ActorFusedArgs {
 };
 constexpr int kFusedRows = 96, kGs = 129, kHs = 68;  // kHs: 16-byte aligned rows for the head's float4 reads
 
-// LDS of one actor workgroup (carved from dynamic shared memory; kActorLdsFloats(S1) floats in total)
+// LDS of one actor workgroup
 struct ActorLds {
     float4 *f_wih;  // [4 n][2 m][4 rq][64 lane] float4, one direction
     float4 *s_whh;  // [4 gate][8 q][32 unit] float4, one direction
@@ -378,30 +384,18 @@ struct ActorLds {
     float *s_b1, *s_bih;  // [64], [256]
     float *s_w2, *s_b2;   // [16][64] (n_out0 + n_out1 rows used), [16]
     float *s_hx;    // [16 sequences][32]
-    float *s_lg;    // [96 * 16] perturbed logits -- aliases s_g, which is dead once the last recurrence has finished
-    unsigned char *end;
+    float *s_lg;    // [96 * 16] perturbed logits -- alias of s_g, which is dead once the last recurrence has finished
+    uint32_t bytes;
 };
-__host__ __device__ constexpr size_t actor_lds_bytes(int S1)
+__host__ __device__ inline ActorLds actor_lds(int S1, unsigned char *raw = nullptr)
 {
-    return (size_t)(4 * 2 * 4 * 64 + 4 * 8 * 32) * 16 +
-           (size_t)(2 * S1 * 64 + kFusedRows * kGs + kFusedRows * kHs + 64 + 256 + 1024 + 16 + 512) * 4;
-}
-__device__ __forceinline__ ActorLds actor_carve(unsigned char *raw, const int S1)
-{
-    ActorLds S;
-    S.f_wih = reinterpret_cast<float4 *>(raw);
-    S.s_whh = S.f_wih + 4 * 2 * 4 * 64;
-    S.f_w1 = reinterpret_cast<float *>(S.s_whh + 4 * 8 * 32);
-    S.s_g = S.f_w1 + 2 * S1 * 64;
-    S.s_hid = S.s_g + kFusedRows * kGs;
-    S.s_b1 = S.s_hid + kFusedRows * kHs;
-    S.s_bih = S.s_b1 + 64;
-    S.s_w2 = S.s_bih + 256;
-    S.s_b2 = S.s_w2 + 1024;
-    S.s_hx = S.s_b2 + 16;
-    S.s_lg = S.s_g;
-    S.end = reinterpret_cast<unsigned char *>(S.s_hx + 512);
-    return S;
+    LdsCursor c{reinterpret_cast<float *>(raw)}; ActorLds S;
+    S.f_wih = c.take<float4>(4 * 2 * 4 * 64); S.s_whh = c.take<float4>(4 * 8 * 32); S.f_w1 = c.take<float>(2 * S1 * 64);
+    S.s_g = c.take<float>(kFusedRows * kGs); S.s_hid = c.take<float>(kFusedRows * kHs);
+    S.s_b1 = c.take<float>(64); S.s_bih = c.take<float>(256);
+    S.s_w2 = c.take<float>(1024); S.s_b2 = c.take<float>(16);
+    S.s_hx = c.take<float>(512); S.s_lg = S.s_g;
+    S.bytes = 4 * c.at; return S;
 }
 
 // one direction's weights -> LDS: W_ih fragments (32 KB) + W_hh (16 KB, re-laid as [gate][k/4][unit]); called by
@@ -603,7 +597,7 @@ template <int S1C>
 __global__ void __launch_bounds__(512) pw_actor_fused_kernel(const ActorFusedArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const ActorLds S = actor_carve(smem_raw, 4 * S1C);
+    const ActorLds S = actor_lds(4 * S1C, smem_raw);
     const int N = A.N, E = A.E;
     const long env0 = (long)blockIdx.x * E;
     const int envs_here = (int)((long)A.B - env0 < (long)E ? (long)A.B - env0 : (long)E);

@@ -57,37 +57,20 @@ struct Roll3Lds {
     float2 *s_lmb;   // [E * L]
     double *s_fs;    // [16]
     int *s_fc;       // [16]
+    unsigned char *red; uint32_t bytes;   // red: alias, rollout_finish_stats' 8 KB over the start of the block
 };
-__host__ __device__ inline size_t roll3_lds_bytes(int E, int N, int L, int D, int S1)
+__host__ __device__ inline Roll3Lds roll3_lds(int E, int N, int L, int D, int S1, unsigned char *raw = nullptr)
 {
-    const size_t rows = (size_t)E * N;
-    size_t fl = (size_t)N * 4 * 64 * 4 + 2 * 2 * 2 * 64 * 4 + ((rows + 15) / 16) * 1024 + (size_t)2 * S1 * 64 + 64 + 16 + rows * 5 + 1 +
-                rows * (D + 2) + rows + 1;
-    return fl * 4 + 8 * kWave * sizeof(float2) + (size_t)E * L * sizeof(float2) + 16 * (sizeof(double) + sizeof(int)) + 64;
-}
-__device__ __forceinline__ Roll3Lds roll3_carve(unsigned char *raw, int E, int N, int L, int D, int S1)
-{
-    // offsets in floats from the (16-byte aligned) base; no pointer <-> integer casts (LDS address space kept)
     const int rows = E * N;
-    float *base = reinterpret_cast<float *>(raw);
-    Roll3Lds S;
-    int o = 0;
-    S.s_xf = reinterpret_cast<float4 *>(base + o); o += N * 4 * 64 * 4;
-    S.s_hx = reinterpret_cast<float4 *>(base + o); o += 2 * 2 * 2 * 64 * 4;
-    S.s_hf = reinterpret_cast<float4 *>(base + o); o += ((rows + 15) / 16) * 1024;
-    S.f_w1 = base + o; o += 2 * S1 * 64;
-    S.s_b1 = base + o; o += 64;
-    S.s_b2 = base + o; o += 16;
-    S.s_noise = base + o; o += rows * 5;
-    o = (o + 1) & ~1;
-    S.s_obs = base + o; o += rows * (D + 2);
-    S.s_act = reinterpret_cast<int32_t *>(base + o); o += rows;
-    o = (o + 1) & ~1;
-    S.s_posb = reinterpret_cast<float2 *>(base + o); o += 8 * kWave * 2;
-    S.s_lmb = reinterpret_cast<float2 *>(base + o); o += E * L * 2;
-    S.s_fs = reinterpret_cast<double *>(base + o); o += 32;
-    S.s_fc = reinterpret_cast<int *>(base + o);
-    return S;
+    LdsCursor c{reinterpret_cast<float *>(raw), false}; Roll3Lds S;
+    S.s_xf = c.take<float4>(N * 4 * 64); S.s_hx = c.take<float4>(2 * 2 * 2 * 64);
+    S.s_hf = c.take<float4>(((rows + 15) / 16) * 4 * 64);
+    S.f_w1 = c.take<float>(2 * S1 * 64);
+    S.s_b1 = c.take<float>(64); S.s_b2 = c.take<float>(16); S.s_noise = c.take<float>(rows * 5);
+    S.s_obs = c.take<float>(rows * (D + 2), 8); S.s_act = c.take<int32_t>(rows);
+    S.s_posb = c.take<float2>(8 * kWave, 8); S.s_lmb = c.take<float2>(E * L);
+    S.s_fs = c.take<double>(16); S.s_fc = c.take<int>(16);
+    S.red = raw; S.bytes = 4 * (c.at - c.pad) + 8 + 64; return S;   // trailing slack: the launch has always reserved both 4-byte pads, and 64 bytes
 }
 
 template <int S1C, int NT, bool SINK, bool BF3 = false>  // BF3: the opt-in, not exact bf16x3 input projection (pw_kernels_actor16.hpp)
@@ -99,7 +82,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
     const ActorFusedArgs &A = P.A;
     const StreamParams &V = P.V;
     const int N = NT ? NT : A.N, L = LT ? LT : V.L, D = A.D, DS = D + 2, E = A.E;
-    const Roll3Lds S = roll3_carve(smem_raw, E, N, L, D, S1);
+    const Roll3Lds S = roll3_lds(E, N, L, D, S1, smem_raw);
 
     const int tid = threadIdx.x, lane = tid & 63, half = lane >> 5, col = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -521,7 +504,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
         wg_lds_barrier();
         if (live && a == 0) { S.s_fs[el] = fin_sum; S.s_fc[el] = fin_cnt; }
         wg_lds_barrier();
-        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.scratch, P.finished_sum, P.finished_count, smem_raw);
+        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.scratch, P.finished_sum, P.finished_count, S.red);
     }
 }
 

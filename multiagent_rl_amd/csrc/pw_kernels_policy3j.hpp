@@ -73,45 +73,24 @@ struct Roll3jLds {
     float *s_ret;    // [16] running episode return (SINK)
     double *s_fs;    // [16]
     int *s_fc;       // [16]
+    unsigned char *red; uint32_t bytes;   // red: alias, rollout_finish_stats' 8 KB over the start of the block
 };
-__host__ __device__ inline size_t roll3j_lds_bytes(int E, int NP, int L, bool half)   // NP: the row stride (>= N)
-{
-    const size_t rows = (size_t)E * NP;
-    const size_t head = half ? (size_t)NP * 2 * 64 * 4 : ((rows + 15) / 16) * 1024;
-    const size_t fl = 2 * 2 * 4 * 64 * 4 + 2 * 2 * 2 * 64 * 4 + head + 16 + 3 + rows * 4 + 1;
-    // (!HALF: the byte actions alias the x1 ring -- idle between the head and the environment step -- and no near masks are kept: at
-    // N = 30 the full-head form fits its 16 environments with 240 bytes to spare)
-    return fl * 4 + (half ? ((rows + 15) & ~(size_t)15) + rows * sizeof(uint64_t) : 0) + 8 * kWave * sizeof(float2) + (size_t)E * L * sizeof(float2) + 16 * (3 * 4 + sizeof(double) + sizeof(int)) + 64;
-}
-__device__ __forceinline__ Roll3jLds roll3j_carve(unsigned char *raw, int E, int NP, int L, bool half)
+// NP: the row stride (>= N).  !half: the byte actions alias the x1 ring -- idle between the head and the environment step -- and no
+// near masks are kept: at N = 30 the full-head form fits its 16 environments with 240 bytes to spare
+__host__ __device__ inline Roll3jLds roll3j_lds(int E, int NP, int L, bool half, unsigned char *raw = nullptr)
 {
     const int rows = E * NP;
-    float *base = reinterpret_cast<float *>(raw);
-    Roll3jLds S;
-    int o = 0;
-    S.s_xf = reinterpret_cast<float4 *>(base + o); o += 2 * 2 * 4 * 64 * 4;
-    S.s_hx = reinterpret_cast<float4 *>(base + o); o += 2 * 2 * 2 * 64 * 4;
-    S.s_hf = reinterpret_cast<float4 *>(base + o); o += half ? NP * 2 * 64 * 4 : ((rows + 15) / 16) * 1024;
-    S.s_b2 = base + o; o += 16;
-    o = (o + 3) & ~3;
-    S.s_st = reinterpret_cast<float4 *>(base + o); o += rows * 4;
-    if (half) {
-        S.s_act = reinterpret_cast<uint8_t *>(base + o); o += ((rows + 15) & ~15) / 4;
-        o = (o + 1) & ~1;
-        S.s_near = reinterpret_cast<uint64_t *>(base + o); o += rows * 2;
-    } else {
-        S.s_act = reinterpret_cast<uint8_t *>(S.s_xf);   // rows <= 1024 bytes of the ring's 16 KB: written by the head, read by the environment lanes
-        S.s_near = nullptr;
-        o = (o + 1) & ~1;
-    }
-    S.s_posb = reinterpret_cast<float2 *>(base + o); o += 8 * kWave * 2;
-    S.s_lmb = reinterpret_cast<float2 *>(base + o); o += E * L * 2;
-    S.s_fs = reinterpret_cast<double *>(base + o); o += 32;
-    S.s_fc = reinterpret_cast<int *>(base + o); o += 16;
-    S.s_eps = reinterpret_cast<int *>(base + o); o += 16;
-    S.s_epc = reinterpret_cast<uint32_t *>(base + o); o += 16;
-    S.s_ret = base + o;
-    return S;
+    LdsCursor c{reinterpret_cast<float *>(raw), false}; Roll3jLds S;
+    S.s_xf = c.take<float4>(2 * 2 * 4 * 64); S.s_hx = c.take<float4>(2 * 2 * 2 * 64);
+    S.s_hf = c.take<float4>(half ? NP * 2 * 64 : ((rows + 15) / 16) * 4 * 64);
+    S.s_b2 = c.take<float>(16); S.s_st = c.take<float4>(rows, 16);
+    // !half: the byte actions are an alias of the x1 ring (rows <= 1024 bytes of its 16 KB) and there are no near masks
+    S.s_act = half ? c.take<uint8_t>((rows + 15) & ~15) : reinterpret_cast<uint8_t *>(S.s_xf);
+    S.s_near = half ? c.take<uint64_t>(rows, 8) : nullptr;
+    S.s_posb = c.take<float2>(8 * kWave, half ? 4 : 8); S.s_lmb = c.take<float2>(E * L);
+    S.s_fs = c.take<double>(16); S.s_fc = c.take<int>(16);
+    S.s_eps = c.take<int>(16); S.s_epc = c.take<uint32_t>(16); S.s_ret = c.take<float>(16);
+    S.red = raw; S.bytes = 4 * (c.at - c.pad) + 16 + 64; return S;   // trailing slack: the launch has always reserved a 12- and a 4-byte pad, and 64 bytes
 }
 
 template <int S1C, bool SINK, bool HALF>
@@ -123,7 +102,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
     const ActorFusedArgs &A = P.A;
     const StreamParams &V = P.V;
     const int N = A.N, L = V.L, D = A.D, E = A.E, NP = P.NP;
-    const Roll3jLds S = roll3j_carve(smem_raw, E, NP, L, HALF);
+    const Roll3jLds S = roll3j_lds(E, NP, L, HALF, smem_raw);
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -563,7 +542,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
     }
     if (SINK && P.episode_return) {
         wg_lds_barrier();
-        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.scratch, P.finished_sum, P.finished_count, smem_raw);
+        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.scratch, P.finished_sum, P.finished_count, S.red);
     }
 }
 

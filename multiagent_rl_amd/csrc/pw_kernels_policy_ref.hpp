@@ -37,6 +37,23 @@ struct PolicyRolloutRefArgs {
     unsigned long long *scratch;
 };
 
+// The actor16 block (N = 2, 16 environments), then the rollout's own regions
+struct PolicyRefLds {
+    Actor16Lds a16; float *s_obs2, *s_noise; int32_t *s_act; double *s_fs; int *s_fc;
+    unsigned char *red; uint32_t bytes;   // red: alias, rollout_finish_stats' 8 KB over the start of the block
+};
+__host__ __device__ inline PolicyRefLds policy_ref_lds(int S1, int D, int E, unsigned char *raw = nullptr)
+{
+    PolicyRefLds o; o.a16 = actor16_lds(2, E * 2, S1, raw);
+    LdsCursor c = LdsCursor::after(raw, o.a16.bytes, o.a16.end);
+    // observation rows, TWO buffers of [96][D]: the policy reads buffer `cur`, the environment lanes publish the next rows into the other
+    // one -- so that, with a ring sink, the IDLE waves can copy the rows the policy acted on into ring.obs during the environment step
+    o.s_obs2 = c.take<float>(2 * kFusedRows * D); o.s_act = c.take<int32_t>(2 * kFusedRows);   // s_act: [96][2] (movement, symbol)
+    o.s_fs = c.take<double>(16); o.s_fc = c.take<int>(16);   // [16] each: finished-episode sums / counts (SINK)
+    o.s_noise = reinterpret_cast<float *>(c.take<float4>(actor16_noise_blocks(32, 5 + kDimC), 16));   // [32][4 blocks][4] Gumbel noise of the coming heads (drawn a step ahead)
+    o.red = raw; o.bytes = 4 * (c.at - c.pad) + 16; return o;   // trailing slack: the launch has always reserved 16 bytes for the noise's pad
+}
+
 #ifdef PW_STAMPS
 __device__ unsigned long long g_pw_ref_stamps[30];
 #endif
@@ -47,20 +64,13 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const ActorFusedArgs &A = P.A;
     const RefParams &V = P.V;
-    const Actor16Lds S = actor16_carve(reinterpret_cast<float *>(smem_raw), N, A.E * N, 4 * S1C);
     const int D = A.D;
+    const PolicyRefLds Y = policy_ref_lds(4 * S1C, D, A.E, smem_raw);
+    const Actor16Lds &S = Y.a16;
     Actor16W W;  // the actor's weights: registers for the whole launch (pw_kernels_actor16.hpp)
     actor16_load<S1C>(A, S, W);
     Actor16D1<S1C> T1;  // dense1 as 16 x 16 tiles: with N = 2 the 32 x 32 form has two blocks for eight waves
     actor16_load_d1<S1C>(A, T1);
-    // observation rows, TWO buffers of [96][D]: the policy reads buffer `cur`, the environment lanes publish the next rows into the other
-    // one -- so that, with a ring sink, the IDLE waves can copy the rows the policy acted on into ring.obs during the environment step
-    float *s_obs2 = reinterpret_cast<float *>(S.end);
-    int32_t *s_act = reinterpret_cast<int32_t *>(s_obs2 + 2 * kFusedRows * D);  // [96][2] (movement, symbol)
-    double *s_fs = reinterpret_cast<double *>(s_act + 2 * kFusedRows);     // [16] (+ [16] ints): finished-episode sums / counts (SINK)
-    int *s_fc = reinterpret_cast<int *>(s_fs + 16);
-    float *s_noise = reinterpret_cast<float *>(smem_raw) +                 // [32][4 blocks][4] Gumbel noise of the coming heads (drawn a step
-                     (((int)(reinterpret_cast<float *>(s_fc + 16) - reinterpret_cast<float *>(smem_raw)) + 3) & ~3);   // ahead), 16-byte aligned
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -95,10 +105,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
         float co[DC];
 #pragma unroll
         for (int q = 0; q < DC; ++q) co[q] = __shfl_xor(s.c[q], 1, kWave);
-        if (live) ref_write_obs<DC, false>(V, s, co, a, s_obs2 + r * D);
+        if (live) ref_write_obs<DC, false>(V, s, co, a, Y.s_obs2 + r * D);
     }
     const uint64_t step0 = A.step_dev ? (uint64_t)*A.step_dev : A.step;
-    actor16_draw_noise(A, s_noise, rows_here, row_base, step0, tid, 512);
+    actor16_draw_noise(A, Y.s_noise, rows_here, row_base, step0, tid, 512);
     wg_lds_barrier();
 
     // the rest of a step once the agents are advanced and the next observation rows published: rewards + episode step count
@@ -152,13 +162,13 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
 #define PW_REF_STAMP_ARGS
 #endif
     for (int t = 0; t < P.T; ++t) {
-        float *s_obs = s_obs2 + (t & 1) * (kFusedRows * D);          // what the policy acts on in this step
-        float *s_next = s_obs2 + ((t + 1) & 1) * (kFusedRows * D);   // where the environment lanes publish the next rows
+        float *s_obs = Y.s_obs2 + (t & 1) * (kFusedRows * D);          // what the policy acts on in this step
+        float *s_next = Y.s_obs2 + ((t + 1) & 1) * (kFusedRows * D);   // where the environment lanes publish the next rows
         // ---- policy: observation rows (LDS) -> one sampled index per head and row (LDS)
-        actor16_forward<S1C, false>(A, S, W, s_obs, D, rows_here, envs_here, row_base, step0 + (uint64_t)t, nullptr, s_act, pre_hook,
-                                    mid_hook, s_noise, &T1 PW_REF_STAMP_ARGS);  // a barrier at its end
+        actor16_forward<S1C, false>(A, S, W, s_obs, D, rows_here, envs_here, row_base, step0 + (uint64_t)t, nullptr, Y.s_act, pre_hook,
+                                    mid_hook, Y.s_noise, &T1 PW_REF_STAMP_ARGS);  // a barrier at its end
         // the noise of the NEXT step's heads: by the seven waves that wait for the environment wave
-        if (t + 1 < P.T && !env_wave) actor16_draw_noise(A, s_noise, rows_here, row_base, step0 + (uint64_t)(t + 1), tid, 7 * kWave);
+        if (t + 1 < P.T && !env_wave) actor16_draw_noise(A, Y.s_noise, rows_here, row_base, step0 + (uint64_t)(t + 1), tid, 7 * kWave);
         if (SINK && P.has_ring && !env_wave) {
             // the observations the policy acted on -> ring.obs, by the seven waves that would otherwise wait for the environment wave
             for (int idx = tid; idx < rows_here * D; idx += 448) {
@@ -171,7 +181,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
         // ---- environment step (pw_reference_rollout_kernel's arithmetic, index actions)
         if (env_wave) {
             const size_t row = (size_t)t * BN + g;
-            ai = s_act[2 * r]; ci = s_act[2 * r + 1];
+            ai = Y.s_act[2 * r]; ci = Y.s_act[2 * r + 1];
             if (SINK && P.has_ring) {  // the pair the policy sampled -> ring.act (the observation rows: the idle waves, above)
                 slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
                 if (live) {
@@ -238,9 +248,9 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
     }
     if (SINK && P.episode_return) {  // finished-episode statistics: per-workgroup partials, the last workgroup adds them up in order
         wg_lds_barrier();
-        if (live && a == 0) { s_fs[el] = fin_sum; s_fc[el] = fin_cnt; }
+        if (live && a == 0) { Y.s_fs[el] = fin_sum; Y.s_fc[el] = fin_cnt; }
         wg_lds_barrier();
-        rollout_finish_stats(envs_here, s_fs, s_fc, P.scratch, P.finished_sum, P.finished_count, smem_raw);
+        rollout_finish_stats(envs_here, Y.s_fs, Y.s_fc, P.scratch, P.finished_sum, P.finished_count, Y.red);
     }
 }
 

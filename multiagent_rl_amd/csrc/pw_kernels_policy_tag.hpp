@@ -23,11 +23,23 @@ struct PolicyRolloutTagArgs {
     unsigned long long *scratch;
 };
 
-__host__ __device__ inline size_t policy_tag_lds_bytes(int S1, int D, int E, int L, int N)
+// The actor16 block, then the rollout's own regions
+struct PolicyTagLds {
+    Actor16Lds a16; float *s_obs, *s_rewb, *s_noise; int32_t *s_act; float2 *s_posb, *s_velb, *s_lmb; uint32_t *s_mlob, *s_mhib; double *s_fs; int *s_fc;
+    unsigned char *red; uint32_t bytes;   // red: alias, rollout_finish_stats' 8 KB over the start of the block
+};
+__host__ __device__ inline PolicyTagLds policy_tag_lds(int S1, int D, int E, int L, int N, unsigned char *raw = nullptr)
 {
-    return actor16_lds_floats(N, E * N, S1) * sizeof(float) + (size_t)kFusedRows * D * sizeof(float) + kFusedRows * sizeof(int32_t) +
-           4 * kWave * sizeof(float2) + (size_t)E * L * sizeof(float2) + 3 * 2 * kWave * sizeof(float) +
-           16 * (sizeof(double) + sizeof(int)) + (size_t)actor16_noise_floats(kFusedRows, 5) * sizeof(float);
+    PolicyTagLds o; o.a16 = actor16_lds(N, E * N, S1, raw);
+    LdsCursor c = LdsCursor::after(raw, o.a16.bytes, o.a16.end);
+    o.s_obs = c.take<float>(kFusedRows * D); o.s_act = c.take<int32_t>(kFusedRows);   // [96][D] observation rows, [96]
+    o.s_posb = c.take<float2>(2 * kWave); o.s_velb = c.take<float2>(2 * kWave);   // [2 env waves][64] each
+    o.s_lmb = c.take<float2>(E * L);               // [E * L]
+    o.s_mlob = c.take<uint32_t>(2 * kWave); o.s_mhib = c.take<uint32_t>(2 * kWave);   // [2][64] collision masks; mhib unused (32-bit masks), keeps the offsets behind it
+    o.s_rewb = c.take<float>(2 * kWave);           // [2][64]
+    o.s_fs = c.take<double>(16); o.s_fc = c.take<int>(16);   // [16] each
+    o.s_noise = reinterpret_cast<float *>(c.take<float4>(actor16_noise_blocks(kFusedRows, 5), 16));   // [96][2 blocks][4] Gumbel noise of the coming head (drawn a step ahead)
+    o.red = raw; o.bytes = 4 * (c.at - c.pad) + 16; return o;   // trailing slack: the launch has always reserved 16 bytes for the noise's pad
 }
 
 // One 5-logit head per agent: every agent of simple_tag takes the same five movement actions; the observation rows
@@ -42,21 +54,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
     const ActorFusedArgs &A = P.A;
     const TagParams &V = P.V;
     const int N = A.N, L = V.L, D = A.D, NA = V.A;
-    const Actor16Lds S = actor16_carve(reinterpret_cast<float *>(smem_raw), N, A.E * N, 4 * S1C);
+    const PolicyTagLds Y = policy_tag_lds(4 * S1C, D, A.E, L, N, smem_raw);
+    const Actor16Lds &S = Y.a16;
     Actor16W W;  // the actor's weights: registers for the whole launch (pw_kernels_actor16.hpp)
     actor16_load<S1C>(A, S, W);
-    float *s_obs = reinterpret_cast<float *>(S.end);                       // [96][D] observation rows
-    int32_t *s_act = reinterpret_cast<int32_t *>(s_obs + kFusedRows * D);  // [96]
-    float2 *s_posb = reinterpret_cast<float2 *>(s_act + kFusedRows);       // [2 env waves][64]
-    float2 *s_velb = s_posb + 2 * kWave;                                   // [2][64]
-    float2 *s_lmb = s_velb + 2 * kWave;                                    // [E * L]
-    uint32_t *s_mlob = reinterpret_cast<uint32_t *>(s_lmb + A.E * L);      // [2][64] collision masks, low / high words
-    uint32_t *s_mhib = s_mlob + 2 * kWave;                                 // (unused since the masks are 32 bits wide; keeps the carve-up)
-    float *s_rewb = reinterpret_cast<float *>(s_mhib + 2 * kWave);         // [2][64]
-    double *s_fs = reinterpret_cast<double *>(s_rewb + 2 * kWave);         // [16] (+ [16] ints)
-    int *s_fc = reinterpret_cast<int *>(s_fs + 16);
-    float *s_noise = reinterpret_cast<float *>(smem_raw) +                 // [96][2 blocks][4] Gumbel noise of the coming head (drawn a step
-                     (((int)(reinterpret_cast<float *>(s_fc + 16) - reinterpret_cast<float *>(smem_raw)) + 3) & ~3);   // ahead), 16-byte aligned
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -82,11 +83,11 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
     const long env = env0 + el;
     const uint32_t g_lane = (uint32_t)env * (uint32_t)N + (uint32_t)a, g = g_lane;
     const int ew = env_wave ? ewi : 0;
-    float2 *s_pos = s_posb + ew * kWave, *s_vel = s_velb + ew * kWave;
-    uint32_t *s_mlo = s_mlob + ew * kWave;
-    float *s_rew = s_rewb + ew * kWave;
+    float2 *s_pos = Y.s_posb + ew * kWave, *s_vel = Y.s_velb + ew * kWave;
+    uint32_t *s_mlo = Y.s_mlob + ew * kWave;
+    float *s_rew = Y.s_rewb + ew * kWave;
     const float2 *pp = s_pos + base, *vv = s_vel + base;
-    float2 *lmv = s_lmb + el * L;
+    float2 *lmv = Y.s_lmb + el * L;
     const int cls = a >= NA ? 1 : 0;
     // Register diet (this kernel sat at the 256-register cap of a 512-thread workgroup and spilled 4 .. 10 VGPRs to scratch): the
     // masks are 32 bits wide (the host admits D = 4 + 2L + 2(N - 1) + 2G <= 48 here: N <= 22, L <= 21), the finished-episode sums live
@@ -132,7 +133,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
         }
         near_a &= ~(1u << a);
     };
-    if (SINK && tid < 16) { s_fs[tid] = 0.0; s_fc[tid] = 0; }   // per-env finished-episode (sum, count) of this launch
+    if (SINK && tid < 16) { Y.s_fs[tid] = 0.0; Y.s_fc[tid] = 0; }   // per-env finished-episode (sum, count) of this launch
     if (env_wave) {
         if (SINK && P.episode_return && live && a == 0) ep_ret = P.episode_return[env];
         px = V.pos_x[g]; py = V.pos_y[g]; vx = V.vel_x[g]; vy = V.vel_y[g];
@@ -143,14 +144,14 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
         if (live) { s_pos[me] = make_float2(px, py); s_vel[me] = make_float2(vx, vy); }
         wave_lds_sync();
         partner_pass();
-        if (live) write_row(s_obs + r * D);
+        if (live) write_row(Y.s_obs + r * D);
     }
     const float k = V.contact_margin, cf = V.contact_force, dt = V.dt, damp = V.damp, mass = V.mass;
     const uint64_t step0 = A.step_dev ? (uint64_t)*A.step_dev : A.step;
     // the Gumbel noise of step t + 1 is drawn by the waves without environment duty while the environment waves advance step t (by
     // everybody, first, when every wave has environment duty)
     const int noise_thr = n_env_waves < 8 ? (8 - n_env_waves) * kWave : 512;
-    actor16_draw_noise(A, s_noise, rows_here, row_base, step0, tid, 512);
+    actor16_draw_noise(A, Y.s_noise, rows_here, row_base, step0, tid, 512);
     wg_lds_barrier();
 
     // The rest of an environment step once the agents are advanced and the next observation rows published, in two pieces:
@@ -195,7 +196,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
         t_acc = acc;
         if (SINK && live && a == 0 && P.episode_return) {
             const float rsum = ep_ret + acc;
-            if (t_term) { s_fs[el] += (double)rsum; s_fc[el] += 1; ep_ret = 0.0f; }   // once per episode: LDS, not registers
+            if (t_term) { Y.s_fs[el] += (double)rsum; Y.s_fc[el] += 1; ep_ret = 0.0f; }   // once per episode: LDS, not registers
             else ep_ret = rsum;
         }
     };
@@ -217,7 +218,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
                 if (V.terminal) V.terminal[(size_t)t * A.B + env] = t_term ? 1 : 0;
             }
             // with_obs: no reset in between, so next_obs and obs are both the row this lane published in LDS -- copied, not rebuilt
-            const float2 *row = reinterpret_cast<const float2 *>(s_obs + r * D);
+            const float2 *row = reinterpret_cast<const float2 *>(Y.s_obs + r * D);
             if (SINK && P.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
                 const size_t slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
                 float *dst = P.ring.next_obs + (slot * N + a) * D;
@@ -243,22 +244,22 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
 #define PW_TAG_STAMP_ARGS
 #endif
     for (int t = 0; t < P.T; ++t) {
-        actor16_forward<S1C, false>(A, S, W, s_obs, D, rows_here, envs_here, row_base, step0 + (uint64_t)t, nullptr, s_act, pre_hook,
-                                    mid_hook, s_noise, nullptr PW_TAG_STAMP_ARGS);  // a barrier at its end
-        if (t + 1 < P.T && tid < noise_thr) actor16_draw_noise(A, s_noise, rows_here, row_base, step0 + (uint64_t)(t + 1), tid, noise_thr);
+        actor16_forward<S1C, false>(A, S, W, Y.s_obs, D, rows_here, envs_here, row_base, step0 + (uint64_t)t, nullptr, Y.s_act, pre_hook,
+                                    mid_hook, Y.s_noise, nullptr PW_TAG_STAMP_ARGS);  // a barrier at its end
+        if (t + 1 < P.T && tid < noise_thr) actor16_draw_noise(A, Y.s_noise, rows_here, row_base, step0 + (uint64_t)(t + 1), tid, noise_thr);
         PW_R2_STAMP(7);
         if (env_wave) {
             const size_t tBN = (size_t)t * BN;
             const uint32_t g = opaque(g_lane);
             const int r = (int)opaque((uint32_t)r_lane);
-            ai = s_act[r];
+            ai = Y.s_act[r];
             if (SINK && P.has_ring) {  // the observation the policy acted on (still in LDS) -> ring.obs
                 const size_t slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
                 if (live) {
                     if (P.ring.state_rows) {
                         sink_state_obs(P.ring, slot, N, a, L, lmv, px, py, vx, vy);
                     } else {
-                        const float2 *src = reinterpret_cast<const float2 *>(s_obs + r * D);
+                        const float2 *src = reinterpret_cast<const float2 *>(Y.s_obs + r * D);
                         float2 *dst = reinterpret_cast<float2 *>(P.ring.obs + (slot * N + a) * D);
                         for (int c = 0; c < D / 2; ++c) dst[c] = src[c];
                     }
@@ -322,10 +323,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
                 if (__any(term && V.auto_reset)) partner_pass();
                 if (live) {
                     if (V.obs) write_row(V.obs + (tBN + g) * D);
-                    write_row(s_obs + r * D);
+                    write_row(Y.s_obs + r * D);
                 }
             } else {
-                if (live) write_row(s_obs + r * D);
+                if (live) write_row(Y.s_obs + r * D);
                 tail_stage = 1;
                 tail_t = t;
             }
@@ -357,7 +358,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
     }
     if (SINK && P.episode_return) {
         wg_lds_barrier();
-        rollout_finish_stats(envs_here, s_fs, s_fc, P.scratch, P.finished_sum, P.finished_count, smem_raw);
+        rollout_finish_stats(envs_here, Y.s_fs, Y.s_fc, P.scratch, P.finished_sum, P.finished_count, Y.red);
     }
 }
 

@@ -44,7 +44,7 @@ __global__ void __launch_bounds__(kWave) pw_spread_fast_kernel(const KParams P, 
                                                                const FastConsts C)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const Smem S = carve(P, smem_raw);
+    const Smem S = smem_lds(P.epw, P.N, P.L, smem_raw);
     const Lane ln = make_lane(P);
     const int N = NT ? NT : P.N, L = P.L, D = P.D;
     const size_t BN = (size_t)P.B * N;
@@ -455,6 +455,15 @@ __device__ __forceinline__ void stream_partner_pass(const int N, const int a, co
     }
 }
 
+struct SpreadStreamLds { float2 *s_pos, *s_lm; float4 *s_row; uint32_t bytes; };
+__host__ __device__ inline SpreadStreamLds spread_stream_lds(int epw, int L, unsigned char *raw = nullptr)
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; SpreadStreamLds o;
+    o.s_pos = c.take<float2>(kWave); o.s_row = c.take<float4>(kWave);   // [64] positions; [64] {pos, vel} per row, for the block-wise obs stores
+    o.s_lm = c.take<float2>(epw * L);     // [epw * L]
+    o.bytes = 4 * c.at; return o;
+}
+
 template <int NT, int LT, bool UNIT_MASS, bool COLL = false, bool BLOCK = false>
 __global__ void __launch_bounds__(kWave) pw_spread_stream_kernel(const StreamParams A, const int T)
 {
@@ -462,9 +471,7 @@ __global__ void __launch_bounds__(kWave) pw_spread_stream_kernel(const StreamPar
     constexpr bool kNtPlanes = NT > 0 && NT <= 6;  // per-agent / per-env planes with the non-temporal hint (PW_PLANE_STORE; pw_common.hpp nt_store)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int N = NT ? NT : A.N, L = LT ? LT : A.L, D = 4 + 2 * L;
-    float2 *s_pos = reinterpret_cast<float2 *>(smem_raw);  // [64]
-    float4 *s_row = reinterpret_cast<float4 *>(s_pos + kWave);  // [64] {pos, vel} per row, for the block-wise obs stores
-    float2 *s_lm = reinterpret_cast<float2 *>(s_row + kWave);   // [epw * L]
+    const SpreadStreamLds Y = spread_stream_lds(A.epw, L, smem_raw);
     const int rows_here = (A.B - (int)blockIdx.x * A.epw < A.epw ? A.B - (int)blockIdx.x * A.epw : A.epw) * N;
 
     int e_local = (int)threadIdx.x / N;
@@ -476,8 +483,8 @@ __global__ void __launch_bounds__(kWave) pw_spread_stream_kernel(const StreamPar
     const int base = e_local * N;
     const uint32_t g = (uint32_t)env * (uint32_t)N + (uint32_t)a;
     const size_t BN = (size_t)A.B * N;
-    const float2 *pp = s_pos + base;
-    float2 *lmv = s_lm + e_local * L;
+    const float2 *pp = Y.s_pos + base;
+    float2 *lmv = Y.s_lm + e_local * L;
     const int la = a < L ? a : 0;  // the landmark this lane "owns" (lanes a >= L duplicate 0, unused)
 
     float px = A.pos_x[g], py = A.pos_y[g], vx = A.vel_x[g], vy = A.vel_y[g];
@@ -489,7 +496,7 @@ __global__ void __launch_bounds__(kWave) pw_spread_stream_kernel(const StreamPar
         oly = A.lm_y[(size_t)env * L + la];
         lmv[la] = make_float2(olx, oly);
     }
-    s_pos[base + a] = make_float2(px, py);
+    Y.s_pos[base + a] = make_float2(px, py);
     wave_lds_sync();
     MaskT coll, near;
     float best;
@@ -531,7 +538,7 @@ __global__ void __launch_bounds__(kWave) pw_spread_stream_kernel(const StreamPar
         px = px + vx * dt;
         py = py + vy * dt;
         wave_lds_sync();
-        s_pos[base + a] = make_float2(px, py);
+        Y.s_pos[base + a] = make_float2(px, py);
         wave_lds_sync();
         PW_STAMP(2);
 
@@ -573,17 +580,17 @@ __global__ void __launch_bounds__(kWave) pw_spread_stream_kernel(const StreamPar
                 pw_reset_xy(A.seed, env_id, ep_count, (uint32_t)(N + la), -1.0f, 1.0f, &olx, &oly);
                 lmv[la] = make_float2(olx, oly);
             }
-            s_pos[base + a] = make_float2(px, py);
+            Y.s_pos[base + a] = make_float2(px, py);
         }
         // (lanes whose env did not reset wait here for the ones that did: one wave, reconverged)
-        if (BLOCK) s_row[base + a] = make_float4(px, py, vx, vy);
+        if (BLOCK) Y.s_row[base + a] = make_float4(px, py, vx, vy);
         wave_lds_sync();
         if (A.auto_reset && __any(term))
             stream_partner_pass<NT, MaskT>(N, a, pp, px, py, olx, oly, A.coll_thr2, A.near_thr2, coll, near, best);
         PW_STAMP(5);
         if constexpr (BLOCK)
             stream_write_obs_block<NT, LT>(A.obs + (tBN + (size_t)blockIdx.x * A.epw * N) * D, rows_here, (int)threadIdx.x,
-                                           s_row, s_lm);
+                                           Y.s_row, Y.s_lm);
         else
             stream_write_obs<LT>(A.obs + (tBN + g) * D, L, lmv, px, py, vx, vy);
         PW_STAMP(6);
@@ -637,6 +644,18 @@ __device__ __forceinline__ MaskT duo_near_pass(const int N, const int a, const f
     return near & ~((MaskT)1 << a);
 }
 
+struct SpreadDuoLds { float4 *s_ring, *s_row; float2 *s_lm, *s_utab, *s_zero; float *s_min, *s_rew; int32_t *s_actr; uint32_t bytes; };
+__host__ __device__ inline SpreadDuoLds spread_duo_lds(int epw, int L, unsigned char *raw = nullptr)
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; SpreadDuoLds o;
+    o.s_ring = c.take<float4>(3 * kWave); o.s_lm = c.take<float2>(epw * L);   // [3][64] {px, py, vx, vy}; [epw * L] (wave O only)
+    o.s_min = c.take<float>(kWave); o.s_rew = c.take<float>(kWave);   // [64] per-landmark min dist, [64] per-agent reward (wave O)
+    o.s_row = c.take<float4>(kWave, 16);   // [64] {pos, vel} of every row after the step (post-reset where the env reset), for O's block-wise obs stores (float4 reads: padded when epw * L is odd)
+    o.s_utab = c.take<float2>(8); o.s_zero = c.take<float2>(8);   // [8] action force per index (wave P); {0, 0} (planned observation stores), 56 bytes unused
+    o.s_actr = c.take<int32_t>(4 * kWave);   // [4][64] wave P's action ring (kActRing instantiations)
+    o.bytes = 4 * (c.at - c.pad) + 16; return o;     // trailing slack: the launch has always reserved 16 bytes for the pad
+}
+
 template <int NT, int LT, bool UNIT_MASS, bool COLL = false, bool BLOCK = false, bool TRIO = false>
 __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(const StreamParams A, const int T)
 {
@@ -644,17 +663,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
     constexpr bool kNtPlanes = NT > 0 && NT <= 6;  // per-agent / per-env planes with the non-temporal hint (PW_PLANE_STORE; pw_common.hpp nt_store)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int N = NT ? NT : A.N, L = LT ? LT : A.L, D = 4 + 2 * L;
-    float4 *s_ring = reinterpret_cast<float4 *>(smem_raw);            // [3][64] {px, py, vx, vy}
-    float2 *s_lm = reinterpret_cast<float2 *>(s_ring + 3 * kWave);    // [epw * L]      (wave O only)
-    float *s_min = reinterpret_cast<float *>(s_lm + A.epw * L);       // [64] per-landmark min dist (O)
-    float *s_rew = s_min + kWave;                                     // [64] per-agent reward      (O)
-    // [64] {pos, vel} of every row after the step (post-reset where the env reset), for O's block-wise obs stores;
-    // 16-byte aligned: 3*64*16 + epw*L*8 + 512 bytes precede it and epw*L*8 is a multiple of 16 when L is even
-    // (odd L: the block writer reads it as float4 too, so pad)
-    float4 *s_row = reinterpret_cast<float4 *>(smem_raw + ((3 * kWave * sizeof(float4) + (size_t)A.epw * L * sizeof(float2) +
-                                                            2 * kWave * sizeof(float) + 15) & ~(size_t)15));
-    float2 *s_utab = reinterpret_cast<float2 *>(s_row + kWave);      // [8] action force per index (wave P)
-    float2 *s_zero = s_utab + 8;                                     // {0, 0} (planned observation stores)
+    const SpreadDuoLds Y = spread_duo_lds(A.epw, L, smem_raw);
     // Three-wave form at N = 12 (C5's N = 12 point: 820 workgroups at B = 4096): wave P's action indices arrive four steps ahead by
     // LDS-direct loads, as in pw_spread_quad_kernel / pw_tag_duo_kernel (pw_common.hpp act_fetch_issue).  With the output wave split
     // in two, P is the step's longest wave there and its one-step-ahead register load cost it 800 of its 3230 cycles per step (stamps,
@@ -662,7 +671,6 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
     // 6144 (profiles/r5_n12_action_ring.txt).  N = 24 in this form loses 1.4 % (B = 2048), and the two-wave form keeps the register load
     // everywhere: its output wave is the longer one, and P waits for the index instead of waiting at the barrier (profiles/r3_tag_prefetch.txt).
     constexpr bool kActRing = TRIO && NT == 12;
-    int32_t *s_actr = reinterpret_cast<int32_t *>(s_utab + 16);     // [4][64] (kActRing; 16-byte aligned)
     constexpr int kPlanIters = obs_plan_iters<NT, LT>();
     constexpr bool kPlan = BLOCK && kPlanIters >= 1 && kPlanIters <= PW_PLAN_MAX;
 
@@ -690,7 +698,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
         switch (A.p_prio & 3) { case 1: __builtin_amdgcn_s_setprio(1); break; case 2: __builtin_amdgcn_s_setprio(2); break;
                                 case 3: __builtin_amdgcn_s_setprio(3); break; default: break; }
         float px = A.pos_x[g], py = A.pos_y[g], vx = A.vel_x[g], vy = A.vel_y[g];
-        s_ring[me] = make_float4(px, py, vx, vy);
+        Y.s_ring[me] = make_float4(px, py, vx, vy);
         wave_lds_sync();
         // U2 + U4 as a table: the action force of an index is one of five constants, computed here once with the step's
         // own expressions (so the bits are the step's), entry 5 = any other index (no force); a step reads ONE entry
@@ -700,14 +708,14 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
             float uy = 0.0f + ((ai == 3 ? 1.0f : 0.0f) - (ai == 4 ? 1.0f : 0.0f));
             ux *= A.sens; uy *= A.sens;
             if (A.fscale != 1.0f) { ux = A.fscale * ux; uy = A.fscale * uy; }
-            s_utab[lane] = make_float2(ux + 0.0f, uy + 0.0f);
+            Y.s_utab[lane] = make_float2(ux + 0.0f, uy + 0.0f);
         }
         wave_lds_sync();
-        MaskT near = duo_near_pass<NT, MaskT>(N, a, s_ring + base, px, py, A.near_thr2);
+        MaskT near = duo_near_pass<NT, MaskT>(N, a, Y.s_ring + base, px, py, A.near_thr2);
         const float k = A.contact_margin, cf = A.contact_force, dt = A.dt, damp = A.damp, mass = A.mass;
         int act_next = 0;
         const int32_t *act_g = A.act + g;
-        const uint32_t act_lds = kActRing ? __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(s_actr)) : 0u;
+        const uint32_t act_lds = kActRing ? __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(Y.s_actr)) : 0u;
         auto fetch_act = [&](int t) {  // indices of step t (clamped: the tail re-fetches the last step) -> slot t & 3
             act_fetch_issue(act_g + (size_t)(t < T ? t : T - 1) * BN, act_lds + (uint32_t)(t & 3) * (kWave * 4));
         };
@@ -724,16 +732,16 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
             uint32_t ai;
             if constexpr (kActRing) {
                 act_fetch_wait3();  // step t's indices are in LDS (the later fetches stay in flight)
-                ai = (uint32_t)s_actr[(t & 3) * kWave + lane];
+                ai = (uint32_t)Y.s_actr[(t & 3) * kWave + lane];
                 fetch_act(t + 4);   // into the slot just read
             } else {
                 ai = (uint32_t)act_next;
                 const int tn = t + 1 < T ? t + 1 : t;
                 act_next = A.act[(size_t)tn * BN + g];
             }
-            const float2 u0 = s_utab[ai < 5u ? ai : 5u];  // {u_x + 0, u_y + 0}: the accumulators' starting values
+            const float2 u0 = Y.s_utab[ai < 5u ? ai : 5u];  // {u_x + 0, u_y + 0}: the accumulators' starting values
             float fx = u0.x, fy = u0.y;
-            const float4 *pp = s_ring + cur * kWave + base;
+            const float4 *pp = Y.s_ring + cur * kWave + base;
             PW_STAMP(0);
             near_force_loop<MaskT, float4>(near, pp, px, py, A.dist_min, k, cf, fx, fy);
             PW_STAMP(1);
@@ -743,7 +751,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
             px = px + vx * dt;
             py = py + vy * dt;
             int nxt = cur + 1; nxt = nxt == 3 ? 0 : nxt;
-            s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
+            Y.s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
             ep_step += 1;
             if (A.auto_reset && A.max_episode_len > 0 && ep_step >= A.max_episode_len) {
                 ep_count += 1;
@@ -751,13 +759,13 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
                 pw_reset_xy(A.seed, env_id, ep_count, (uint32_t)a, -1.0f, 1.0f, &px, &py);
                 vx = 0.f; vy = 0.f;
                 nxt = nxt + 1; nxt = nxt == 3 ? 0 : nxt;
-                s_ring[nxt * kWave + me] = make_float4(px, py, 0.f, 0.f);
+                Y.s_ring[nxt * kWave + me] = make_float4(px, py, 0.f, 0.f);
             }
             cur = nxt;
             PW_STAMP(2);
             duo_barrier();  // slot(s) published; O has finished with the slot P overwrites next
             PW_STAMP(3);
-            near = duo_near_pass<NT, MaskT>(N, a, s_ring + cur * kWave + base, px, py, A.near_thr2);
+            near = duo_near_pass<NT, MaskT>(N, a, Y.s_ring + cur * kWave + base, px, py, A.near_thr2);
             PW_STAMP(4);
         }
         PW_STAMP_FLUSH;
@@ -775,7 +783,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
         const bool do_rew = !TRIO || wave == 1, do_obs = !TRIO || wave == 2;  // compile-time true in the two-wave form
         switch ((A.p_prio >> (2 * wave)) & 3) { case 1: __builtin_amdgcn_s_setprio(1); break; case 2: __builtin_amdgcn_s_setprio(2); break;
                                                 case 3: __builtin_amdgcn_s_setprio(3); break; default: break; }
-        float2 *lmv = s_lm + e_local * L;
+        float2 *lmv = Y.s_lm + e_local * L;
         const int la = a < L ? a : 0;
         float olx = 0.f, oly = 0.f;
         if (L > 0) {
@@ -788,8 +796,8 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
         uint32_t plan[kPlan ? kPlanIters : 1];
         if constexpr (kPlan) {
             if (do_obs) {
-                if (lane == 0) *s_zero = make_float2(0.0f, 0.0f);
-                obs_plan_build<NT, LT, kPlanIters>(plan, rows_here, lane, smem_raw, s_row, s_lm, s_zero);
+                if (lane == 0) *Y.s_zero = make_float2(0.0f, 0.0f);
+                obs_plan_build<NT, LT, kPlanIters>(plan, rows_here, lane, smem_raw, Y.s_row, Y.s_lm, Y.s_zero);
             }
         }
         PW_STAMP_DECL;
@@ -799,7 +807,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
             duo_barrier();
             PW_STAMP(0);
             int nxt = cur + 1; nxt = nxt == 3 ? 0 : nxt;
-            const float4 *slot = s_ring + nxt * kWave + base;
+            const float4 *slot = Y.s_ring + nxt * kWave + base;
             const float4 mine = slot[a];
             float px = mine.x, py = mine.y, vx = mine.z, vy = mine.w;
             if (do_rew) {
@@ -815,11 +823,11 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
                     const float e2 = ex * ex + ey * ey;
                     best = (j == 0 || e2 < best) ? e2 : best;
                 }
-                s_min[me] = sqrtf(best);
+                Y.s_min[me] = sqrtf(best);
                 wave_lds_sync();
                 float r = 0.0f;
 #pragma unroll(LT > 0 ? LT : 1)
-                for (int l = 0; l < (LT ? LT : L); ++l) r -= s_min[base + l];
+                for (int l = 0; l < (LT ? LT : L); ++l) r -= Y.s_min[base + l];
                 // "rew -= 1" once per colliding agent (itself included): the subtrahends are all 1.0, so only their NUMBER
                 // matters.  Few agents collide at a time: for large N a loop up to the wave's largest count (a handful of
                 // iterations) replaces N bit tests -- N = 48: ~12 instead of 144 instructions per step, on grids that are
@@ -833,11 +841,11 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
                     for (int j = 0; j < (NT ? NT : N); ++j)
                         if ((coll >> j) & 1) r -= 1.0f;
                 }
-                s_rew[me] = r;
+                Y.s_rew[me] = r;
                 wave_lds_sync();
                 float acc = 0.0f;
 #pragma unroll(NT > 0 ? NT : 1)
-                for (int i = 0; i < (NT ? NT : N); ++i) acc += s_rew[base + i];
+                for (int i = 0; i < (NT ? NT : N); ++i) acc += Y.s_rew[base + i];
                 PW_STAMP(1);
                 PW_PLANE_STORE(A.rew[tBN + g], r);
                 if (COLL) { PW_PLANE_STORE(A.coll[tBN + g], (uint64_t)coll); }
@@ -861,17 +869,17 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_spread_duo_kernel(c
                     if (do_obs) lmv[la] = make_float2(olx, oly);
                 }
                 nxt = nxt + 1; nxt = nxt == 3 ? 0 : nxt;
-                const float4 fresh = s_ring[nxt * kWave + me];  // post-reset state published by P
+                const float4 fresh = Y.s_ring[nxt * kWave + me];  // post-reset state published by P
                 px = fresh.x; py = fresh.y; vx = fresh.z; vy = fresh.w;
             }
             cur = nxt;
             if (do_obs) {
-                if (BLOCK) s_row[me] = kPlan ? make_float4(vx, vy, px, py) : make_float4(px, py, vx, vy);
+                if (BLOCK) Y.s_row[me] = kPlan ? make_float4(vx, vy, px, py) : make_float4(px, py, vx, vy);
                 wave_lds_sync();
                 if constexpr (kPlan)
                     obs_plan_store<NT, LT, kPlanIters>(A.obs + (tBN + (size_t)blockIdx.x * A.epw * N) * D, rows_here, lane, plan, smem_raw);
                 else if constexpr (BLOCK)
-                    stream_write_obs_block<NT, LT>(A.obs + (tBN + (size_t)blockIdx.x * A.epw * N) * D, rows_here, lane, s_row, s_lm);
+                    stream_write_obs_block<NT, LT>(A.obs + (tBN + (size_t)blockIdx.x * A.epw * N) * D, rows_here, lane, Y.s_row, Y.s_lm);
                 else
                     stream_write_obs<LT>(A.obs + (tBN + g) * D, L, lmv, px, py, vx, vy);
             }

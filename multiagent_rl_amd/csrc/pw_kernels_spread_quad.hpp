@@ -114,19 +114,24 @@ __device__ __forceinline__ void quad_pair_force(const float2 qi, const float2 qj
 #define PW_QUAD_PAD_OB()
 #endif
 constexpr int kQuadActAhead = PW_QUAD_ACT_AHEAD;
-constexpr int kQuadActRingBytes = kQuadActAhead * kWave * (int)sizeof(int32_t);  // per physics wave
+constexpr int kQuadN = 6, kQuadL = 6, kQuadEPP = 4, kQuadEPW = 8;   // agents, landmarks, envs per physics wave / per workgroup
+struct SpreadQuadLds { float4 *s_ring; float2 *s_ftab, *s_lmB, *s_utab; float *s_min, *s_rew; int32_t *s_act; uint32_t bytes; };
+__host__ __device__ inline SpreadQuadLds spread_quad_lds(unsigned char *raw = nullptr)
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; SpreadQuadLds o;
+    o.s_ring = c.take<float4>(4 * kWave);                        // [4][64] {px, py, vx, vy}, index e_local * 6 + a
+    o.s_ftab = c.take<float2>(2 * kQuadEPP * kQuadN * kQuadN);   // [2 P waves][24 agents][6 partners]
+    o.s_min = c.take<float>(kWave); o.s_rew = c.take<float>(kWave);   // [64] each, not used any more: they keep the offsets behind them
+    o.s_lmB = c.take<float2>(kQuadEPW * kQuadL); o.s_act = c.take<int32_t>(2 * kQuadActAhead * kWave);   // [8 * 6] OB; [2 P waves][4 steps][64] action indices
+    o.s_utab = c.take<float2>(2 * 8);                            // [2 P waves][8] action force per index
+    o.bytes = 4 * c.at; return o;
+}
 template <bool UNIT_MASS, bool COLL = false, bool K1 = false>
 __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamParams A, const int T)
 {
-    constexpr int N = 6, L = 6, D = 16, P2 = 15, EPP = 4, EPW = 8;
+    constexpr int N = kQuadN, L = kQuadL, D = 16, P2 = 15, EPP = kQuadEPP, EPW = kQuadEPW;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    float4 *s_ring = reinterpret_cast<float4 *>(smem_raw);                 // [4][64] {px, py, vx, vy}, index e_local * 6 + a
-    float2 *s_ftab = reinterpret_cast<float2 *>(s_ring + 4 * kWave);       // [2 P waves][24 agents][6 partners]
-    float *s_min = reinterpret_cast<float *>(s_ftab + 2 * EPP * N * N);    // [64] OA
-    float *s_rew = s_min + kWave;                                          // [64] OA
-    float2 *s_lmB = reinterpret_cast<float2 *>(s_rew + kWave);             // [8 * 6] OB (16-byte aligned)
-    int32_t *s_act = reinterpret_cast<int32_t *>(s_lmB + EPW * L);         // [2 P waves][4 steps][64] action indices
-    float2 *s_utab = reinterpret_cast<float2 *>(s_act + 2 * kQuadActAhead * kWave);    // [2 P waves][8] action force per index
+    const SpreadQuadLds Y = spread_quad_lds(smem_raw);
 
     // Roles by wave index, swapped in every other batch of 256 workgroups: the hardware places a workgroup's waves 0..3 on
     // the CU's SIMDs in order, and with two workgroups per CU (B = 4096: 512 workgroups on 256 CUs, workgroup j and j + 256
@@ -193,17 +198,17 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         const int ri = (e0 + pe) * N + pi, rj = (e0 + pe) * N + pj;
         // force table [agent][partner slot]: a row holds the agent's 5 partners in ascending order (slot = partner index,
         // minus one behind the agent's own index), padded to 6 entries so that rows stay 16-byte aligned
-        float2 *ftab = s_ftab + wave * (EPP * N * N);
+        float2 *ftab = Y.s_ftab + wave * (EPP * N * N);
         float2 *f_ij = ftab + (pe * N + pi) * N + (pj - 1), *f_ji = ftab + (pe * N + pj) * N + pi;   // pi < pj
         const float2 *row = ftab + (e4 * N + a) * N;
 
         float px = A.pos_x[g], py = A.pos_y[g], vx = A.vel_x[g], vy = A.vel_y[g];
         int ep_off = A.ep_step[env];  // clock before step t = t + ep_off
         uint32_t ep_count = A.ep_count[env];
-        s_ring[me] = make_float4(px, py, vx, vy);
+        Y.s_ring[me] = make_float4(px, py, vx, vy);
         // U2 + U4 as a table: the action force of an index is one of five constants, computed here once with the step's
         // own expressions (so the bits are the step's), entry 5 = any other index (no force); a step reads ONE entry
-        float2 *utab = s_utab + wave * 8;
+        float2 *utab = Y.s_utab + wave * 8;
         if (lane < 6) {
             const int ai = lane;
             float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
@@ -220,7 +225,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         const unsigned char *act_row = reinterpret_cast<const unsigned char *>(A.act);   // the action plane of the next step to fetch: workgroup-uniform, a running pointer
         const size_t act_stride = BN * sizeof(int32_t);
         const uint32_t act_off = g * (uint32_t)sizeof(int32_t);
-        int32_t *act_ring = s_act + wave * (kQuadActAhead * kWave);
+        int32_t *act_ring = Y.s_act + wave * (kQuadActAhead * kWave);
         const uint32_t act_lds = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(act_ring));
         // indices of step t -> slot t & 3; called for t = 0, 1, 2, ... in turn.  The tail re-fetches the last step: the pointer's
         // stride turns 0 there (also from the start, if T is below the fetch depth)
@@ -235,8 +240,8 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         // the pair lanes' operands of the coming step are fetched right after the publish, before the barrier (this
         // wave only reads its own envs' entries, and a wave's LDS operations execute in issue order): the read's latency
         // hides behind the barrier
-        float2 qi = *reinterpret_cast<const float2 *>(s_ring + ri);
-        float2 qj = *reinterpret_cast<const float2 *>(s_ring + rj);
+        float2 qi = *reinterpret_cast<const float2 *>(Y.s_ring + ri);
+        float2 qj = *reinterpret_cast<const float2 *>(Y.s_ring + rj);
         PW_STAMP_DECL;
         for (int t = 0; t < T; ++t) {
             PW_STAMP_START;
@@ -268,7 +273,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             px = px + vx * dt;
             py = py + vy * dt;
             int nxt = (cur + 1) & 3;
-            s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
+            Y.s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
             if (__builtin_expect(two_slots, 0)) {  // rare (once per episode): the envs at their episode's end restart, EVERY env publishes a second slot
                 if (t + 1 + ep_off >= A.max_episode_len) {
                     ep_count += 1;
@@ -278,12 +283,12 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
                 }
                 reset_step_update(t);
                 nxt = (nxt + 1) & 3;
-                s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
+                Y.s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
             }
             cur = nxt;
             asm volatile("" ::: "memory");
-            qi = *reinterpret_cast<const float2 *>(s_ring + cur * kWave + ri);
-            qj = *reinterpret_cast<const float2 *>(s_ring + cur * kWave + rj);
+            qi = *reinterpret_cast<const float2 *>(Y.s_ring + cur * kWave + ri);
+            qj = *reinterpret_cast<const float2 *>(Y.s_ring + cur * kWave + rj);
             PW_STAMP(1);
             PW_QUAD_PAD_P();
             PW_QUAD_BARRIER(t);
@@ -329,7 +334,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         // the pieces, in the order an iteration interleaves them
         float2 mine, q6[N];
         auto a_reads = [&](const int nxt) __attribute__((always_inline)) {
-            const float4 *slot = s_ring + nxt * kWave + base;
+            const float4 *slot = Y.s_ring + nxt * kWave + base;
             mine = *reinterpret_cast<const float2 *>(slot + a);
 #pragma unroll
             for (int j = 0; j < N; ++j) q6[j] = *reinterpret_cast<const float2 *>(slot + j);
@@ -471,9 +476,9 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
     auto load_landmarks = [&]() {  // the two landmarks of this lane's column group, per row's env
 #pragma unroll
         for (int u = 0; u < 3; ++u)
-            lm_u[u] = *reinterpret_cast<const float4 *>(s_lmB + (row_u[u] / N) * L + (cgrp > 0 ? 2 * cgrp - 2 : 0));
+            lm_u[u] = *reinterpret_cast<const float4 *>(Y.s_lmB + (row_u[u] / N) * L + (cgrp > 0 ? 2 * cgrp - 2 : 0));
     };
-    s_lmB[me] = make_float2(olx, oly);
+    Y.s_lmB[me] = make_float2(olx, oly);
     wave_lds_sync();
     load_landmarks();
     // workgroup-uniform plane pointers of step t (the compiler keeps them in scalar registers: every term is uniform)
@@ -495,8 +500,8 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             const bool rst = t >= t_term;
             if (rst) {
                 if (A.final_obs) {
-                    const float4 st = s_ring[nxt * kWave + me];  // this lane's own (env, agent) row, pre-reset
-                    stream_write_obs<L>(A.final_obs + ((size_t)t * BN + g) * D, L, s_lmB + base, st.x, st.y, st.z, st.w);
+                    const float4 st = Y.s_ring[nxt * kWave + me];  // this lane's own (env, agent) row, pre-reset
+                    stream_write_obs<L>(A.final_obs + ((size_t)t * BN + g) * D, L, Y.s_lmB + base, st.x, st.y, st.z, st.w);
                 }
                 ep_count += 1;
                 ep_off = -(t + 1);
@@ -505,13 +510,13 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             }
             reset_step_update(t);
             wave_lds_sync();     // the pre-reset rows have read the old landmarks
-            if (rst) s_lmB[me] = make_float2(olx, oly);
+            if (rst) Y.s_lmB[me] = make_float2(olx, oly);
             wave_lds_sync();
             load_landmarks();
             nxt = (nxt + 1) & 3;  // the post-reset slot (the same state for envs that did not reset)
         }
         cur = nxt;
-        const float4 *slot = s_ring + nxt * kWave;
+        const float4 *slot = Y.s_ring + nxt * kWave;
         float4 st[3];
 #pragma unroll
         for (int u = 0; u < 3; ++u) st[u] = slot[row_u[u]];

@@ -54,18 +54,23 @@ __device__ __forceinline__ void tag_write_obs(float *__restrict__ o, const int N
     while (2 * k < D) o2[k++] = make_float2(0.0f, 0.0f);
 }
 
+struct TagStreamLds { float2 *s_pos, *s_vel, *s_lm; uint32_t *s_mlo, *s_mhi; float *s_rew; uint32_t bytes; };
+__host__ __device__ inline TagStreamLds tag_stream_lds(int epw, int L, unsigned char *raw = nullptr)
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; TagStreamLds o;
+    o.s_pos = c.take<float2>(kWave); o.s_vel = c.take<float2>(kWave);       // [64] each
+    o.s_mlo = c.take<uint32_t>(kWave); o.s_mhi = c.take<uint32_t>(kWave);   // [64] collision mask, low / high words
+    o.s_rew = c.take<float>(kWave); o.s_lm = c.take<float2>(epw * L);       // [64], [epw * L]
+    o.bytes = 4 * c.at; return o;
+}
+
 // NT / AT / LT: compile-time N / A / L (0 / -1 / 0 = runtime)
 template <int NT, int AT, int LT, bool UNIT_MASS, bool COLL = false>
 __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P, const int T)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int N = NT ? NT : P.N, A = AT >= 0 ? AT : P.A, L = LT ? LT : P.L, D = P.D;
-    float2 *s_pos = reinterpret_cast<float2 *>(smem_raw);   // [64]
-    float2 *s_vel = s_pos + kWave;                           // [64]
-    uint32_t *s_mlo = reinterpret_cast<uint32_t *>(s_vel + kWave);  // [64] collision mask, low / high words
-    uint32_t *s_mhi = s_mlo + kWave;
-    float *s_rew = reinterpret_cast<float *>(s_mhi + kWave);  // [64]
-    float2 *s_lm = reinterpret_cast<float2 *>(s_rew + kWave); // [epw * L]
+    const TagStreamLds Y = tag_stream_lds(P.epw, L, smem_raw);
 
     int e_local = (int)threadIdx.x / N;
     int a = (int)threadIdx.x - e_local * N;
@@ -77,8 +82,8 @@ __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P,
     const int cls = a >= A ? 1 : 0;
     const uint32_t g = (uint32_t)env * (uint32_t)N + (uint32_t)a;
     const size_t BN = (size_t)P.B * N;
-    const float2 *pp = s_pos + base, *vv = s_vel + base;
-    float2 *lmv = s_lm + e_local * L;
+    const float2 *pp = Y.s_pos + base, *vv = Y.s_vel + base;
+    float2 *lmv = Y.s_lm + e_local * L;
     const uint64_t env_id = P.env_id_base + (uint64_t)env;
     const uint64_t adv_bits = A >= 64 ? ~0ull : ((1ull << A) - 1ull);
 
@@ -91,8 +96,8 @@ __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P,
     int ep_step = P.ep_step[env];
     uint32_t ep_count = P.ep_count[env];
     for (int l = a; l < L; l += N) lmv[l] = make_float2(P.lm_x[(size_t)env * L + l], P.lm_y[(size_t)env * L + l]);
-    s_pos[me] = make_float2(px, py);
-    s_vel[me] = make_float2(vx, vy);
+    Y.s_pos[me] = make_float2(px, py);
+    Y.s_vel[me] = make_float2(vx, vy);
     wave_lds_sync();
 
     // collision mask of the current state + near sets of the next force evaluation
@@ -160,14 +165,14 @@ __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P,
         px = px + vx * dt;
         py = py + vy * dt;
         wave_lds_sync();
-        s_pos[me] = make_float2(px, py);
-        s_vel[me] = make_float2(vx, vy);
+        Y.s_pos[me] = make_float2(px, py);
+        Y.s_vel[me] = make_float2(vx, vy);
         wave_lds_sync();
         partner_pass();
 
         // ---- simple_tag.reward
-        s_mlo[me] = (uint32_t)coll;
-        s_mhi[me] = (uint32_t)(coll >> 32);
+        Y.s_mlo[me] = (uint32_t)coll;
+        Y.s_mhi[me] = (uint32_t)(coll >> 32);
         wave_lds_sync();
         float r = 0.0f;
         if (cls) {
@@ -177,14 +182,14 @@ __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P,
             r -= tag_bound(fabsf(py));
         } else {
             for (int gj = A; gj < N; ++gj) {  // +10 per colliding (good, adversary) pair: exact small integers
-                const uint64_t mg = ((uint64_t)s_mhi[base + gj] << 32) | s_mlo[base + gj];
+                const uint64_t mg = ((uint64_t)Y.s_mhi[base + gj] << 32) | Y.s_mlo[base + gj];
                 r += 10.0f * (float)__builtin_popcountll(mg & adv_bits);
             }
         }
-        s_rew[me] = r;
+        Y.s_rew[me] = r;
         wave_lds_sync();
         float acc = 0.0f;
-        for (int i = 0; i < N; ++i) acc += s_rew[base + i];
+        for (int i = 0; i < N; ++i) acc += Y.s_rew[base + i];
         nt_store(&P.rew[tBN + g], r);
         nt_store(&P.done[tBN + g], (uint8_t)0);
         if (COLL) nt_store(&P.coll[tBN + g], coll);
@@ -205,8 +210,8 @@ __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P,
                 pw_reset_xy(P.seed, env_id, ep_count, (uint32_t)(N + l), -0.9f, 0.9f, &x, &y);
                 lmv[l] = make_float2(x, y);
             }
-            s_pos[me] = make_float2(px, py);
-            s_vel[me] = make_float2(0.f, 0.f);
+            Y.s_pos[me] = make_float2(px, py);
+            Y.s_vel[me] = make_float2(0.f, 0.f);
         }
         wave_lds_sync();
         if (P.auto_reset && __any(term)) partner_pass();
@@ -233,22 +238,28 @@ __global__ void __launch_bounds__(kWave) pw_tag_stream_kernel(const TagParams P,
 // its own copy of the landmarks (both draw them from Philox at a reset), so the only cross-wave traffic is
 // the ring.  Used while the grid is small enough to be latency bound.
 // ------------------------------------------------------------------------------------------
+// rows_D: the row length D where the launch stores observation blocks (TagParams.obs_block), else 0: no staging regions
+struct TagDuoLds { float4 *s_ring, *s_state; uint32_t *s_mlo, *s_mhi; float *s_rew, *s_rows; float2 *s_lm_p, *s_lm_o, *s_zero; int32_t *s_act; uint32_t bytes; };
+__host__ __device__ inline TagDuoLds tag_duo_lds(int epw, int L, int rows_D, unsigned char *raw = nullptr)
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; TagDuoLds o;
+    o.s_ring = c.take<float4>(3 * kWave);                                 // [3][64] {px, py, vx, vy}
+    o.s_mlo = c.take<uint32_t>(kWave); o.s_mhi = c.take<uint32_t>(kWave);   // [64] each (wave O)
+    o.s_rew = c.take<float>(kWave);                                       // [64] (wave O)
+    o.s_lm_p = c.take<float2>(epw * L); o.s_lm_o = c.take<float2>(epw * L); // [epw * L] each: wave P's landmarks, wave O's
+    o.s_act = c.take<int32_t>(4 * kWave, 16);   // [4][64] wave P's action indices, fetched four steps ahead by LDS-direct loads (pw_common.hpp act_fetch_issue)
+    o.s_rows = c.take<float>(kWave * rows_D);   // [64][D] the wave's observation rows, staged for the block-wise store
+    // the compile-time rosters compose the block directly instead of staging rows (kDirect): aliases inside `rows`, [64] {pos, vel} of every row; {0, 0}
+    o.s_state = reinterpret_cast<float4 *>(o.s_rows); o.s_zero = reinterpret_cast<float2 *>(o.s_state + kWave);
+    o.bytes = 4 * c.at; return o;
+}
+
 template <int NT, int AT, int LT, bool UNIT_MASS, bool COLL = false, bool TRIO = false>
 __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(const TagParams P, const int T)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int N = NT ? NT : P.N, A = AT >= 0 ? AT : P.A, L = LT ? LT : P.L, D = P.D;
-    float4 *s_ring = reinterpret_cast<float4 *>(smem_raw);                 // [3][64] {px, py, vx, vy}
-    uint32_t *s_mlo = reinterpret_cast<uint32_t *>(s_ring + 3 * kWave);    // [64] (wave O)
-    uint32_t *s_mhi = s_mlo + kWave;
-    float *s_rew = reinterpret_cast<float *>(s_mhi + kWave);               // [64] (wave O)
-    float2 *s_lm_p = reinterpret_cast<float2 *>(s_rew + kWave);            // [epw * L] wave P's landmarks
-    float2 *s_lm_o = s_lm_p + P.epw * L;                                   // [epw * L] wave O's landmarks
-    // [4][64] wave P's action indices, fetched four steps ahead by LDS-direct loads (pw_common.hpp act_fetch_issue)
-    int32_t *s_act = reinterpret_cast<int32_t *>(smem_raw + ((3 * kWave * sizeof(float4) + 3 * kWave * sizeof(float) +
-                                                              2 * (size_t)P.epw * L * sizeof(float2) + 15) & ~(size_t)15));
-    // [64][D] the wave's observation rows, staged for the block-wise store (only when P.obs_block; 16-byte aligned)
-    float *s_rows = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(s_act) + kActRingBytes);
+    const TagDuoLds Y = tag_duo_lds(P.epw, L, P.obs_block ? D : 0, smem_raw);
 
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int lane = (int)threadIdx.x & 63;
@@ -270,13 +281,13 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
     if (wave == 0) {
         // ================================ wave P: physics ================================
         if (P.p_prio) __builtin_amdgcn_s_setprio(3);  // serve the physics wave first where it shares a SIMD with output waves
-        float2 *lmv = s_lm_p + e_local * L;
+        float2 *lmv = Y.s_lm_p + e_local * L;
         const float my_sens = P.sens[cls], my_fscale = P.fscale[cls], my_maxspeed = P.max_speed[cls];
         const float dmin_adv = P.dist_min[cls][0], dmin_good = P.dist_min[cls][1], dmin_lm = P.dist_min_lm[cls];
         const float nthr_adv = P.near_thr2[cls][0], nthr_good = P.near_thr2[cls][1], nthr_lm = P.near_thr2_lm[cls];
         float px = P.pos_x[g], py = P.pos_y[g], vx = P.vel_x[g], vy = P.vel_y[g];
         for (int l = a; l < L; l += N) lmv[l] = make_float2(P.lm_x[(size_t)env * L + l], P.lm_y[(size_t)env * L + l]);
-        s_ring[me] = make_float4(px, py, vx, vy);
+        Y.s_ring[me] = make_float4(px, py, vx, vy);
         wave_lds_sync();
         uint64_t near_a = 0, near_l = 0;
         auto near_pass = [&](const float4 *slot) {
@@ -295,14 +306,14 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
                 if (bits_near(dx * dx + dy * dy, nthr_lm)) near_l |= 1ull << l;
             }
         };
-        near_pass(s_ring + base);
+        near_pass(Y.s_ring + base);
         const float k = P.contact_margin, cf = P.contact_force, dt = P.dt, damp = P.damp, mass = P.mass;
         // Action indices: four steps ahead by LDS-direct loads, as in pw_spread_quad_kernel.  Stamps at C3 (B = 8192,
         // profiles/r3_tag_prefetch.txt): the index loaded ONE step ahead into a register still cost this wave 1020 of its
         // 3140 cycles per step -- HBM latency under the output waves' write stream exceeds a step.  This wave has no other
         // vector memory operation in its loop; every load the compiler counts is consumed before the first fetch.
         const int32_t *act_g = P.act + g;
-        const uint32_t act_lds = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(s_act));
+        const uint32_t act_lds = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(Y.s_act));
         auto fetch_act = [&](int t) {  // indices of step t (clamped: the tail re-fetches the last step) -> slot t & 3
             act_fetch_issue(act_g + (size_t)(t < T ? t : T - 1) * BN, act_lds + (uint32_t)(t & 3) * (kWave * 4));
         };
@@ -316,14 +327,14 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
         for (int t = 0; t < T; ++t) {
             PW_STAMP_START;
             act_fetch_wait3();  // step t's indices are in LDS
-            const int ai = s_act[(t & 3) * kWave + lane];
+            const int ai = Y.s_act[(t & 3) * kWave + lane];
             fetch_act(t + 4);   // into the slot just read
             float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
             float uy = 0.0f + ((ai == 3 ? 1.0f : 0.0f) - (ai == 4 ? 1.0f : 0.0f));
             ux *= my_sens; uy *= my_sens;
             if (my_fscale != 1.0f) { ux = my_fscale * ux; uy = my_fscale * uy; }
             float fx = ux + 0.0f, fy = uy + 0.0f;
-            const float4 *pp = s_ring + cur * kWave + base;
+            const float4 *pp = Y.s_ring + cur * kWave + base;
             PW_STAMP(0);
             // ONE loop over the lane's near entities -- agents (ascending j), then landmarks (ascending l): upstream's entity
             // order per lane.  A wave runs as many iterations as its busiest lane needs: in two loops that was
@@ -361,7 +372,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
             px = px + vx * dt;
             py = py + vy * dt;
             int nxt = cur + 1; nxt = nxt == 3 ? 0 : nxt;
-            s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
+            Y.s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
             ep_step += 1;
             if (P.auto_reset && P.max_episode_len > 0 && ep_step >= P.max_episode_len) {
                 ep_count += 1;
@@ -374,13 +385,13 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
                     lmv[l] = make_float2(x, y);
                 }
                 nxt = nxt + 1; nxt = nxt == 3 ? 0 : nxt;
-                s_ring[nxt * kWave + me] = make_float4(px, py, 0.f, 0.f);
+                Y.s_ring[nxt * kWave + me] = make_float4(px, py, 0.f, 0.f);
             }
             cur = nxt;
             PW_STAMP(2);
             duo_barrier();
             PW_STAMP(3);
-            near_pass(s_ring + cur * kWave + base);
+            near_pass(Y.s_ring + cur * kWave + base);
             PW_STAMP(4);
         }
         act_fetch_drain();  // the tail's fetches have landed before the wave ends
@@ -397,7 +408,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
         // nothing but the ring slot they read, so each follows the slot sequence and the episode clock itself.
         const bool do_rew = !TRIO || wave == 1, do_obs = !TRIO || wave == 2;  // compile-time true in the two-wave form
         if (TRIO && wave == 2 && P.p_prio) __builtin_amdgcn_s_setprio(2);  // the observation wave is the longer of the two output waves
-        float2 *lmv = s_lm_o + e_local * L;
+        float2 *lmv = Y.s_lm_o + e_local * L;
         const float cthr_adv = P.coll_thr2[cls][0], cthr_good = P.coll_thr2[cls][1];
         const uint64_t adv_bits = A >= 64 ? ~0ull : ((1ull << A) - 1ull);
         for (int l = a; l < L; l += N) lmv[l] = make_float2(P.lm_x[(size_t)env * L + l], P.lm_y[(size_t)env * L + l]);
@@ -436,33 +447,31 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
         constexpr int DE = kDirect ? (4 + 2 * LT + 2 * (NT - 1) + 2 * (NT - AT)) / 2 : 1;
         constexpr int kMaxRows = kDirect ? (kWave / NT) * NT : 1;
         constexpr int NIT = kDirect ? (kMaxRows * DE + kWave - 1) / kWave : 1;
-        float4 *s_state = reinterpret_cast<float4 *>(s_rows);                 // [64] {pos, vel} of every row, current slot
-        float2 *s_zero = reinterpret_cast<float2 *>(s_state + kWave);         // {0, 0}
         int offA[NIT], offB[NIT];   // byte offsets into the workgroup's LDS
         const int envs_here_o = P.B - (int)blockIdx.x * P.epw < P.epw ? P.B - (int)blockIdx.x * P.epw : P.epw;
         const int n_entries = envs_here_o * N * DE;
         if (kDirect && do_obs && P.obs_block) {
-            if (lane == 0) *s_zero = make_float2(0.0f, 0.0f);
-            const int zoff = (int)(reinterpret_cast<unsigned char *>(s_zero) - smem_raw);
+            if (lane == 0) *Y.s_zero = make_float2(0.0f, 0.0f);
+            const int zoff = (int)(reinterpret_cast<unsigned char *>(Y.s_zero) - smem_raw);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
                 const int n = lane + kWave * it;
                 const int nn = n < n_entries ? n : 0;
                 const int r = nn / DE, kk = nn - r * DE;
                 const int e = r / NT, ar = r - e * NT;
-                const int self = (int)(reinterpret_cast<unsigned char *>(s_state + r) - smem_raw);  // {px, py, vx, vy}
+                const int self = (int)(reinterpret_cast<unsigned char *>(Y.s_state + r) - smem_raw);  // {px, py, vx, vy}
                 int oa, ob = zoff;
                 if (kk == 0) oa = self + 8;                        // vel
                 else if (kk == 1) oa = self;                       // pos
-                else if (kk < 2 + LT) { oa = (int)(reinterpret_cast<unsigned char *>(s_lm_o + e * LT + (kk - 2)) - smem_raw); ob = self; }
+                else if (kk < 2 + LT) { oa = (int)(reinterpret_cast<unsigned char *>(Y.s_lm_o + e * LT + (kk - 2)) - smem_raw); ob = self; }
                 else if (kk < 2 + LT + NT - 1) {
                     const int m = kk - 2 - LT, j = m < ar ? m : m + 1;
-                    oa = (int)(reinterpret_cast<unsigned char *>(s_state + e * NT + j) - smem_raw);
+                    oa = (int)(reinterpret_cast<unsigned char *>(Y.s_state + e * NT + j) - smem_raw);
                     ob = self;
                 } else {
                     int j = AT + (kk - (2 + LT + NT - 1));          // good agents in order, skipping the row's own
                     if (ar >= AT && j >= ar) j += 1;
-                    oa = j < NT ? (int)(reinterpret_cast<unsigned char *>(s_state + e * NT + j) - smem_raw) + 8 : zoff;
+                    oa = j < NT ? (int)(reinterpret_cast<unsigned char *>(Y.s_state + e * NT + j) - smem_raw) + 8 : zoff;
                 }
                 offA[it] = oa; offB[it] = ob;
             }
@@ -474,7 +483,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
             duo_barrier();
             PW_STAMP(0);
             int nxt = cur + 1; nxt = nxt == 3 ? 0 : nxt;
-            const float4 *slot = s_ring + nxt * kWave + base;
+            const float4 *slot = Y.s_ring + nxt * kWave + base;
             const float4 mine = slot[a];
             float px = mine.x, py = mine.y, vx = mine.z, vy = mine.w;
             ep_step += 1;
@@ -487,8 +496,8 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
                     const float dx = q.x - px, dy = q.y - py;
                     if (dx * dx + dy * dy < (j >= A ? cthr_good : cthr_adv)) coll |= 1ull << j;
                 }
-                s_mlo[me] = (uint32_t)coll;
-                s_mhi[me] = (uint32_t)(coll >> 32);
+                Y.s_mlo[me] = (uint32_t)coll;
+                Y.s_mhi[me] = (uint32_t)(coll >> 32);
                 wave_lds_sync();
                 float r = 0.0f;
                 if (cls) {
@@ -498,14 +507,14 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
                     r -= tag_bound(fabsf(py));
                 } else {
                     for (int gj = A; gj < N; ++gj) {
-                        const uint64_t mg = ((uint64_t)s_mhi[base + gj] << 32) | s_mlo[base + gj];
+                        const uint64_t mg = ((uint64_t)Y.s_mhi[base + gj] << 32) | Y.s_mlo[base + gj];
                         r += 10.0f * (float)__builtin_popcountll(mg & adv_bits);
                     }
                 }
-                s_rew[me] = r;
+                Y.s_rew[me] = r;
                 wave_lds_sync();
                 float acc = 0.0f;
-                for (int i = 0; i < N; ++i) acc += s_rew[base + i];
+                for (int i = 0; i < N; ++i) acc += Y.s_rew[base + i];
                 PW_STAMP(1);
                 nt_store(&P.rew[tBN + g], r);
                 nt_store(&P.done[tBN + g], (uint8_t)0);
@@ -526,7 +535,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
                     }
                 }
                 nxt = nxt + 1; nxt = nxt == 3 ? 0 : nxt;
-                slot = s_ring + nxt * kWave + base;  // post-reset state published by P
+                slot = Y.s_ring + nxt * kWave + base;  // post-reset state published by P
                 const float4 fresh = slot[a];
                 px = fresh.x; py = fresh.y; vx = fresh.z; vy = fresh.w;
             }
@@ -535,7 +544,7 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
             if (!do_obs) {
                 // (the rewards wave of a trio: nothing more in this step)
             } else if (kDirect && P.obs_block) {
-                s_state[me] = make_float4(px, py, vx, vy);
+                Y.s_state[me] = make_float4(px, py, vx, vy);
                 wave_lds_sync();
                 float2 *blk2 = reinterpret_cast<float2 *>(P.obs + (tBN + (size_t)blockIdx.x * P.epw * N) * D);
                 float2 va[NIT], vb[NIT];
@@ -553,17 +562,17 @@ __global__ void __launch_bounds__((TRIO ? 3 : 2) * kWave) pw_tag_duo_kernel(cons
                 // floats (every store instruction touches 48 cache lines); staged in LDS they leave as ONE block, 1 KiB
                 // (or 512 B) contiguous per store instruction -- what pw_kernels_spread.hpp's stream_write_obs_block does
                 // for simple_spread, here through LDS because a tag row is ragged (pw_common.hpp, nt_store: the hint).
-                write_row(s_rows + me * D, slot, px, py, vx, vy);
+                write_row(Y.s_rows + me * D, slot, px, py, vx, vy);
                 wave_lds_sync();
                 const int envs_here = P.B - (int)blockIdx.x * P.epw < P.epw ? P.B - (int)blockIdx.x * P.epw : P.epw;
                 const int total = envs_here * N * D;  // floats
                 float *blk = P.obs + (tBN + (size_t)blockIdx.x * P.epw * N) * D;
                 if (P.obs_block == 4) {
                     for (int q = lane; 4 * q < total; q += kWave)
-                        nt_store(reinterpret_cast<float4 *>(blk) + q, reinterpret_cast<const float4 *>(s_rows)[q]);
+                        nt_store(reinterpret_cast<float4 *>(blk) + q, reinterpret_cast<const float4 *>(Y.s_rows)[q]);
                 } else {
                     for (int q = lane; 2 * q < total; q += kWave)
-                        nt_store(reinterpret_cast<float2 *>(blk) + q, reinterpret_cast<const float2 *>(s_rows)[q]);
+                        nt_store(reinterpret_cast<float2 *>(blk) + q, reinterpret_cast<const float2 *>(Y.s_rows)[q]);
                 }
                 wave_lds_sync();  // the block's LDS reads are done before the rows change again
             } else {

@@ -275,7 +275,7 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
         return PW_OK;
     }
     const dim3 grid((kp.B + kp.epw - 1) / kp.epw), block(kWave);
-    const size_t shmem = smem_bytes(kp);
+    const size_t shmem = smem_lds(kp.epw, kp.N, kp.L).bytes;
     // max_episode_len = 1 with auto-reset: EVERY step ends an episode.  The multi-wave forms (duo / trio / quad) hand {pos, vel} from
     // the physics wave to the output waves through a 3- or 4-slot LDS ring and use TWO slots in a step that resets (pre-reset state,
     // post-reset state); with a reset in every step the physics wave, one step ahead, overwrites the pre-reset slot the output
@@ -289,13 +289,11 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
         A.act = io->act_idx; A.coll = io->coll;
         const bool wc = io->coll != nullptr;  // the optional collision-mask output: its own instantiations
         hipStream_t st = static_cast<hipStream_t>(stream);
-        const size_t shm = 2 * kWave * sizeof(float2) + 3 * kWave * sizeof(float) + (size_t)kp.epw * kp.L * sizeof(float2);
+        const size_t shm = tag_stream_lds(kp.epw, kp.L).bytes;
         const bool um = kp.mass == 1.0f;
         // two waves per env group, as for simple_spread.  With the block-wise observation stores (below) the duo form
         // leads on every grid measured: B = 8192: 1.69 vs 2.41 us per step, B = 65536: 10.3 vs 19.0 (profiles/r2_tag_block.txt)
         const bool duo = !every_step_resets && (dp.duo < 0 ? grid.x <= 8192 : dp.duo != 0);
-        size_t shm2 = ((3 * kWave * sizeof(float4) + 3 * kWave * sizeof(float) + 2 * (size_t)kp.epw * kp.L * sizeof(float2) + 15) &
-                       ~(size_t)15) + kActRingBytes;  // ring, masks, rewards, both waves' landmarks | wave P's action ring
         // Block-wise observation stores of the duo kernel (rows staged in LDS): short rows only (LDS), chunks of 4 floats
         // when every wave's block starts and ends on 16 bytes, else of 2 (D is even).  pw_dispatch.obs_block overrides.
         A.obs_block = 0;
@@ -309,9 +307,9 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
                 const bool v4 = ((size_t)kp.B * kp.N * kp.D) % 4 == 0 && ((size_t)kp.epw * kp.N * kp.D) % 4 == 0 &&
                                 (reinterpret_cast<uintptr_t>(io->obs) & 15) == 0 && kp.B % kp.epw == 0;
                 A.obs_block = v4 ? 4 : 2;
-                shm2 += (size_t)kWave * kp.D * sizeof(float);
             }
         }
+        const size_t shm2 = tag_duo_lds(kp.epw, kp.L, A.obs_block ? kp.D : 0).bytes;
         // Three waves per env group (the output wave split into a rewards wave and an observation wave) where the single
         // output wave is the step's critical path: measured crossover in profiles/r2_tag_block.txt.  pw_dispatch.trio overrides.
         bool trio = duo && grid.x >= 512 && grid.x <= 1280;
@@ -347,7 +345,7 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
         // time on grids up to 2048 workgroups (N = 3 / 12, B = 16384), +2..4 % on the larger ones (profiles/r2_priority.txt)
         A.p_prio = dp.p_prio >= 0 ? dp.p_prio : (grid.x <= 2048 ? 3 : 0);
         hipStream_t st = static_cast<hipStream_t>(stream);
-        const size_t shm = (size_t)(kWave + kp.epw * kp.L) * sizeof(float2) + kWave * sizeof(float4);
+        const size_t shm = spread_stream_lds(kp.epw, kp.L).bytes;
         const bool um = kp.mass == 1.0f;
         const bool wc = io->coll != nullptr;  // the optional collision-mask output: instantiated for N = 3, 6 and runtime N
         // Observation rows stored row-per-lane, or as one contiguous block per wave (stream_write_obs_block): the
@@ -369,8 +367,7 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
             if (dp.quad >= 0) quad = quad_ok && dp.quad != 0;
             if (every_step_resets) quad = false;
             if (quad) {
-                const size_t qshm = 4 * kWave * sizeof(float4) + 2 * 4 * 6 * 6 * sizeof(float2) + 2 * kWave * sizeof(float) +
-                                    8 * 6 * sizeof(float2) + 2 * kQuadActRingBytes + 2 * 8 * sizeof(float2);
+                const size_t qshm = spread_quad_lds().bytes;
                 const bool k1 = h->fc.k1 != 0;  // the canonical margin 1e-3 qualifies
                 if (wc && k1) PW_LAUNCH(h, (pw_spread_quad_kernel<true, true, true>), dim3(qgrid), dim3(4 * kWave), qshm, st, A, T);
                 else if (wc) PW_LAUNCH(h, (pw_spread_quad_kernel<true, true>), dim3(qgrid), dim3(4 * kWave), qshm, st, A, T);
@@ -384,8 +381,7 @@ int launch_rollout(pw_handle *h, const pw_step_io *io, int T, void *stream)
         // per CU); once every SIMD holds several waves the single-wave kernel issues fewer instructions
         const bool duo = !every_step_resets && (dp.duo < 0 ? grid.x <= 8192 : dp.duo != 0);
         if (duo) {
-            const size_t shm2 = 3 * kWave * sizeof(float4) + (size_t)kp.epw * kp.L * sizeof(float2) +
-                                2 * kWave * sizeof(float) + 16 + kWave * sizeof(float4) + 16 * sizeof(float2) + kActRingBytes;   // .. utab + zero (padded), action ring
+            const size_t shm2 = spread_duo_lds(kp.epw, kp.L).bytes;
             // three waves per env group (the output wave split in two) where the single output wave is the step's critical
             // path: block-store instantiations on mid-size grids (measured: profiles/r2_trio.txt).  pw_dispatch.trio overrides.
             // (only the compile-time instantiations below have the three-wave form: a runtime-N launch stays two waves wide)
@@ -502,7 +498,7 @@ int launch_aux(pw_handle *h, int mode, const uint8_t *env_mask, float *obs, floa
         return PW_OK;
     }
     const dim3 grid((kp.B + kp.epw - 1) / kp.epw), block(kWave);
-    const size_t shmem = smem_bytes(kp);
+    const size_t shmem = smem_lds(kp.epw, kp.N, kp.L).bytes;
     return dispatch(h, [&](auto scen, auto om) {
         hipLaunchKernelGGL((pw_aux_kernel<decltype(scen)::value, decltype(om)::value>), grid, block, shmem,
                            static_cast<hipStream_t>(stream), kp, mode, env_mask, obs, rew, coll);

@@ -13,7 +13,7 @@ int critic_launch(const CriticArgs &C, hipStream_t stream)
 {
     static unsigned long long optin_mask = 0;
     const auto kernel = pw_critic_forward_kernel<KO, KA>;
-    const size_t lds = critic_lds_bytes(C.N, C.R);
+    const size_t lds = critic_lds(C.N, C.R).bytes;
     PW_LDS_OPTIN(&optin_mask, kernel);
     const long groups = (C.b + C.R - 1) / C.R;
     hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);

@@ -110,7 +110,7 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
     hipStream_t st = static_cast<hipStream_t>(stream);
     // N <= 16: the BiLSTM on v_mfma_f32_16x16x4_f32 (pw_kernels_actor16.hpp), 16 environments per workgroup whatever N is; same
     // bits as the kernel below, which keeps the long sequences (its 96-row workgroups hold N <= 96)
-    const size_t shm16 = actor16_lds_floats(N, 16 * N, S1) * sizeof(float);
+    const size_t shm16 = actor16_lds(N, 16 * N, S1).bytes;
     if (N <= 16 && shm16 <= 160 * 1024) {
         a.E = 16;
         const unsigned grid16 = (unsigned)((B + 15) / 16);
@@ -130,7 +130,7 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
         return PW_OK;
     }
     if (a.bf16x3) return fail(PW_EINVAL, "pw_actor_set_bf16x3 serves N <= 16 only");
-    const size_t shm = actor_lds_bytes(S1);
+    const size_t shm = actor_lds(S1).bytes;
     const unsigned grid = (unsigned)((B + a.E - 1) / a.E);
     static unsigned long long attr_set[9] = {};  // per kernel: bit = device
 #define PW_FUSED(C)                                                                                                      \
@@ -180,8 +180,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         R.done = io->done; R.terminal = io->terminal;
         const int rS1C = (kp.D + 7) / 8;
         if (rS1C != 3) return fail(PW_EINVAL, "simple_reference one-launch rollout: the observation is 21 numbers (3 landmarks)");
-        const size_t rshm = actor16_lds_floats(2, 32, 4 * rS1C) * sizeof(float) + (size_t)2 * kFusedRows * kp.D * sizeof(float) + 2 * kFusedRows * sizeof(int32_t) +
-                            16 * (sizeof(double) + sizeof(int)) + (size_t)actor16_noise_floats(32, 5 + PW_DIM_C) * sizeof(float);
+        const size_t rshm = policy_ref_lds(4 * rS1C, kp.D, R.A.E).bytes;
         sink_into(R, sink);
         if (sink) {
             static unsigned long long attr_sets = 0; /* bit = device */
@@ -232,7 +231,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         Q.T = num_steps; Q.act_out = act_out;
         sink_into(Q, sink);
         const int tS1C = (kp.D + 7) / 8;
-        const size_t tshm = policy_tag_lds_bytes(4 * tS1C, kp.D, qa.E, kp.L, kp.N);
+        const size_t tshm = policy_tag_lds(4 * tS1C, kp.D, qa.E, kp.L, kp.N).bytes;
         if (tshm > 160 * 1024 || tS1C < 2 || tS1C > 6)
             return fail(PW_EINVAL, "simple_tag one-launch rollout: observation length must be in [9, 48] and fit the LDS");
         const unsigned tgrid = (unsigned)((kp.B + qa.E - 1) / qa.E);
@@ -271,7 +270,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         return fail(PW_EINVAL, "policy_form 1 / 2 (the first two rollout kernels) were retired in 0.1.5; use 0 (automatic), 3 or 4");
     int E3 = 0;
     for (int e = kp.B < 16 ? kp.B : 16; e >= 1; --e)  // 16 MFMA columns = 16 environments whatever N is (no 96-row limit here)
-        if (roll3_lds_bytes(e, kp.N, kp.L, kp.D, S1) <= 160 * 1024) { E3 = e; break; }
+        if (roll3_lds(e, kp.N, kp.L, kp.D, S1).bytes <= 160 * 1024) { E3 = e; break; }
     const int full = kp.B < 16 ? kp.B : 16;     // environments per workgroup that fill the 16 MFMA columns
     bool use_v3 = form == 3 ? E3 > 0 : form == 0 && E3 >= full;
     // Long agent axes: the third form with dense1 just in time and no observation rows in LDS (pw_kernels_policy3j.hpp) keeps 16
@@ -290,14 +289,14 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         if (!halfj) {
             const int ecap = 8 * (kWave / kp.N) < want ? 8 * (kWave / kp.N) : want;
             for (int e = ecap; e >= 1; --e)
-                if (roll3j_lds_bytes(e, kp.N, kp.L, false) <= 160 * 1024) { E3j = e; break; }
+                if (roll3j_lds(e, kp.N, kp.L, false).bytes <= 160 * 1024) { E3j = e; break; }
         }
         if (S1C >= 7 && E3j < want) {
             for (int e = want; e > E3j; --e)
-                if (roll3j_lds_bytes(e, kp.N, kp.L, true) <= 160 * 1024) { E3j = e; halfj = true; break; }
+                if (roll3j_lds(e, kp.N, kp.L, true).bytes <= 160 * 1024) { E3j = e; halfj = true; break; }
         }
         // an odd LDS row stride (no bank conflicts between the sixteen sequences: pw_kernels_policy3j.hpp) wherever it costs no environment
-        if (E3j > 0 && roll3j_lds_bytes(E3j, kp.N | 1, kp.L, halfj) <= 160 * 1024) NPj = kp.N | 1;
+        if (E3j > 0 && roll3j_lds(E3j, kp.N | 1, kp.L, halfj).bytes <= 160 * 1024) NPj = kp.N | 1;
     }
     if (form == 4 && E3j == 0) return fail(PW_EINVAL, "policy_form 4 (just-in-time dense1) serves the local observation with L <= N");
     if (wide && (E3j == 0 || (form != 0 && form != 4)))
@@ -307,7 +306,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     if (!use_v3 && E3j > 0 && (form == 4 || wide || E3j >= (kp.B < 8 ? kp.B : 8))) {
         a.E = E3j;
         P.NP = NPj;
-        const size_t shmj = roll3j_lds_bytes(E3j, NPj, kp.L, halfj);
+        const size_t shmj = roll3j_lds(E3j, NPj, kp.L, halfj).bytes;
         const unsigned gridj = (unsigned)((kp.B + E3j - 1) / E3j);
 #define PW_R3J2(C, SK, HF)                                                                                               \
     do {                                                                                                                 \
@@ -333,7 +332,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
                                         : "the selected rollout form does not fit this configuration's observation rows in LDS (policy_form 0 chooses)");
     {
         a.E = E3;
-        const size_t shm2 = roll3_lds_bytes(E3, kp.N, kp.L, kp.D, S1);
+        const size_t shm2 = roll3_lds(E3, kp.N, kp.L, kp.D, S1).bytes;
         const unsigned grid2 = (unsigned)((kp.B + E3 - 1) / E3);
 #define PW_R24(C, NT, SK, BF)                                                                                            \
     do {                                                                                                                 \
@@ -451,7 +450,7 @@ int pw_actor_front(const float *X, const float *frag, const float *b1, const flo
     if ((reinterpret_cast<uintptr_t>(frag) | reinterpret_cast<uintptr_t>(G)) & 15)
         return fail(PW_EINVAL, "frag and G must be 16-byte aligned");
     const int S1C = (in_dim + 7) / 8, S1 = 4 * S1C;
-    const size_t shm = (size_t)8 * 2 * 4 * 64 * sizeof(float4) + (size_t)(2 * S1 * 64 + 64 + 256 + 4 * 32 * 33) * sizeof(float);
+    const size_t shm = actor_front_lds(S1).bytes;
     const long tiles = (rows + 127) / 128;
     hipStream_t st = static_cast<hipStream_t>(stream);
     static unsigned long long attr_set[9] = {};  // per kernel: bit = device
