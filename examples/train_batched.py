@@ -2,6 +2,7 @@
 """Entry script of the batched engine -- the counterpart of the reference's ``main.py:29-67``.
 
     python examples/train_batched.py --scenario simple_spread --envs 4096 --episodes 40960
+    python examples/train_batched.py --scenario simple_spread --agents 3 --full-observation --envs 256 --episodes 512
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train_batched.py --envs 4096
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_batched.py --backend gloo   (one GPU)
 
@@ -33,6 +34,11 @@ def main(argv=None):
     ap.add_argument('--scenario', action='append', help='simple_spread | simple_tag | simple_reference (repeatable)')
     ap.add_argument('--envs', type=int, default=4096, help='B per GPU')
     ap.add_argument('--agents', type=int, default=None, help='simple_spread: make_world(num_agents=n), scenarios.py:170')
+    ap.add_argument('--full-observation', action='store_true',
+                    help="simple_spread: upstream MPE's own observation (make_env(local_observation=False), scenarios.py:124); the rollout "
+                         'runs on the generic one-launch kernel and the ring keeps rows')
+    ap.add_argument('--policy-form', type=int, default=0,
+                    help='pw_dispatch.policy_form of the rollout: 0 automatic, 3 / 4 the simple_spread forms, 5 the generic form')
     ap.add_argument('--episodes', type=int, default=None, help='arglist.num_episodes (finished episodes over all envs of a rank)')
     ap.add_argument('--seeds', type=int, default=1, help='cnt in range(seeds), main.py:37')
     ap.add_argument('--chunk', type=int, default=100, help='batched env steps per launch')
@@ -106,8 +112,14 @@ def main(argv=None):
             kw = dict(n=args.agents) if scenario_name == 'simple_spread' and args.agents else {}
             if scenario_name == 'simple_tag':
                 kw = dict(num_adversaries=3, num_good=1) if args.agents is None else dict(num_adversaries=args.agents - 2, num_good=2)
+            if args.full_observation:
+                kw['local_observation'] = False
             env = make_batched_env(scenario_name, args.envs, auto_reset=True, max_episode_len=arglist.max_episode_len,
                                    seed=seed, env_id_base=rank * args.envs, **kw)
+            if args.policy_form:
+                env.set_dispatch(policy_form=args.policy_form)
+            # a STATE ring holds {vel, pos} + landmarks: enough for the local observation and simple_tag on the specialised rollout forms only
+            state_ok = scenario_name in ('simple_spread', 'simple_tag') and not args.full_observation and args.policy_form != 5
             dim_obs, dim_action, action_type = dims_from_env(env)             # main.py:51-58
             actor = ActorNetwork(input_dim=dim_obs, out_dim=dim_action)       # main.py:60-61
             n_act = sum(dim_action) if isinstance(dim_action, list) else dim_action
@@ -119,12 +131,12 @@ def main(argv=None):
                 broadcast_actor(actor, src=0)                                  # same initial weights on every rank
                 # state-only blocks (simple_spread, simple_tag) land in a STATE ring on the learner rank (rows rebuilt when a batch is
                 # sampled: a third of the ring writes); simple_reference travels on compact-row blocks into its two-head row ring
-                state_ring = scenario_name in ('simple_spread', 'simple_tag')
+                state_ring = state_ok
                 gather = FullTransitionGather(env, args.chunk, rank, world, dev, ring='state' if state_ring else 'rows')
                 gather.prime()
             hist = train_batched(env, actor, critic, Trainer, scenario_name, action_type, cnt=cnt, out_dir=args.out_dir,
                                  chunk=args.chunk, max_updates_per_chunk=args.max_updates_per_chunk, gather=gather,
-                                 ring='state' if (gather is None and scenario_name in ('simple_spread', 'simple_tag')) else 'rows',
+                                 ring='state' if (gather is None and state_ok) else 'rows',
                                  rank=rank, world=world, log=print if rank == 0 else (lambda *a: None))
             results.append((scenario_name, cnt, hist['stats']))
             if rank == 0:

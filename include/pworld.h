@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 108 /* 0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 109 /* 0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -199,7 +199,8 @@ typedef struct pw_dispatch {
     int32_t p_prio;        /* -1 auto; >= 0: issue-priority bits of the duo kernels' waves (2 bits per wave; simple_tag: 0 / 1) */
     int32_t envs_per_wave; /* 0 auto; n >= 1: envs per wave, clamped to 64 / N */
     int32_t policy_form;   /* 0 auto; 3: pw_policy_rollout3_kernel; 4: pw_policy_rollout3j_kernel; 1, 2: retired (PW_EINVAL)
-                            * (the third form with dense1 just in time: long agent axes, N <= 32) */
+                            * (the third form with dense1 just in time: long agent axes, N <= 32);
+                            * 5: pw_policy_rollout_generic_kernel on any simple_spread / simple_tag handle it fits */
 } pw_dispatch;
 int pw_dispatch_default(pw_dispatch *d);                    /* every choice automatic */
 int pw_set_dispatch(pw_handle *h, const pw_dispatch *d);    /* between launches; the bound state is untouched */
@@ -221,7 +222,7 @@ int pw_set_actor_precision(pw_handle *h, int32_t mode);
 int pw_get_actor_precision(const pw_handle *h);
 int pw_actor_set_bf16x3(int32_t on);   /* returns the previous value */
 
-/* Name of the device kernel the last pw_step / pw_rollout on this handle launched (a static string; "" before the
+/* Name of the device kernel the last pw_step / pw_rollout / pw_policy_rollout on this handle launched (a static string; "" before the
  * first launch).  The dispatcher picks a kernel per (scenario, N, L, B, outputs requested): measurement tools name the
  * dominant kernel from this, not from a table of their own. */
 const char *pw_rollout_kernel(const pw_handle *h);
@@ -503,12 +504,24 @@ typedef struct pw_rollout_sink {
  * 64] / b2 = dense2_1 and dense2_2 concatenated, one Gumbel-argmax per head exactly as pw_actor_fused(n_out0 = 5, n_out1 =
  * PW_DIM_C) -- and act_out [num_steps,B,N,2] = (movement, symbol); the ring sink must be the two-head ring (act_heads = 2, head widths
  * 5 | PW_DIM_C; 0.1.5 -- before, the chunk went into it with a second launch, pw_replay_add_rollout); results equal a loop of
- * pw_actor_fused + pw_step(act_idx, act_comm). */
+ * pw_actor_fused + pw_step(act_idx, act_comm).
+ * Every other simple_spread / simple_tag configuration pw_step serves (0.1.9: the full observation, L > N, landmark contact on
+ * simple_spread, per-agent sizes / accelerations / speed clamps, a simple_tag roster with one agent unlike its role, a handle with
+ * pw_dispatch.force_generic): the generic form, pw_policy_rollout_generic_kernel -- the arithmetic of pw_rollout_kernel, so the same
+ * bits as the pw_actor_fused + pw_step loop; one 5-logit head, exact float32 only, rows of at most 64 numbers, at most 96 rows and
+ * 160 KB of LDS per workgroup (pw_policy_generic_envs_per_workgroup; PW_EINVAL naming N and D otherwise); the sink takes the plain
+ * row ring only (a STATE, two-head or per-agent ring is PW_EINVAL).  Selected automatically for the handles the forms above refuse
+ * -- except handles whose agents differ within a role (size, acceleration, force scale or speed clamp unlike the role's first
+ * agent), which stay PW_EINVAL under automatic dispatch -- and on any simple_spread / simple_tag handle by pw_dispatch.policy_form = 5. */
 int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const float *b_ih, const float *w_hh_fw,
                       const float *w_hh_bw, const float *w2, const float *b2, int32_t relu_out, uint64_t seed,
                       uint64_t step, const int64_t *step_dev /* device, or NULL */, const pw_step_io *io,
                       int32_t *act_out, int32_t num_steps, const pw_rollout_sink *sink /* or NULL */, void *stream);
 size_t pw_policy_rollout_scratch_bytes(const pw_handle *h);
+/* Environments per 512-thread workgroup of the generic form for a configuration (host arithmetic only, no device): the largest
+ * E <= 16 with E * N <= 96 rows whose LDS layout fits 160 KB, or 0 when none does or the observation row is longer than 64 numbers
+ * (pw_policy_rollout then returns PW_EINVAL).  obs_mode applies to simple_spread, A (adversaries) to simple_tag. */
+int pw_policy_generic_envs_per_workgroup(int32_t scenario, int32_t obs_mode, int32_t N, int32_t L, int32_t A);
 
 /* Test hook: y[i] = f(x[i]) with the DEVICE implementation of one math primitive, so its bits can be compared
  * with a CPU implementation of pworld_math.h.  fn: 0 the kernels' fast correctly-rounded sqrt, 1 their

@@ -149,6 +149,7 @@ SIGNATURES = {
     'pw_policy_rollout': (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                        C.c_int32, C.c_void_p, C.c_void_p]),
     'pw_policy_rollout_scratch_bytes': (C.c_size_t, [C.c_void_p]),
+    'pw_policy_generic_envs_per_workgroup': (C.c_int, [C.c_int32] * 5),
     'pw_bilstm_forward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p]),
     'pw_actor_head': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p,

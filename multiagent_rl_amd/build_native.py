@@ -7,6 +7,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pworld_policy.hip'),
+        os.path.join(HERE, 'csrc', 'pworld_policy_generic.hip'),
         os.path.join(HERE, 'csrc', 'pworld_critic.hip'), os.path.join(HERE, 'csrc', 'pworld_optim.hip'),
         os.path.join(HERE, 'csrc', 'pworld_replay.hip')]
 OUT = os.path.join(HERE, 'libpworld.so')
@@ -58,7 +59,7 @@ def _stale(obj):
 
 def unit_sources(unit):
     """Every file translation unit `unit` ('pworld' = environment, 'pworld_policy' = actor and policy rollouts,
-    'pworld_critic' = the learner's critic forward, 'pworld_optim' = clip + Adam + soft update, 'pworld_replay' = replay ring /
+    'pworld_policy_generic' = the generic one-launch policy rollout, 'pworld_critic' = the learner's critic forward, 'pworld_optim' = clip + Adam + soft update, 'pworld_replay' = replay ring /
     wire blocks) is compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
     sources (no compiler, no recorded paths), so it gives the same answer in any copy of the tree."""
     import re

@@ -8,9 +8,15 @@
 
 #include "pworld.h"
 
-// libpworld.so is five translation units (pworld.hip: environment; pworld_replay.hip: replay ring, wire blocks; pworld_policy.hip: actor,
-// policy rollouts; pworld_critic.hip; pworld_optim.hip).  The thread-local error text lives in pworld.hip; all reach it through this hook.
+// libpworld.so is six translation units (pworld.hip: environment; pworld_replay.hip: replay ring, wire blocks; pworld_policy.hip: actor,
+// policy rollouts; pworld_policy_generic.hip: the generic policy rollout; pworld_critic.hip; pworld_optim.hip).  The thread-local error text lives in pworld.hip; all reach it through this hook.
 extern "C" __attribute__((visibility("hidden"))) void pw_internal_set_error(const char *msg);
+// pworld_policy_generic.hip: the launcher of pw_policy_rollout_generic_kernel; pw_policy_rollout (pworld_policy.hip) has checked the
+// handle, the weights, io and num_steps and hands everything else over.
+extern "C" __attribute__((visibility("hidden"))) int pw_internal_policy_rollout_generic(
+    pw_handle *h, const float *frag, const float *b1, const float *b_ih, const float *w_hh_fw, const float *w_hh_bw, const float *w2,
+    const float *b2, int32_t relu_out, uint64_t seed, uint64_t step, const int64_t *step_dev, const pw_step_io *io, int32_t *act_out,
+    int32_t num_steps, const pw_rollout_sink *sink, void *stream);
 
 namespace {
 

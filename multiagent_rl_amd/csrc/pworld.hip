@@ -707,7 +707,7 @@ int pw_set_dispatch(pw_handle *h, const pw_dispatch *d)
     if (!h || !d) return fail(PW_EINVAL, "null argument");
     if (d->struct_size != sizeof(pw_dispatch)) return fail(PW_EINVAL, "pw_dispatch.struct_size mismatch (ABI)");
     if (d->duo < -1 || d->duo > 1 || d->quad < -1 || d->quad > 1 || d->obs_block < -1 || d->obs_block > 1 || d->trio < -1 ||
-        d->trio > 1 || d->p_prio < -1 || d->p_prio > 0xFFFF || d->envs_per_wave < 0 || d->policy_form < 0 || d->policy_form > 4)
+        d->trio > 1 || d->p_prio < -1 || d->p_prio > 0xFFFF || d->envs_per_wave < 0 || d->policy_form < 0 || d->policy_form > 5)
         return fail(PW_EINVAL, "pw_dispatch field out of range");
     h->disp = *d;
     h->disp.force_generic = d->force_generic != 0;

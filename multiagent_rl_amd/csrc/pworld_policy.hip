@@ -5,6 +5,7 @@
 // Entry points are declared in include/pworld.h; the handle and the error text are shared with pworld.hip.
 #include "pw_handle.hpp"
 #include "pw_kernels_policy.hpp"
+#include "pw_policy_host.hpp"
 #include "pw_kernels_actor16.hpp"
 #include "pw_kernels_policy3.hpp"
 #include "pw_kernels_policy3j.hpp"
@@ -14,45 +15,6 @@
 namespace {
 
 int g_actor_bf16x3 = 0;  // process-wide, off unless pw_actor_set_bf16x3 turns it on (no environment reads)
-
-// The part of ActorFusedArgs every launch form fills the same way: weights, sizes, heads, Philox seed / step and the
-// environments per 96-row workgroup (the 16x16x4-core kernels override E).  X, H, logits, act and bf16x3 stay with the caller.
-ActorFusedArgs actor_args(const float *frag, const float *b1, const float *b_ih, const float *w_hh_fw, const float *w_hh_bw,
-                          const float *w2, const float *b2, int B, int N, int D, int relu_out, int n_out0, int n_out1,
-                          uint64_t seed, uint64_t step, const int64_t *step_dev)
-{
-    ActorFusedArgs a = {};
-    a.frag = frag; a.b1 = b1; a.bih = b_ih; a.whh_f = w_hh_fw; a.whh_r = w_hh_bw; a.w2 = w2; a.b2 = b2;
-    a.B = B; a.N = N; a.D = D; a.relu_out = relu_out; a.n_out0 = n_out0; a.n_out1 = n_out1;
-    a.E = 96 / N < 16 ? 96 / N : 16;
-    a.seed = seed; a.step = step; a.step_dev = step_dev;
-    return a;
-}
-
-// A rollout sink's ring has the rollout's row shape and room for the chunk of `rows` transitions from a valid cursor, and its
-// bookkeeping pointers come together.
-int sink_fits(const pw_rollout_sink *sink, int N, int D, int64_t rows)
-{
-    const pw_replay_store *ring = sink->ring;
-    if (ring && (ring->num_agents != N || ring->obs_dim != D || ring->capacity < 1 || sink->ring_start < 0 ||
-                 sink->ring_start >= ring->capacity || rows > ring->capacity))
-        return fail(PW_EINVAL, "ring sink: shape mismatch or the chunk does not fit the ring");
-    if (sink->episode_return && (!sink->finished_sum || !sink->finished_count || !sink->scratch))
-        return fail(PW_EINVAL, "bookkeeping needs episode_return, finished_sum, finished_count and scratch");
-    return PW_OK;
-}
-
-// The sink into the argument block of a one-launch rollout (PolicyRolloutArgs / PolicyRolloutTagArgs / PolicyRolloutRefArgs: the
-// same fields under the same names; the block is zeroed, so without a sink nothing is set).
-template <typename Args>
-void sink_into(Args &P, const pw_rollout_sink *sink)
-{
-    if (sink && sink->ring) { P.ring = *sink->ring; P.has_ring = 1; P.ring_start = sink->ring_start; }
-    if (sink && sink->episode_return) {
-        P.episode_return = sink->episode_return; P.finished_sum = sink->finished_sum;
-        P.finished_count = sink->finished_count; P.scratch = static_cast<unsigned long long *>(sink->scratch);
-    }
-}
 
 }  // namespace
 
@@ -198,9 +160,20 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         return PW_OK;
     }
     const bool tag = h->cfg.scenario == PW_SIMPLE_TAG && h->tag_fast;
+    // The generic form (pw_kernels_policy_generic.hpp, pworld_policy_generic.hip): whatever pw_rollout_kernel serves.  policy_form 5
+    // selects it on any simple_spread / simple_tag handle; automatically it takes the handles the specialised forms below refuse --
+    // except handles whose agents differ within a role, which stay refused under automatic dispatch (served under policy_form 5 only).
+    if (h->disp.policy_form == 5 || (h->disp.policy_form == 0 && !h->fast && !tag)) {
+        if (h->disp.policy_form == 0 && (h->cfg.scenario == PW_SIMPLE_SPREAD || h->cfg.scenario == PW_SIMPLE_TAG) && agents_differ_within_role(kp))
+            return fail(PW_EINVAL, "pw_policy_rollout under automatic dispatch serves homogeneous agents (simple_tag: homogeneous roles); "
+                                   "heterogeneous agents: select policy_form = 5");
+        return pw_internal_policy_rollout_generic(h, frag, b1, b_ih, w_hh_fw, w_hh_bw, w2, b2, relu_out, seed, step, step_dev, io, act_out,
+                                                  num_steps, sink, stream);
+    }
     if (!h->fast && !tag)
         return fail(PW_EINVAL, "pw_policy_rollout serves the simple_spread fast-path configurations (local observation, "
-                               "homogeneous agents, L <= N) and simple_tag with homogeneous roles");
+                               "homogeneous agents, L <= N) and simple_tag with homogeneous roles in forms 3 / 4; policy_form 0 or 5 "
+                               "reaches the generic form");
     // observation rows longer than 64 numbers (simple_spread N = L > 30) are served by the just-in-time form alone (D <= 104)
     const bool wide = kp.D > 64;
     if (kp.N > 64 || kp.D > 104) return fail(PW_EINVAL, "N must be <= 64 and the observation length <= 104");
@@ -267,7 +240,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     // nothing selected them.)  pw_dispatch.policy_form overrides the choice.
     const int form = h->disp.policy_form;
     if (form == 1 || form == 2)
-        return fail(PW_EINVAL, "policy_form 1 / 2 (the first two rollout kernels) were retired in 0.1.5; use 0 (automatic), 3 or 4");
+        return fail(PW_EINVAL, "policy_form 1 / 2 (the first two rollout kernels) were retired in 0.1.5; use 0 (automatic), 3, 4 or 5");
     int E3 = 0;
     for (int e = kp.B < 16 ? kp.B : 16; e >= 1; --e)  // 16 MFMA columns = 16 environments whatever N is (no 96-row limit here)
         if (roll3_lds(e, kp.N, kp.L, kp.D, S1).bytes <= 160 * 1024) { E3 = e; break; }

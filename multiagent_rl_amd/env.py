@@ -174,7 +174,8 @@ class BatchedParticleEnv(object):
 
     def set_dispatch(self, **fields):
         """Override the dispatcher's choices for this handle, e.g. ``set_dispatch(duo=0)`` (one-wave stream form),
-        ``set_dispatch(quad=1)``, ``set_dispatch(envs_per_wave=64)``; unnamed fields keep their current value."""
+        ``set_dispatch(quad=1)``, ``set_dispatch(envs_per_wave=64)``, ``set_dispatch(policy_form=5)`` (the generic one-launch policy
+        rollout on any simple_spread / simple_tag env it fits); unnamed fields keep their current value.  The library checks the ranges."""
         d = _lib.PwDispatch()
         check(self.lib.pw_get_dispatch(self._h, C.byref(d)))
         for k, v in fields.items():

@@ -329,9 +329,12 @@ class BatchedRollout(object):
         runs policy + sampling + env step for the whole chunk with observations / actions / world state resident on
         the CU, and writes the transitions straight into the replay ring and the episode statistics from the same
         kernel (``pw_rollout_sink``).  ``keep_outputs=True`` also materialises the chunk's [T, ...] step outputs
-        (``self.last_chunk``).  Needs a FusedActor and a simple_spread fast-path, homogeneous-role simple_tag or simple_reference env (the latter
-        with a ring built with ``act_heads=(5, dim_c)``); stores exactly what ``collect``
-        stores (statistics up to float64 summation order)."""
+        (``self.last_chunk``).  Needs a FusedActor and a simple_spread, simple_tag or simple_reference env (the latter with a ring built with
+        ``act_heads=(5, dim_c)``).  simple_spread on the fast path and simple_tag with homogeneous roles run on their specialised kernels
+        (row or STATE ring); every other configuration ``env.step`` serves -- the full observation, L > N, landmark contact,
+        ``dispatch=dict(force_generic=1)`` -- runs on the generic one-launch kernel with a plain row ring, rows of at most 64 numbers;
+        agents that differ within a role need ``env.set_dispatch(policy_form=5)``.  Stores exactly what ``collect`` stores (statistics up
+        to float64 summation order)."""
         assert self._graph is None and hasattr(self.policy, 'rollout')
         stats = (self.episode_return, self.finished_return_sum, self.finished_episodes)
         done_steps = 0

@@ -117,7 +117,9 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     block, the learner lives on rank 0.  ``make_rollout(env, actor, memory, seed) -> (fused_actor, batched_rollout)`` replaces
     the HIP pair (tests drive the control flow without a GPU).  ``ring='state'`` (single-rank form; simple_spread with the local
     observation, simple_tag): the rollout's ring sink fills a STATE ring -- {vel, pos} + the episode's landmarks per transition, a
-    third of the bytes -- and ``sample_index`` rebuilds the rows the learner trains on (bit-identical batches).  Returns the history
+    third of the bytes -- and ``sample_index`` rebuilds the rows the learner trains on (bit-identical batches).  Envs only the generic
+    one-launch rollout serves (the full observation, L > N, landmark contact on simple_spread, ``policy_form=5``) take ``ring='rows'``:
+    their rollout refuses a STATE ring.  Returns the history
     dict (with ``stats``: env-steps, updates, wall time)."""
     from .replay_buffer import ReplayBuffer
     cfg = _default_arglist if arglist is None else arglist

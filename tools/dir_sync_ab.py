@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of the per-direction hand-off (pw_dispatch.policy_form 5: the four waves of an LSTM direction meet through an LDS counter inside
+"""A/B of the per-direction hand-off (the removed experiment's pw_dispatch.policy_form 5 -- in the product 5 now names the generic rollout form: the four waves of an LSTM direction meet through an LDS counter inside
 the timestep loop) against form 3 (one workgroup barrier per timestep): bit-identity of every output of a 50-step launch, then us per
 batched step with the ring sink (policy_profile_run's method), interleaved repeats.  Needs the experiment applied first (it was measured and
 removed: `git apply tools/experiments/r5_dir_sync.patch`, rebuild), then   python3 tools/dir_sync_ab.py   (profiles/r5_policy_dir_sync.txt)"""
