@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 109 /* 0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 110 /* 0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -213,9 +213,10 @@ int pw_get_dispatch(const pw_handle *h, pw_dispatch *out);
  * comparison on the reference's weights (tests/test_gpu_engine.py), but sampled actions can differ from the exact form's.
  * Selected by this call only (no environment variable changes results: a process-wide switch would silently turn every "exact"
  * rollout of the process into this mode); never a default, never a headline figure.
- * Served by the simple_spread rollout in its third kernel form and by pw_actor_fused at N <= 16; anything else returns PW_EINVAL
- * rather than run in float32 unannounced.
- * pw_actor_set_bf16x3: the same switch for the handle-less pw_actor_fused (process-wide, off until set; N <= 16 only). */
+ * Served by the simple_spread rollout in its third kernel form and by pw_actor_fused at N <= 16 with rows of at most 64 numbers;
+ * anything else returns PW_EINVAL rather than run in float32 unannounced.
+ * pw_actor_set_bf16x3: the same switch for the handle-less pw_actor_fused (process-wide, off until set; N <= 16 and in_dim <= 64
+ * only: rows of 65 .. 104 numbers run on pw_actor_fused_kernel, which has no bf16x3 form). */
 #define PW_ACTOR_F32 0
 #define PW_ACTOR_BF16X3 1
 int pw_set_actor_precision(pw_handle *h, int32_t mode);
@@ -451,7 +452,9 @@ int pw_dense(const float *X, const float *W, const float *b, int64_t rows, int32
  * (v_mfma_f32_32x32x2_f32, exact float32): dense1 + F.relu + the input projections of both LSTM directions.
  * The weights are consumed in MFMA fragment order: pw_actor_front_pack writes that image (w1 [64,in_dim],
  * w_ih [256,64] = [W_ih; W_ih_reverse] row-major -> frag[pw_actor_front_pack_floats(in_dim)]) once per weight
- * update; b_ih [256] = b_ih + b_hh per direction. */
+ * update; b_ih [256] = b_ih + b_hh per direction.  in_dim in [1, 104] for pw_actor_front_pack and pw_actor_front
+ * (pw_actor_front_kernel<ceil(in_dim / 8)>, 13 instantiations); the image of a given in_dim serves pw_actor_front,
+ * pw_actor_fused and pw_policy_rollout alike. */
 size_t pw_actor_front_pack_floats(int32_t in_dim);
 int pw_actor_front_pack(const float *w1, const float *w_ih, int32_t in_dim, float *frag, void *stream);
 int pw_actor_front(const float *X, const float *frag, const float *b1, const float *b_ih, int64_t rows, int32_t in_dim,
@@ -467,7 +470,9 @@ int pw_actor_head(const float *H, const float *w2, const float *b2, int64_t rows
  * the two layers concatenated, logits [B,N,n_out0+n_out1] in that order (run.py:39-41), act [B,N,2].
  * n_out0 + n_out1 <= 16.  With n_out0 = 5, n_out1 = 0: same arithmetic and the same Philox keying as
  * pw_actor_front + pw_bilstm_forward + pw_actor_head chained (identical results); G and H stay in LDS.
- * frag = pw_actor_front_pack's image; N <= 96. */
+ * frag = pw_actor_front_pack's image; N <= 96, in_dim in [1, 104].  Kernels: N <= 16 with in_dim <= 64 runs
+ * pw_actor_fused16_kernel (16 environments per workgroup), everything else -- N = 17 .. 96, and every in_dim of
+ * 65 .. 104 whatever N is -- pw_actor_fused_kernel (min(16, 96 / N) environments per workgroup); same bits. */
 int pw_actor_fused(const float *X, const float *frag, const float *b1, const float *b_ih, const float *w_hh_fw,
                    const float *w_hh_bw, const float *w2, const float *b2, int32_t n_out0, int32_t n_out1, int64_t B,
                    int32_t N, int32_t in_dim, int32_t relu_out, uint64_t seed, uint64_t step,

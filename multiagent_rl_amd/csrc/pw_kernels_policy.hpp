@@ -360,7 +360,8 @@ __global__ void __launch_bounds__(256) pw_actor_head_kernel(const float *__restr
 //             MultiDiscrete actor, main.py:52-54: act [rows, 2]).
 // Same arithmetic, in the same order, as pw_actor_front_kernel + pw_bilstm_kernel + pw_actor_head_kernel
 // (the tests demand identical bits); what is removed is the HBM round trip of G (1 KB per row, twice), of H,
-// and two launches.  LDS: 6-16 KB stage-1 fragments + 32 + 16 + 48.4 (Gs) + 25.5 (Hs) + 7 KB small = <= 145 KB.
+// and two launches.  LDS: 2-16 KB stage-1 fragments + 32 + 16 + 48.4 (Gs) + 25.5 (Hs) + 7 KB small = <= 145 KB for rows of at most
+// 64 numbers (S1C <= 8); rows of 65 .. 104 numbers (S1C = 9 .. 13) take 18-26 KB of stage-1 fragments: 155.2 KB at S1C = 13.
 // ------------------------------------------------------------------------------------------
 struct ActorFusedArgs {
     const float *X, *frag, *b1, *bih, *whh_f, *whh_r, *w2, *b2;
@@ -438,13 +439,16 @@ __device__ __forceinline__ void actor_forward_wg(const ActorFusedArgs &A, const 
     const int rt = wave < 4 ? wave >> 1 : 2;
     const int n_lo = wave < 4 ? (wave & 1) * 2 : wave - 4, n_cnt = wave < 4 ? 2 : 1;
     const bool front = rt * 32 < rows_here;  // wave-uniform
-    float xb[S1];  // this lane's stage-1 B operands, requested before the weights so that the loads overlap the fill
+    // rows longer than 64 numbers (S1C > 8): the B operands come in two batches -- the first 32 k-steps here, the rest right before the
+    // first batch's MFMAs -- so that no more than a row of 64 numbers' worth of them waits through the weight fill
+    constexpr int SA = S1C > 8 ? 32 : S1;
+    float xb[SA];  // this lane's stage-1 B operands, requested before the weights so that the loads overlap the fill
     {
         int lr = rt * 32 + col;
         if (lr >= rows_here) lr = rows_here - 1;
         const float *xr = xrows + (size_t)lr * A.D;
 #pragma unroll
-        for (int sidx = 0; sidx < S1; ++sidx) {
+        for (int sidx = 0; sidx < SA; ++sidx) {
             const int k = 2 * sidx + half;
             xb[sidx] = k < A.D ? xr[k] : 0.0f;
         }
@@ -469,11 +473,39 @@ __device__ __forceinline__ void actor_forward_wg(const ActorFusedArgs &A, const 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc1[m][r] = 0.0f;
     if (front) {
+        if constexpr (S1C > 8) {
+            // second batch: k-steps SA .. S1 - 1, the loads issued before the first batch's MFMAs; one accumulator chain per tile, k
+            // ascending through both batches -- the order of the single loop below
+            float xc[S1 - SA];
+            {
+                int lr = rt * 32 + col;
+                if (lr >= rows_here) lr = rows_here - 1;
+                const float *xr = xrows + (size_t)lr * A.D;
 #pragma unroll
-        for (int sidx = 0; sidx < S1; ++sidx) {
+                for (int sidx = SA; sidx < S1; ++sidx) {
+                    const int k = 2 * sidx + half;
+                    xc[sidx - SA] = k < A.D ? xr[k] : 0.0f;
+                }
+            }
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
-                acc1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(S.f_w1[(m * S1 + sidx) * 64 + lane], xb[sidx], acc1[m], 0, 0, 0);
+            for (int sidx = 0; sidx < SA; ++sidx) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+                    acc1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(S.f_w1[(m * S1 + sidx) * 64 + lane], xb[sidx], acc1[m], 0, 0, 0);
+            }
+#pragma unroll
+            for (int sidx = SA; sidx < S1; ++sidx) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+                    acc1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(S.f_w1[(m * S1 + sidx) * 64 + lane], xc[sidx - SA], acc1[m], 0, 0, 0);
+            }
+        } else {
+#pragma unroll
+            for (int sidx = 0; sidx < S1; ++sidx) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+                    acc1[m] = __builtin_amdgcn_mfma_f32_32x32x2f32(S.f_w1[(m * S1 + sidx) * 64 + lane], xb[sidx], acc1[m], 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int m = 0; m < 2; ++m)

@@ -62,18 +62,19 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
     if (!X || !frag || !b1 || !b_ih || !w_hh_fw || !w_hh_bw || !w2 || !b2 || (!H && !logits && !act))
         return fail(PW_EINVAL, "null argument");
     if (B < 1 || N < 1 || N > 96 || B > (int64_t)0x7fffffff) return fail(PW_EINVAL, "N must be in [1, 96]");
-    if (in_dim < 1 || in_dim > 64) return fail(PW_EINVAL, "in_dim must be in [1, 64]");
+    if (in_dim < 1 || in_dim > 104) return fail(PW_EINVAL, "pw_actor_fused: in_dim must be in [1, 104]");
     if ((reinterpret_cast<uintptr_t>(frag) | reinterpret_cast<uintptr_t>(w_hh_fw) | reinterpret_cast<uintptr_t>(w_hh_bw)) & 15)
         return fail(PW_EINVAL, "frag and w_hh must be 16-byte aligned");
     ActorFusedArgs a = actor_args(frag, b1, b_ih, w_hh_fw, w_hh_bw, w2, b2, (int)B, N, in_dim, relu_out, n_out0, n_out1, seed, step, step_dev);
     a.X = X; a.H = H; a.logits = logits; a.act = act;
-    a.bf16x3 = g_actor_bf16x3;  // honoured by the 16x16x4-core kernel (N <= 16) only
+    a.bf16x3 = g_actor_bf16x3;  // honoured by the 16x16x4-core kernel (N <= 16, in_dim <= 64) only
     const int S1C = (in_dim + 7) / 8, S1 = 4 * S1C;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // N <= 16: the BiLSTM on v_mfma_f32_16x16x4_f32 (pw_kernels_actor16.hpp), 16 environments per workgroup whatever N is; same
-    // bits as the kernel below, which keeps the long sequences (its 96-row workgroups hold N <= 96)
+    // N <= 16 and rows of at most 64 numbers: the BiLSTM on v_mfma_f32_16x16x4_f32 (pw_kernels_actor16.hpp), 16 environments per
+    // workgroup whatever N is; same bits as the kernel below, which keeps the long sequences (its 96-row workgroups hold N <= 96) and
+    // every row of 65 .. 104 numbers whatever N is (the 16-wide kernel's row block in LDS does not hold those in general)
     const size_t shm16 = actor16_lds(N, 16 * N, S1).bytes;
-    if (N <= 16 && shm16 <= 160 * 1024) {
+    if (N <= 16 && in_dim <= 64 && shm16 <= 160 * 1024) {
         a.E = 16;
         const unsigned grid16 = (unsigned)((B + 15) / 16);
 #define PW_FUSED16B(C, BF)                                                                                               \
@@ -91,10 +92,12 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
         PW_HIP_CHECK(hipGetLastError());
         return PW_OK;
     }
-    if (a.bf16x3) return fail(PW_EINVAL, "pw_actor_set_bf16x3 serves N <= 16 only");
+    if (a.bf16x3)
+        return fail(PW_EINVAL, in_dim > 64 ? "pw_actor_set_bf16x3 serves in_dim <= 64 only: rows of 65 .. 104 numbers run on pw_actor_fused_kernel, which has no bf16x3 form"
+                                           : "pw_actor_set_bf16x3 serves N <= 16 only");
     const size_t shm = actor_lds(S1).bytes;
     const unsigned grid = (unsigned)((B + a.E - 1) / a.E);
-    static unsigned long long attr_set[9] = {};  // per kernel: bit = device
+    static unsigned long long attr_set[14] = {};  // per kernel (indexed by S1C = 1 .. 13): bit = device
 #define PW_FUSED(C)                                                                                                      \
     case C:                                                                                                              \
         PW_LDS_OPTIN(&attr_set[C], (pw_actor_fused_kernel<C>)); \
@@ -102,6 +105,7 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
         break;
     switch (S1C) {
         PW_FUSED(1) PW_FUSED(2) PW_FUSED(3) PW_FUSED(4) PW_FUSED(5) PW_FUSED(6) PW_FUSED(7) PW_FUSED(8)
+        PW_FUSED(9) PW_FUSED(10) PW_FUSED(11) PW_FUSED(12) PW_FUSED(13)   // in_dim 65 .. 104
     }
 #undef PW_FUSED
     PW_HIP_CHECK(hipGetLastError());
@@ -403,9 +407,9 @@ size_t pw_actor_front_pack_floats(int32_t in_dim) { return actor_frag16_offset((
 int pw_actor_front_pack(const float *w1, const float *w_ih, int32_t in_dim, float *frag, void *stream)
 {
     if (!w1 || !w_ih || !frag) return fail(PW_EINVAL, "null argument");
-    // in_dim <= 64: every consumer; 65 .. 104: the W1 image is wider (S1 = 4 * ceil(in_dim / 8) k steps) and only the just-in-time
-    // rollout form (pw_policy_rollout3j_kernel: simple_spread up to N = L = 50) reads it
-    if (in_dim < 1 || in_dim > 104) return fail(PW_EINVAL, "in_dim must be in [1, 104]");
+    // in_dim <= 64: every consumer; 65 .. 104: the W1 image is wider (S1 = 4 * ceil(in_dim / 8) k steps); pw_actor_fused_kernel,
+    // pw_actor_front_kernel and the just-in-time rollout form (pw_policy_rollout3j_kernel: simple_spread up to N = L = 50) read it
+    if (in_dim < 1 || in_dim > 104) return fail(PW_EINVAL, "pw_actor_front_pack: in_dim must be in [1, 104]");
     if ((reinterpret_cast<uintptr_t>(w_ih) | reinterpret_cast<uintptr_t>(frag)) & 15)
         return fail(PW_EINVAL, "w_ih and frag must be 16-byte aligned");
     const unsigned w1_threads = 2u * (unsigned)(((in_dim + 7) >> 3) * 4) * 64u;   // the W1 section; the other two take 4096 threads
@@ -419,14 +423,14 @@ int pw_actor_front(const float *X, const float *frag, const float *b1, const flo
                    float *G, void *stream)
 {
     if (!X || !frag || !b1 || !b_ih || !G) return fail(PW_EINVAL, "null argument");
-    if (rows < 1 || in_dim < 1 || in_dim > 64) return fail(PW_EINVAL, "in_dim must be in [1, 64]");
+    if (rows < 1 || in_dim < 1 || in_dim > 104) return fail(PW_EINVAL, "pw_actor_front: rows >= 1, in_dim must be in [1, 104]");
     if ((reinterpret_cast<uintptr_t>(frag) | reinterpret_cast<uintptr_t>(G)) & 15)
         return fail(PW_EINVAL, "frag and G must be 16-byte aligned");
     const int S1C = (in_dim + 7) / 8, S1 = 4 * S1C;
     const size_t shm = actor_front_lds(S1).bytes;
     const long tiles = (rows + 127) / 128;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    static unsigned long long attr_set[9] = {};  // per kernel: bit = device
+    static unsigned long long attr_set[14] = {};  // per kernel (indexed by S1C = 1 .. 13): bit = device
 #define PW_FRONT(C)                                                                                                      \
     case C:                                                                                                              \
         PW_LDS_OPTIN(&attr_set[C], (pw_actor_front_kernel<C>)); \
@@ -435,6 +439,7 @@ int pw_actor_front(const float *X, const float *frag, const float *b1, const flo
         break;
     switch (S1C) {
         PW_FRONT(1) PW_FRONT(2) PW_FRONT(3) PW_FRONT(4) PW_FRONT(5) PW_FRONT(6) PW_FRONT(7) PW_FRONT(8)
+        PW_FRONT(9) PW_FRONT(10) PW_FRONT(11) PW_FRONT(12) PW_FRONT(13)   // in_dim 65 .. 104
     }
 #undef PW_FRONT
     PW_HIP_CHECK(hipGetLastError());

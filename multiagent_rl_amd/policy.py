@@ -91,6 +91,10 @@ class FusedActor(object):
     every intermediate in registers / LDS.  ``PW_ACTOR_NO_FUSE=1`` selects the same arithmetic as three launches
     (``pw_actor_front``, ``pw_bilstm_forward``, ``pw_actor_head`` -- identical results, also used when N > 96), and
     ``PW_ACTOR_NO_MFMA=1`` additionally replaces the front end by weight-stationary dense1 + a rocBLAS GEMM.
+
+    Observation rows hold up to 104 numbers (simple_spread's local rows up to N = 50) in the one-launch form and in the
+    three-launch chain alike; the ``PW_ACTOR_NO_MFMA=1`` front end (``pw_dense``) stops at 64 and raises
+    ``NotImplementedError`` beyond.
     """
 
     def __init__(self, actor, seed=0):
@@ -156,10 +160,14 @@ class FusedActor(object):
 
     @torch.no_grad()
     def hidden(self, obs):
-        """obs [B,N,D] -> relu(BiLSTM(relu(dense1(obs)))) [B,N,64]."""
+        """obs [B,N,D] -> relu(BiLSTM(relu(dense1(obs)))) [B,N,64].  D <= 104 (``PW_ACTOR_NO_MFMA=1``: D <= 64)."""
         B, N, D = obs.shape
         if self.use_fused and N <= 96:
             return self._fused(obs, want_h=True)[0]
+        if not self.use_mfma_front and D > 64:
+            raise NotImplementedError('PW_ACTOR_NO_MFMA=1: the weight-stationary dense1 (pw_dense) serves rows of at most 64 '
+                                      'numbers, got D = %d; unset the switch (PW_ACTOR_NO_FUSE=1 alone keeps the three-launch '
+                                      'chain, which serves D <= 104)' % D)
         x = obs.reshape(B * N, D).to(torch.float32).contiguous()
         p = lambda t: self._C.c_void_p(t.data_ptr())  # noqa: E731
         h = torch.empty(B, N, 64, dtype=torch.float32, device=self.device)

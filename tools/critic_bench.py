@@ -9,9 +9,13 @@ kernels, on the GPU (there is no fallback: without one this fails).
             no_grad -- the only way to y before pw_critic_forward existed;
 (b) fused:  FusedActor.logits (pw_actor_fused) + the same sampling + FusedCritic.td_target (pw_critic_forward with the epilogue).
 b = 1024 (the reference's batch), simple_spread's local rows D = 4 + 2 N, N in {3, 6, 12, 24, 48}; device events around ITERS
-calls after warm-up, five repeats per path, the two paths alternating.  The one-launch actor serves rows up to 64 numbers, so
-at N = 48 (D = 100) path (b) keeps the stock target actor and fuses the critic only; the table says so.
+calls after warm-up, five repeats per path, the two paths alternating.  The one-launch actor serves rows up to 104 numbers, so
+every row of the table, N = 48 (D = 100) included, runs FusedActor.logits for the target actor.
 Launch counts: kernels seen by torch.profiler in one call of each path.
+    python tools/critic_bench.py --wide [--out profiles/actor_wide_rows.txt]   # N = 48 alone: (a), (b) and the mix that served
+        N = 48 before the actor took rows longer than 64 numbers (stock target actor + pw_critic_forward), then the actor alone
+        (stock ActorNetwork forward against FusedActor.logits); exit status 1 if the mix is not slower than (b) by more than the
+        spread of the mix's repeats.
 Then the example learner (examples/madr_learner.py Trainer with the attention critic) at N = 6: wall time per optimize() with and
 without accelerate_trainer(targets=True), five repeats each, alternating.
 Exit status 1 if at N = 6 path (b) is not faster than path (a) by more than the spread (max - min) of (a)'s five repeats.
@@ -38,7 +42,7 @@ def make_paths(N, D):
     actor, critic = ActorNetwork(D, 5).cuda().eval(), CriticNetwork(D + 5, 1).cuda().eval()
     s1 = torch.randn(B, N, D, device='cuda')
     r, d = torch.randn(B, device='cuda'), (torch.rand(B, device='cuda') < 0.1).float()
-    fused_actor = FusedActor(actor) if D <= 64 else None
+    fused_actor = FusedActor(actor)
     fc = FusedCritic(critic)
 
     def sample(logits):
@@ -51,9 +55,20 @@ def make_paths(N, D):
 
     @torch.no_grad()
     def fused():
-        logits = fused_actor.logits(s1) if fused_actor is not None else actor(s1)
-        return fc.td_target(s1, sample(logits), r, d, GAMMA)
-    return stock, fused, fused_actor is not None
+        return fc.td_target(s1, sample(fused_actor.logits(s1)), r, d, GAMMA)
+
+    @torch.no_grad()
+    def mix():       # stock target actor + the fused critic
+        return fc.td_target(s1, sample(actor(s1)), r, d, GAMMA)
+
+    @torch.no_grad()
+    def actor_stock():
+        return actor(s1)
+
+    @torch.no_grad()
+    def actor_fused():
+        return fused_actor.logits(s1)
+    return stock, fused, dict(mix=mix, actor_stock=actor_stock, actor_fused=actor_fused)
 
 
 def device_time_us(fn, iters):
@@ -78,6 +93,43 @@ def launches(fn):
         return str(n) if n else 'n/a'
     except Exception as exc:   # the count is a by-product: the timings do not depend on the profiler
         return 'n/a (%s)' % type(exc).__name__
+
+
+def wide_rows(args):
+    """N = 48 (D = 100): the TD target on three paths and the actor alone, same method as the table."""
+    N, D = 48, 100
+    stock, fused, more = make_paths(N, D)
+    paths = [('(a) stock PyTorch-ROCm', stock), ('(m) stock target actor + pw_critic_forward', more['mix']),
+             ('(b) pw_actor_fused + sampling + pw_critic_forward', fused)]
+    actor_paths = [('stock ActorNetwork forward', more['actor_stock']), ('FusedActor.logits (pw_actor_fused)', more['actor_fused'])]
+    lines = []
+    for title, group in (('TD target of a batch', paths), ('the target actor alone, logits [b, N, 5]', actor_paths)):
+        for _ in range(20):
+            for _, fn in group:
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name, _ in group}
+        for _ in range(REPEATS):
+            for name, fn in group:
+                t[name].append(device_time_us(fn, args.iters))
+        lines.append('%s, N = %d, D = %d, b = %d: device-event us per call (%d calls per repeat, %d repeats, paths alternating)' % (
+            title, N, D, B, args.iters, REPEATS))
+        for name, fn in group:
+            v = t[name]
+            lines.append('  %-52s mean %8.1f  min %8.1f  max %8.1f  launches %-4s [%s]' % (
+                name, sum(v) / len(v), min(v), max(v), launches(fn), ' '.join('%.1f' % x for x in v)))
+        if group is paths:
+            m, b = t[paths[1][0]], t[paths[2][0]]
+            gain, spread = sum(m) / len(m) - sum(b) / len(b), max(m) - min(m)
+            ok = gain > spread
+            lines.append('  condition: (m) - (b) = %.1f us against the spread of (m)\'s repeats %.1f us: %s' % (
+                gain, spread, 'met' if ok else 'NOT met'))
+    text = '\n'.join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text + '\n')
+    return 0 if ok else 1
 
 
 def learner_times(lines, iters):
@@ -129,9 +181,12 @@ def main():
     ap.add_argument('--out', default=None)
     ap.add_argument('--kernel-only', action='store_true', help='200 fused TD targets at --agents and nothing else (for rocprofv3)')
     ap.add_argument('--agents', type=int, default=6, help='N of --kernel-only')
+    ap.add_argument('--wide', action='store_true', help='N = 48 (D = 100) alone: three TD-target paths and the actor alone')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('critic_bench: needs a GPU (no fallback)')
+    if args.wide:
+        return wide_rows(args)
     if args.kernel_only:
         fused = make_paths(args.agents, 4 + 2 * args.agents)[1]
         for _ in range(200):
@@ -145,7 +200,7 @@ def main():
     verdict = None
     for N in (3, 6, 12, 24, 48):
         D = 4 + 2 * N
-        stock, fused, whole = make_paths(N, D)
+        stock, fused, _ = make_paths(N, D)
         for _ in range(20):
             stock()
             fused()
@@ -156,8 +211,7 @@ def main():
             tb.append(device_time_us(fused, args.iters))
         ma, mb = sum(ta) / REPEATS, sum(tb) / REPEATS
         lines.append('%-4d %-5d %8.1f [%8.1f, %8.1f] %8s %8.1f [%8.1f, %8.1f] %8s %-8.2f %s | %s%s' % (
-            N, D, ma, min(ta), max(ta), '', mb, min(tb), max(tb), '', ma / mb, launches(stock), launches(fused),
-            '' if whole else '   (b: stock target actor, D > 64; critic fused)'))
+            N, D, ma, min(ta), max(ta), '', mb, min(tb), max(tb), '', ma / mb, launches(stock), launches(fused), ''))
         if N == 6:
             verdict = (ma - mb, max(ta) - min(ta))
     ok = verdict[0] > verdict[1]
