@@ -12,7 +12,9 @@ For every scenario and seed count ``cnt`` it does what main.py does -- build the
 ``multiagent_rl_amd.train.train_batched`` in the place of ``experiments.run.run``.  ``--reference`` takes the Trainer and the
 critic from the reference checkout on ``sys.path`` (``rls.agent.multiagent.ddpg_gumbel_fix``); otherwise the small stock-PyTorch
 learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).  ``--critic attention`` gives
-it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``), ``--fused-targets`` runs its target networks'
+it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``); ``--critic bicnet`` is the BiCNet baseline: per-agent
+transitions (``train_batched(per_agent_transition=True)``), ``multiagent_rl_amd.critic.BiCNetCritic`` and the per-agent stand-in learner
+(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only.  ``--fused-targets`` runs its target networks'
 forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
 soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch, or ``accelerate_trainer(.., optimizer=True)`` with
 ``--reference``).
@@ -49,18 +51,22 @@ def main(argv=None):
                     help='process group of a multi-rank run: nccl (= RCCL, one GPU per rank) or gloo (the blocks of the full gather '
                          'travel through pinned host buffers; ranks may share a GPU -- RCCL refuses that)')
     ap.add_argument('--reference', action='store_true', help="use the reference's Trainer / CriticNetwork (rls on sys.path)")
-    ap.add_argument('--critic', default='standin', choices=['standin', 'attention'],
+    ap.add_argument('--critic', default='standin', choices=['standin', 'attention', 'bicnet'],
                     help="standin: madr_learner's mean-pooling critic; attention: multiagent_rl_amd.critic.CriticNetwork, the "
-                         "reference's LSTM + attention architecture (its saved *_critic.pt files load into it)")
+                         "reference's LSTM + attention architecture (its saved *_critic.pt files load into it); bicnet: the BiCNet "
+                         'baseline -- one Q per agent (multiagent_rl_amd.critic.BiCNetCritic) and per-agent transitions')
     ap.add_argument('--fused-targets', action='store_true',
                     help='target actor and target critic of the learner run on the HIP kernels (accelerate_trainer(.., targets=True); '
-                         'needs the attention critic)')
+                         'needs the attention or the bicnet critic)')
     ap.add_argument('--fused-optimizer', action='store_true',
                     help="each network's gradient clip + Adam step + soft update is one HIP launch (madr_learner's fused_optimizer "
                          'switch; with --reference: accelerate_trainer(.., optimizer=True))')
     args = ap.parse_args(argv)
-    if args.fused_targets and args.critic != 'attention' and not args.reference:
-        ap.error('--fused-targets needs --critic attention (the HIP critic is the LSTM + attention architecture)')
+    if args.fused_targets and args.critic not in ('attention', 'bicnet') and not args.reference:
+        ap.error('--fused-targets needs --critic attention or --critic bicnet (the HIP critics are the LSTM architectures)')
+    bicnet = args.critic == 'bicnet'
+    if bicnet and int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        ap.error('--critic bicnet is single-rank: the multi-rank gather carries the shared reward only')
 
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')   # dmabuf IPC for multi-process GPU work (read at the first GPU call)
     import torch
@@ -68,9 +74,15 @@ def main(argv=None):
     from multiagent_rl_amd import arglist, make_batched_env
     from multiagent_rl_amd.policy import ActorNetwork
     from multiagent_rl_amd.train import dims_from_env, seed_everything, train_batched
-    if args.reference:
+    if args.reference and bicnet:
+        from rls.agent.multiagent.BIC_gumbel_fix import Trainer
+        from rls.model.ac_network_multi_gumbel_BIC import CriticNetwork
+    elif args.reference:
         from rls.agent.multiagent.ddpg_gumbel_fix import Trainer
         from rls.model.ac_network_multi_gumbel import CriticNetwork
+    elif bicnet:
+        from madr_learner import BiCNetTrainer as Trainer
+        from multiagent_rl_amd.critic import BiCNetCritic as CriticNetwork
     else:
         from madr_learner import CriticNetwork, Trainer
         if args.critic == 'attention':
@@ -119,7 +131,7 @@ def main(argv=None):
             if args.policy_form:
                 env.set_dispatch(policy_form=args.policy_form)
             # a STATE ring holds {vel, pos} + landmarks: enough for the local observation and simple_tag on the specialised rollout forms only
-            state_ok = scenario_name in ('simple_spread', 'simple_tag') and not args.full_observation and args.policy_form != 5
+            state_ok = scenario_name in ('simple_spread', 'simple_tag') and not args.full_observation and args.policy_form != 5 and not bicnet
             dim_obs, dim_action, action_type = dims_from_env(env)             # main.py:51-58
             actor = ActorNetwork(input_dim=dim_obs, out_dim=dim_action)       # main.py:60-61
             n_act = sum(dim_action) if isinstance(dim_action, list) else dim_action
@@ -137,7 +149,7 @@ def main(argv=None):
             hist = train_batched(env, actor, critic, Trainer, scenario_name, action_type, cnt=cnt, out_dir=args.out_dir,
                                  chunk=args.chunk, max_updates_per_chunk=args.max_updates_per_chunk, gather=gather,
                                  ring='state' if (gather is None and state_ok) else 'rows',
-                                 rank=rank, world=world, log=print if rank == 0 else (lambda *a: None))
+                                 rank=rank, world=world, log=print if rank == 0 else (lambda *a: None), per_agent_transition=bicnet)
             results.append((scenario_name, cnt, hist['stats']))
             if rank == 0:
                 s = hist['stats']

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 110 /* 0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 111 /* 0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -287,7 +287,8 @@ int pw_replay_add_tail(const pw_replay_store *st, int64_t start, const int64_t *
 /* A whole rollout chunk (pw_policy_rollout / pw_rollout outputs, [T, ...]) into the ring in one launch: transition
  * (t, e) goes to slot (start + t*B + e) % capacity -- the order of T pw_replay_add calls -- with obs = obs0 [B,N,D]
  * for t = 0 and the chunk's obs[t-1] after that, next_obs = final_obs where terminal.  io needs obs, rew_shared,
- * terminal (final_obs optional); act [T,B,N] int32 ([T,B,N,2] for a two-head ring, st->act_heads = 2: the MultiDiscrete chunks
+ * terminal (final_obs optional; a per-agent ring, st->per_agent: also rew [T,B,N], required, and done [T,B,N] u8 or NULL = 0, which
+ * fill its [cap,N] planes -- the bookkeeping stays on rew_shared); act [T,B,N] int32 ([T,B,N,2] for a two-head ring, st->act_heads = 2: the MultiDiscrete chunks
  * of pw_policy_rollout on simple_reference).  episode_return / finished_sum / finished_count / scratch
  * (all or none): the chunk's episode-return bookkeeping, as T pw_episode_stats calls up to float64 summation
  * order (fixed, so reproducible); scratch = pw_replay_add_rollout_scratch_bytes(B) device bytes, zeroed once. */
@@ -554,6 +555,17 @@ int pw_critic_forward(const float *obs, const int32_t *act_idx, const float *act
                       const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
                       const float *rew /* or NULL */, const float *done /* or NULL */, float gamma, float *q,
                       float *y /* or NULL */, void *stream);
+
+/* The BiCNet baseline's critic (rls/model/ac_network_multi_gumbel_BIC.py CriticNetwork) and, optionally, the per-agent TD target of
+ * BIC_gumbel_fix.py:155-160 as ONE launch: q [b,N], q[r][t] = <w2, h_t[r]> + b2 on the LSTM's output of step t itself (no ReLU, no
+ * attention) -- front end, recurrence, action forms, weight layout (w2 [1,64] / b2 [1] = dense2.module) and every limit as
+ * pw_critic_forward.  With rew [b,N], done [b,N] (float) and y [b,N] (all three or none): y = rew + gamma * q * (1 - done) element-wise,
+ * left to right without contraction.  q[r][t] depends on agents 0 .. t of row r only (not on N). */
+int pw_critic_forward_steps(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
+                            const float *w1, const float *b1, const float *w_ih, const float *w_hh, const float *b_ih,
+                            const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
+                            const float *rew /* [b,N] or NULL */, const float *done /* [b,N] or NULL */, float gamma,
+                            float *q /* [b,N] */, float *y /* [b,N] or NULL */, void *stream);
 
 /* The tail of a network's update as ONE launch (csrc/pw_kernels_optim.hpp states the float32 operation order):
  *   total_norm = sqrt(sum g^2) over ALL tensors of the call; coef = min(1, max_norm / (total_norm + 1e-6))   [torch.nn.utils.clip_grad_norm_]

@@ -10,6 +10,11 @@ dense2 in ONE launch instead of MIOpen's many-kernel RNN path, two ``bmm``s, a s
 ``Trainer.optimize`` that needs no gradient: ``q_next = target_critic(s1, a1)`` and ``y = r + GAMMA * q_next * (1 - d)``
 (``ddpg_gumbel_fix.py:148-154``).  ``accelerate_trainer(trainer, targets=True)`` hands both target networks of an unmodified
 Trainer to the HIP kernels.
+
+``BiCNetCritic`` is the baseline's critic (``rls/model/ac_network_multi_gumbel_BIC.py:69-141``): the same dense1 and LSTM, then
+``TimeDistributed(Linear(64, 1))`` on every step's output -- one Q per agent, ``[b, N, 1]``, no attention.  ``FusedCritic`` serves
+it with ``pw_critic_forward_steps`` (q and the per-agent TD target of ``BIC_gumbel_fix.py:155-160`` on ``[b, N]``); which of the
+two critics it wraps is read off the structure: ``dense2`` is a ``TimeDistributed`` there and a plain ``Linear`` here.
 """
 import torch
 import torch.nn as nn
@@ -40,8 +45,28 @@ class CriticNetwork(nn.Module):
         return self.dense2(F.relu(ctx))
 
 
+class BiCNetCritic(nn.Module):
+    """Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis -> TimeDistributed(Linear(64, out_dim)) on the LSTM's
+    output itself (no ReLU, no attention): one Q per agent.  Layer names as the reference's (``dense1.module``, ``lstm``,
+    ``dense2.module``).  ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``[b, N, out_dim]``."""
+
+    def __init__(self, input_dim, out_dim=1):
+        super().__init__()
+        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
+        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+        self.dense2 = TimeDistributed(nn.Linear(64, out_dim))
+
+    def forward(self, obs, action):
+        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
+        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
+        steps, _ = self.lstm(hid, None)
+        return self.dense2(steps)
+
+
 class FusedCritic(object):
-    """``critic`` (a ``CriticNetwork`` -- this module's or the reference's -- on the GPU) evaluated by ``pw_critic_forward``.
+    """``critic`` (a ``CriticNetwork`` or a ``BiCNetCritic`` -- this module's or the reference's -- on the GPU) evaluated by
+    ``pw_critic_forward`` / ``pw_critic_forward_steps``.  ``per_step`` says which: True where ``critic.dense2`` wraps its Linear in a
+    ``.module`` (the per-step critic: ``q`` / ``td_target`` are ``[b, N]``, ``forward`` ``[b, N, 1]``, ``rew`` / ``done`` ``[b, N]``).
 
     The kernel reads the parameters where the module keeps them (``nn.Module`` layout, no packed image), so every call computes
     with the module's CURRENT values: a soft update in place between two calls needs no ``refresh()``.  No gradient flows through
@@ -54,15 +79,21 @@ class FusedCritic(object):
         self._C, self._lib_mod, self.lib = C, _lib, _lib.load()
         self.critic = critic
         self.heads = None if heads is None else tuple(int(h) for h in heads)
-        lin1, lstm, lin2 = critic.dense1.module, critic.lstm, critic.dense2
+        self.per_step = not isinstance(critic.dense2, nn.Linear) and hasattr(critic.dense2, 'module')
+        lin1, lstm, lin2 = critic.dense1.module, critic.lstm, self._dense2()
         if not (lin1.out_features == 64 and lstm.input_size == 64 and lstm.hidden_size == 64 and lstm.num_layers == 1
                 and not lstm.bidirectional and lstm.batch_first and lin2.in_features == 64 and lin2.out_features == 1):
-            raise ValueError('FusedCritic serves Linear(D + A, 64) -> LSTM(64 -> 64) -> attention -> Linear(64, 1)')
+            raise ValueError('FusedCritic serves Linear(D + A, 64) -> LSTM(64 -> 64) -> attention -> Linear(64, 1) and the per-step '
+                             'form Linear(D + A, 64) -> LSTM(64 -> 64) -> TimeDistributed(Linear(64, 1)); other heads (e.g. the '
+                             "model-learning variant's dense3) are not served")
         self._params()
+
+    def _dense2(self):
+        return self.critic.dense2.module if self.per_step else self.critic.dense2
 
     def _params(self):
         c = self.critic
-        lin1, lstm, lin2 = c.dense1.module, c.lstm, c.dense2
+        lin1, lstm, lin2 = c.dense1.module, c.lstm, self._dense2()
         ps = (lin1.weight, lin1.bias, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, lin2.weight, lin2.bias)
         dev = ps[0].device
         if dev.type != 'cuda':
@@ -99,31 +130,39 @@ class FusedCritic(object):
                 n0, n1 = self.heads
             else:
                 raise ValueError('index action must be [b, N] or [b, N, 2], got %r' % (tuple(idx.shape),))
-        q = torch.empty(b, dtype=torch.float32, device=self.device)
+        shape = (b, N) if self.per_step else (b,)
+        q = torch.empty(shape, dtype=torch.float32, device=self.device)
         y = r = d = None
         if rew is not None:
-            r, d = f32(rew).reshape(-1), f32(done).reshape(-1)
-            if r.numel() != b or d.numel() != b:
-                raise ValueError('rew and done must hold one number per batch row')
-            y = torch.empty(b, dtype=torch.float32, device=self.device)
+            if self.per_step:
+                if tuple(rew.shape) != shape or tuple(done.shape) != shape:
+                    raise ValueError('the per-step critic takes per-agent rew and done of shape [b, N] = %r, got %r and %r' % (
+                        shape, tuple(rew.shape), tuple(done.shape)))
+                r, d = f32(rew), f32(done)
+            else:
+                r, d = f32(rew).reshape(-1), f32(done).reshape(-1)
+                if r.numel() != b or d.numel() != b:
+                    raise ValueError('rew and done must hold one number per batch row')
+            y = torch.empty(shape, dtype=torch.float32, device=self.device)
         p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
         stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        self._lib_mod.check(self.lib.pw_critic_forward(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D,
-                                                       p(r), p(d), float(gamma), p(q), p(y), stream))
+        entry = self.lib.pw_critic_forward_steps if self.per_step else self.lib.pw_critic_forward
+        self._lib_mod.check(entry(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d), float(gamma), p(q), p(y), stream))
         return q, y
 
     def q(self, obs, act):
-        """obs [b,N,D]; act int [b,N] / [b,N,2] (indices) or float [b,N,A] -> q [b]."""
+        """obs [b,N,D]; act int [b,N] / [b,N,2] (indices) or float [b,N,A] -> q [b] ([b,N] for the per-step critic)."""
         return self._run(obs, act)[0]
 
     def td_target(self, next_obs, act, rew, done, gamma, return_q=False):
-        """-> y [b] = rew + gamma * q(next_obs, act) * (1 - done) from one launch (``return_q``: also that launch's q)."""
+        """-> y [b] = rew + gamma * q(next_obs, act) * (1 - done) from one launch (``return_q``: also that launch's q).  The per-step
+        critic: rew, done and y are per agent, [b,N]."""
         q, y = self._run(next_obs, act, rew, done, gamma)
         return (y, q) if return_q else y
 
     def forward(self, obs, action):
-        """As the module: ``[b, 1]``; a list of action tensors is concatenated along the last axis."""
-        return self._run(obs, action)[0].unsqueeze(1)
+        """As the module: ``[b, 1]`` (``[b, N, 1]`` for the per-step critic); a list of action tensors is concatenated along the last axis."""
+        return self._run(obs, action)[0].unsqueeze(-1)
 
     __call__ = forward
 

@@ -21,6 +21,20 @@
 //     statistics redundantly per wave in registers, the context of a lane's own two units, dense2 as a two-stage reduction.
 // LDS: N R 256 bytes of step outputs + 4 x1 buffers (R KB) + scores: R = 16 serves N <= 32 (146.5 KiB at N = 32), longer agent axes
 // run 8 rows per workgroup (columns 8 .. 15 of the tiles idle; 140.5 KiB at N = 64).  Nothing between the input rows and q touches HBM.
+//
+// The per-step critic (rls/model/ac_network_multi_gumbel_BIC.py CriticNetwork, the BiCNet baseline) is the same front end and
+// recurrence with a head on every step's output instead of the attention: q[r][t] = <w2, h_t[r]> + b2 (no ReLU), and the TD
+// target per agent.  It is the third template parameter of the one kernel (pw_critic_forward_kernel<KO, KA, STEPS>), not a copy:
+//   * only h_{t-1} and h_t are live, so the step outputs are a TWO-slot ring (slot t & 1) and R = 16 rows per workgroup serve
+//     every N <= 64 (critic_steps_lds: 8 KB of step outputs + 16 KB of x1 buffers + the q staging, 28 KB at N = 64);
+//   * the head runs IN the loop: during step t + 1 wave t % 8 forms q_t from the B fragments of h_t every wave has just read for
+//     the recurrence (its own 16 units in ascending order, then the two lane_xor exchanges: a fixed order that does not depend on
+//     N), behind the step's matrix instructions; the last step's head follows the loop.  q_t is staged in LDS as [row][N] so that q
+//     (and y) leave at the end in whole [row][0 .. N) runs -- the workgroup's rows are one contiguous run of rows_here * N floats
+//     -- instead of 16 scattered 4-byte stores per step.  (Chosen from the store pattern, not from a measurement: per-step
+//     stores were not timed.)
+//   INVARIANT of the ring: the slot of h_t (t & 1) is rewritten by step t + 2, i.e. only after the barrier of step t + 1; every
+//   read of h_t -- the recurrence of step t + 1 and the head of q_t, both in step t + 1 -- comes before that barrier.
 #pragma once
 
 #include "pw_common.hpp"
@@ -52,10 +66,30 @@ __host__ __device__ inline CriticLds critic_lds(int N, int R, unsigned char *raw
     o.bytes = 4 * c.at; return o;
 }
 
+// The per-step critic's layout: R = 16 for every N.  [2 slots][4 j][FR]: h_t in slot t & 1, the order of critic_lds; the four x1 buffers;
+// [R][N] q staging (row-major: what leaves for q / y).
+struct CriticStepsLds { float4 *s_out, *s_x; float *s_q; uint32_t bytes; };
+__host__ __device__ inline CriticStepsLds critic_steps_lds(int N, int R, unsigned char *raw = nullptr)
+{
+    LdsCursor c{reinterpret_cast<float *>(raw)}; CriticStepsLds o;
+    o.s_out = c.take<float4>(2 * 4 * 4 * R); o.s_x = c.take<float4>(4 * 4 * 4 * R);
+    o.s_q = c.take<float>(R * N);
+    o.bytes = 4 * c.at; return o;
+}
+template <bool STEPS>
+__device__ __forceinline__ auto critic_layout(const int N, const int R, unsigned char *raw)
+{
+    if constexpr (STEPS) return critic_steps_lds(N, R, raw);
+    else return critic_lds(N, R, raw);
+}
+
 // KO / KA: k steps of dense1 (four k each) the instantiation holds for the observation and the action part: ceil(D / 4) <= KO,
 // ceil(A / 4) <= KA.  (Both compile-time, so that every operand address is one per-lane pointer + an immediate: with the split at
 // a run-time k step the compiler keeps a hoisted address pair per operand across the timestep loop, and spills.)
-template <int KO, int KA>
+// STEPS: the per-step critic, pw_critic_forward_steps (rew / done / q / y are [b][N]); else the attention critic, pw_critic_forward.  One
+// kernel template for both: the discarded branches leave no trace, so the <KO, KA, false> instantiations are, instruction for
+// instruction, the attention kernel as it was before the per-step form existed.
+template <int KO, int KA, bool STEPS>
 __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs C)
 {
     constexpr int KS = KO + KA;
@@ -64,7 +98,7 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int hq = wave & 3, grp = wave >> 2;
     const int N = C.N, D = C.D, A = C.A, K = D + A, R = C.R, FR = 4 * R;
-    const CriticLds Y = critic_lds(N, R, critic_smem);
+    const auto Y = critic_layout<STEPS>(N, R, critic_smem);
     const long b0 = (long)blockIdx.x * R;
     const int rows_here = (int)(C.b - b0 < (long)R ? C.b - b0 : (long)R);
     const bool col_ok = n16 < rows_here;  // columns past the rows of this workgroup compute on row b0 and store nothing
@@ -97,6 +131,30 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
     for (int sx = 0; sx < KS; ++sx) a1[sx] = w1_frag(sx);
 #pragma unroll
     for (int i = 0; i < 4; ++i) b1v[i] = C.b1[16 * hq + 4 * kq + i];
+    // per-step head: w2 in the order of a lane's B fragments (element e of fragment j = unit 16 j + 4 e + kq)
+    float w2v[16], b2v = 0.0f;   // dead (and removed) in the attention instantiations
+    if constexpr (STEPS) {
+#pragma unroll
+        for (int u = 0; u < 16; ++u) w2v[u] = C.w2[16 * (u >> 2) + 4 * (u & 3) + kq];
+        b2v = C.b2[0];
+    }
+    auto out_slot = [](const int t) { return STEPS ? (t & 1) : t; };
+    // q_tq of the workgroup's rows from the fragments of h_tq (one wave): 16 units per lane in ascending order, the four k quarters meet
+    auto head = [&](const int tq, const float4 (&hv)[4]) {
+        float p = 0.0f;
+#pragma unroll
+        for (int jx = 0; jx < 4; ++jx) {
+            p += hv[jx].x * w2v[4 * jx + 0];
+            p += hv[jx].y * w2v[4 * jx + 1];
+            p += hv[jx].z * w2v[4 * jx + 2];
+            p += hv[jx].w * w2v[4 * jx + 3];
+        }
+        p += lane_xor16(p);
+        p += lane_xor32(p);
+        if constexpr (STEPS) {
+            if (kq == 0 && n16 < R) Y.s_q[n16 * N + tq] = p + b2v;
+        }
+    };
 
     // B operands of one dense1 tile: [obs | action] of row (b0 + nq, ts)
     auto load_x = [&](const int ts, float (&xb)[KS]) {
@@ -171,7 +229,7 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
         float xb[KS];
         if (d1_now) load_x(ts2, xb);
         if (t > 0) {
-            const float4 *hx = Y.s_out + ((t - 1) * 4) * FR + slot;
+            const float4 *hx = Y.s_out + (out_slot(t - 1) * 4) * FR + slot;
             const float4 hv[4] = {hx[0], hx[FR], hx[2 * FR], hx[3 * FR]};
 #pragma unroll
             for (int jx = 0; jx < 4; ++jx) {
@@ -185,6 +243,9 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
                 acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][4 * jx + 3], bq.w, acc[0], 0, 0, 0);
                 acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][4 * jx + 3], bq.w, acc[1], 0, 0, 0);
             }
+            if constexpr (STEPS) {
+                if (wave == ((t - 1) & 7)) head(t - 1, hv);   // behind the matrix instructions, before this step's barrier (see INVARIANT)
+            }
         }
         // the two cells of this lane: accumulator registers = gates i, f, g, o of unit 8 wave + 4 T + kq
         float h0v, h1v;
@@ -192,13 +253,34 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
         lstm_cell(acc[1][0], acc[1][1], acc[1][2], acc[1][3], c1, h1v);
         // unit 8 wave + 4 T + kq is k quarter kq of k step 2 wave + T: fragment wave / 2, elements 2 (wave % 2) + T of this lane's slot
         if (n16 < R)
-            reinterpret_cast<float2 *>(Y.s_out + (t * 4 + (wave >> 1)) * FR + kq * R + n16)[wave & 1] = make_float2(h0v, h1v);
+            reinterpret_cast<float2 *>(Y.s_out + (out_slot(t) * 4 + (wave >> 1)) * FR + kq * R + n16)[wave & 1] = make_float2(h0v, h1v);
         if (d1_now) dense1(ts2, xb);
         if (t + 1 < N) inproj(t + 1, accn);  // before the barrier: work for the matrix pipe while the workgroup meets
         wg_lds_barrier();                    // h_t of every unit is in LDS
         if (t + 1 < N) { acc[0] = accn[0]; acc[1] = accn[1]; }
     }
 
+    if constexpr (STEPS) {
+        // ---- the last step's head, then q (and y) of the workgroup's rows leave as one contiguous run of rows_here * N floats
+        if (wave == ((N - 1) & 7)) {
+            const float4 *hx = Y.s_out + (out_slot(N - 1) * 4) * FR + slot;
+            const float4 hv[4] = {hx[0], hx[FR], hx[2 * FR], hx[3 * FR]};
+            head(N - 1, hv);
+        }
+        wg_lds_barrier();
+        const int cnt = rows_here * N;
+        const size_t base = (size_t)b0 * N;
+        for (int i = tid; i < cnt; i += 512) {
+            const float qv = Y.s_q[i];
+            C.q[base + i] = qv;
+            if (C.y) {  // r + GAMMA * q_next * (1. - d) per agent (BIC_gumbel_fix.py:155-160), left to right, no contraction
+                const float gq = C.gamma * qv;
+                const float nd = 1.0f - C.done[base + i];
+                const float prod = gq * nd;
+                C.y[base + i] = C.rew[base + i] + prod;
+            }
+        }
+    } else {
     // ---- attention scores <h_t, h_N>: one timestep per wave and round, a lane sums its 16 units, the four k quarters meet
     {
         const float4 *hn = Y.s_out + ((N - 1) * 4) * FR + slot;
@@ -255,6 +337,7 @@ __global__ void __launch_bounds__(512) pw_critic_forward_kernel(const CriticArgs
             const float prod = gq * nd;
             C.y[b0 + tid] = C.rew[b0 + tid] + prod;
         }
+    }
     }
 }
 

@@ -125,7 +125,8 @@ __global__ void __launch_bounds__(256) pw_replay_add_tail_kernel(const pw_replay
 // A whole rollout chunk into the ring in ONE launch (the sink of pw_policy_rollout / pw_rollout): transition
 // (t, e) -> slot (start + t * B + e) % capacity, i.e. the order in which T calls of pw_replay_add would have stored
 // them; obs of step t is obs0 (t = 0) or the chunk's obs[t - 1], next_obs the PRE-reset observation where the env
-// terminated (run.py:52 vs :60).  The last `stat_blocks` workgroups do the episode-return bookkeeping of the
+// terminated (run.py:52 vs :60).  A per-agent ring takes rew / done from the chunk's [T,B,N] planes (io.rew, io.done), a plain one
+// the shared scalar and 0.  The last `stat_blocks` workgroups do the episode-return bookkeeping of the
 // chunk: thread = env, walking its T steps in order (loads batched 8 deep), a fixed-order tree per workgroup, the
 // partial (sum, count) into `scratch`, and the workgroup that arrives last adds the partials in index order --
 // bit-reproducible without float atomics.  scratch: [2 * stat_blocks + 1] 8-byte words, zero before first use.
@@ -148,7 +149,12 @@ __global__ void __launch_bounds__(256) pw_replay_add_rollout_kernel(const pw_rep
             st.next_obs[slot * ND + c] = fin ? io.final_obs[i] : io.obs[i];
             const size_t NA = (size_t)N * (st.act_heads == 2 ? 2 : 1);  // two-head ring: act [cap,N,2], chunk act [T,B,N,2]
             if (c < NA) st.act[slot * NA + c] = (uint8_t)act[te * NA + c];
-            if (c == 0) {
+            if (st.per_agent) {  // the BiCNet tuple: the chunk's [T,B,N] planes (ND >= 2N: obs_dim >= 5)
+                if (c < (size_t)N) {
+                    st.rew[slot * N + c] = io.rew[te * N + c];
+                    st.done[slot * N + c] = io.done ? (float)io.done[te * N + c] : 0.0f;
+                }
+            } else if (c == 0) {
                 st.rew[slot] = io.rew_shared[te];
                 st.done[slot] = 0.0f;
             }

@@ -1,5 +1,6 @@
 // libpworld.so, third translation unit -- the learner's critic forward and TD target (rls/model/ac_network_multi_gumbel.py
-// CriticNetwork, ddpg_gumbel_fix.py:148-154): pw_critic_forward.  The kernel is csrc/pw_kernels_critic.hpp; the gate functions
+// CriticNetwork, ddpg_gumbel_fix.py:148-154): pw_critic_forward; and the BiCNet baseline's per-step critic with its per-agent TD
+// target (ac_network_multi_gumbel_BIC.py CriticNetwork, BIC_gumbel_fix.py:155-160): pw_critic_forward_steps.  The kernel is csrc/pw_kernels_critic.hpp; the gate functions
 // and the LDS barrier are the actor's (pw_lstm_math.hpp: included, not copied).  Declared in include/pworld.h; the error text
 // is shared with pworld.hip.
 #include "pw_host.hpp"
@@ -12,12 +13,47 @@ template <int KO, int KA>
 int critic_launch(const CriticArgs &C, hipStream_t stream)
 {
     static unsigned long long optin_mask = 0;
-    const auto kernel = pw_critic_forward_kernel<KO, KA>;
+    const auto kernel = pw_critic_forward_kernel<KO, KA, false>;
     const size_t lds = critic_lds(C.N, C.R).bytes;
     PW_LDS_OPTIN(&optin_mask, kernel);
     const long groups = (C.b + C.R - 1) / C.R;
     hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);
     PW_HIP_CHECK(hipGetLastError());
+    return PW_OK;
+}
+
+template <int KO, int KA>
+int critic_steps_launch(const CriticArgs &C, hipStream_t stream)
+{
+    static unsigned long long optin_mask = 0;
+    const auto kernel = pw_critic_forward_kernel<KO, KA, true>;
+    const size_t lds = critic_steps_lds(C.N, C.R).bytes;
+    PW_LDS_OPTIN(&optin_mask, kernel);
+    const long groups = (C.b + C.R - 1) / C.R;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);
+    PW_HIP_CHECK(hipGetLastError());
+    return PW_OK;
+}
+
+// the arguments both entry points share; fills everything of C but R
+int critic_args(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1, const float *w1,
+                const float *b1, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w2,
+                const float *b2, int64_t b, int32_t N, int32_t obs_dim, const float *rew, const float *done, float gamma, float *q,
+                float *y, CriticArgs &C)
+{
+    if (!obs || !w1 || !b1 || !w_ih || !w_hh || !b_ih || !b_hh || !w2 || !b2 || !q) return fail(PW_EINVAL, "null argument");
+    if ((act_idx != nullptr) == (act_vec != nullptr)) return fail(PW_EINVAL, "exactly one of act_idx / act_vec must be given");
+    if (n_act0 < 1 || n_act1 < 0 || n_act0 + n_act1 > 16)
+        return fail(PW_EINVAL, "action widths: n_act0 >= 1, n_act0 + n_act1 <= 16");
+    if (N < 1 || N > PW_MAX_AGENTS) return fail(PW_EINVAL, "N must be in [1, 64]");
+    if (obs_dim < 1 || obs_dim > 104) return fail(PW_EINVAL, "obs_dim must be in [1, 104]");
+    if (b < 1 || b > (int64_t)0x7fffffff) return fail(PW_EINVAL, "b must be in [1, 2^31)");
+    if (y ? (!rew || !done) : (rew || done)) return fail(PW_EINVAL, "the TD target needs rew, done and y together");
+    C.obs = obs; C.act_idx = act_idx; C.act_vec = act_vec;
+    C.w1 = w1; C.b1 = b1; C.w_ih = w_ih; C.w_hh = w_hh; C.b_ih = b_ih; C.b_hh = b_hh; C.w2 = w2; C.b2 = b2;
+    C.rew = rew; C.done = done; C.q = q; C.y = y;
+    C.b = (long)b; C.N = N; C.D = obs_dim; C.A = n_act0 + n_act1; C.n0 = n_act0; C.n1 = n_act1;
+    C.gamma = gamma;
     return PW_OK;
 }
 
@@ -30,24 +66,34 @@ int pw_critic_forward(const float *obs, const int32_t *act_idx, const float *act
                       const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
                       const float *rew, const float *done, float gamma, float *q, float *y, void *stream)
 {
-    if (!obs || !w1 || !b1 || !w_ih || !w_hh || !b_ih || !b_hh || !w2 || !b2 || !q) return fail(PW_EINVAL, "null argument");
-    if ((act_idx != nullptr) == (act_vec != nullptr)) return fail(PW_EINVAL, "exactly one of act_idx / act_vec must be given");
-    if (n_act0 < 1 || n_act1 < 0 || n_act0 + n_act1 > 16)
-        return fail(PW_EINVAL, "action widths: n_act0 >= 1, n_act0 + n_act1 <= 16");
-    if (N < 1 || N > PW_MAX_AGENTS) return fail(PW_EINVAL, "N must be in [1, 64]");
-    if (obs_dim < 1 || obs_dim > 104) return fail(PW_EINVAL, "obs_dim must be in [1, 104]");
-    if (b < 1 || b > (int64_t)0x7fffffff) return fail(PW_EINVAL, "b must be in [1, 2^31)");
-    if (y ? (!rew || !done) : (rew || done)) return fail(PW_EINVAL, "the TD target needs rew, done and y together");
     CriticArgs C;
-    C.obs = obs; C.act_idx = act_idx; C.act_vec = act_vec;
-    C.w1 = w1; C.b1 = b1; C.w_ih = w_ih; C.w_hh = w_hh; C.b_ih = b_ih; C.b_hh = b_hh; C.w2 = w2; C.b2 = b2;
-    C.rew = rew; C.done = done; C.q = q; C.y = y;
-    C.b = (long)b; C.N = N; C.D = obs_dim; C.A = n_act0 + n_act1; C.n0 = n_act0; C.n1 = n_act1;
+    if (int rc = critic_args(obs, act_idx, act_vec, n_act0, n_act1, w1, b1, w_ih, w_hh, b_ih, b_hh, w2, b2, b, N, obs_dim, rew, done,
+                             gamma, q, y, C))
+        return rc;
     C.R = N <= 32 ? 16 : 8;  // all N step outputs of a workgroup's rows stay in LDS for the attention pass
-    C.gamma = gamma;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;  // k steps of dense1: observation part (<= 26), action part (<= 4)
 #define PW_CRITIC_GO(KO) return sa <= 2 ? critic_launch<KO, 2>(C, s) : critic_launch<KO, 4>(C, s)
+    if (so <= 4) PW_CRITIC_GO(4);
+    if (so <= 8) PW_CRITIC_GO(8);
+    if (so <= 16) PW_CRITIC_GO(16);
+    PW_CRITIC_GO(26);
+#undef PW_CRITIC_GO
+}
+
+int pw_critic_forward_steps(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
+                            const float *w1, const float *b1, const float *w_ih, const float *w_hh, const float *b_ih,
+                            const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
+                            const float *rew, const float *done, float gamma, float *q, float *y, void *stream)
+{
+    CriticArgs C;
+    if (int rc = critic_args(obs, act_idx, act_vec, n_act0, n_act1, w1, b1, w_ih, w_hh, b_ih, b_hh, w2, b2, b, N, obs_dim, rew, done,
+                             gamma, q, y, C))
+        return rc;
+    C.R = 16;  // only h_{t-1} and h_t are live: the two-slot ring serves every N with full tiles
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;
+#define PW_CRITIC_GO(KO) return sa <= 2 ? critic_steps_launch<KO, 2>(C, s) : critic_steps_launch<KO, 4>(C, s)
     if (so <= 4) PW_CRITIC_GO(4);
     if (so <= 8) PW_CRITIC_GO(8);
     if (so <= 16) PW_CRITIC_GO(16);

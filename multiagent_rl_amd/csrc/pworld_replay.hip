@@ -171,7 +171,7 @@ int pw_replay_add_rollout(const pw_replay_store *st, int64_t start, int32_t B, i
                           int64_t *finished_count, void *scratch, void *stream)
 {
     if (!st || !obs0 || !io || !act || !io->obs || !io->rew_shared || !io->terminal) return fail(PW_EINVAL, "null argument");
-    if (st->per_agent) return fail(PW_EINVAL, "pw_replay_add_rollout: per-agent rings are served by pw_replay_add and pw_replay_gather only");
+    if (st->per_agent && !io->rew) return fail(PW_EINVAL, "pw_replay_add_rollout: a per-agent ring needs the chunk's per-agent rew [T,B,N]");
     if (st->state_rows) return fail(PW_EINVAL, "pw_replay_add_rollout: a STATE ring is filled by pw_replay_add_state_wire only");
     if (B < 1 || T < 1 || !ring_fits(st, (int64_t)B * T, start))
         return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");

@@ -299,7 +299,8 @@ class ReplayBuffer(object):
         """A whole rollout chunk in ONE launch: ``out`` = the [T, ...] outputs of ``FusedActor.rollout`` /
         ``BatchedParticleEnv.rollout`` (obs, rew_shared, terminal, final_obs, act), ``obs0`` [B,N,D] the
         observation before its first step.  Stored in the order T ``add_batch`` calls would have used; optionally
-        does the chunk's episode-return bookkeeping in the same launch."""
+        does the chunk's episode-return bookkeeping in the same launch.  A ``per_agent`` ring also takes ``out['rew']`` [T,B,N]
+        (required) and ``out['done']`` [T,B,N] (bool / uint8; absent = 0) into its per-agent planes."""
         from ._lib import PwStepIO
         T, B, N, D = out['obs'].shape
         self._ensure_device()
@@ -309,7 +310,15 @@ class ReplayBuffer(object):
             self._allocate(N, D)
         assert (N, D) == (self.num_agents, self.obs_dim) and T * B <= self._maxsize
         io = PwStepIO()
-        for name in ('obs', 'final_obs', 'rew_shared', 'terminal'):
+        names = ('obs', 'final_obs', 'rew_shared', 'terminal')
+        if self.per_agent:   # the BiCNet tuple: the chunk's per-agent planes fill rew / done [cap,N]
+            if out.get('rew') is None:
+                raise ValueError("ReplayBuffer.add_rollout: a per-agent ring needs the chunk's per-agent rewards out['rew'] [T,B,N]")
+            assert tuple(out['rew'].shape) == (T, B, N) and out['rew'].dtype == torch.float32
+            done = out.get('done')
+            assert done is None or (tuple(done.shape) == (T, B, N) and done.element_size() == 1), "out['done'] must be [T,B,N] bool / uint8"
+            names += ('rew', 'done')
+        for name in names:
             t = out.get(name)
             if t is not None:
                 assert t.is_cuda and t.is_contiguous()

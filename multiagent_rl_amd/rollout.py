@@ -238,9 +238,14 @@ class BatchedRollout(object):
                                            p(self.finished_return_sum), p(self.finished_episodes), *args,
                                            self.env._stream()))
 
+    def _per_agent_memory(self):
+        return self.memory is not None and bool(getattr(self.memory, 'per_agent', False))
+
     def _sink(self, obs, actions, out, parity=None, step_counter=None):
-        """Replay append + episode-return bookkeeping: ONE launch when there is a device ring."""
-        if self.memory is not None and actions.dtype == torch.int32 and actions.dim() == 2 and \
+        """Replay append + episode-return bookkeeping: ONE launch when there is a device ring.  A per-agent ring (the BiCNet tuple)
+        takes the per-step ``add_batch`` path with the step's per-agent rewards and dones; the bookkeeping stays on ``rew_shared``."""
+        per_agent = self._per_agent_memory()
+        if self.memory is not None and not per_agent and actions.dtype == torch.int32 and actions.dim() == 2 and \
                 out.get('final_obs') is not None:
             self.memory.add_batch_tail(obs, actions, out['rew_shared'], out['obs'], out['final_obs'], out['terminal'],
                                        self.episode_return, self.finished_return_sum, self.finished_episodes,
@@ -248,7 +253,8 @@ class BatchedRollout(object):
             return
         counters = [] if step_counter is None else [(step_counter, 1, 0)]
         if self.memory is not None:
-            self.memory.add_batch(obs, actions, out['rew_shared'], out['obs'], out.get('final_obs'), out['terminal'],
+            self.memory.add_batch(obs, actions, out['rew'] if per_agent else out['rew_shared'], out['obs'], out.get('final_obs'),
+                                  out['terminal'], done=out['done'].float() if per_agent else None,
                                   device_cursor=parity is not None, advance_cursor=False)
             if parity is not None:
                 counters.append((self.memory._cursor, self.env.num_envs, self.memory._maxsize))
@@ -258,7 +264,7 @@ class BatchedRollout(object):
         obs = self.obs
         actions = self.policy(obs)
         nxt, rew, done, info = self.env.step(actions)
-        self._sink(obs, actions, dict(info, obs=nxt))
+        self._sink(obs, actions, dict(info, obs=nxt, rew=rew, done=done))
         self.obs = nxt
         self.env_steps += self.env.num_envs
         return nxt, rew, done, info
@@ -334,13 +340,23 @@ class BatchedRollout(object):
         (row or STATE ring); every other configuration ``env.step`` serves -- the full observation, L > N, landmark contact,
         ``dispatch=dict(force_generic=1)`` -- runs on the generic one-launch kernel with a plain row ring, rows of at most 64 numbers;
         agents that differ within a role need ``env.set_dispatch(policy_form=5)``.  Stores exactly what ``collect`` stores (statistics up
-        to float64 summation order)."""
+        to float64 summation order).  A per-agent ``memory`` (the BiCNet tuple) is not served by the in-kernel ring sink: the chunk runs
+        with the statistics sink alone and its outputs go into the ring with ``memory.add_rollout`` -- two launches per chunk."""
         assert self._graph is None and hasattr(self.policy, 'rollout')
         stats = (self.episode_return, self.finished_return_sum, self.finished_episodes)
         done_steps = 0
+        per_agent = self._per_agent_memory()
+        obs0 = self.obs      # the observation the chunk starts from: self.obs, then the previous chunk's last obs
         while done_steps < num_steps:
             T = min(chunk, num_steps - done_steps)
-            if keep_outputs:
+            if per_agent:
+                # two sets of output buffers in turn: obs0 is a view of the previous chunk's, which this chunk's launch must not overwrite
+                bufs = self.__dict__.setdefault('_pa_chunks', {})
+                flip = self._pa_flip = 1 - getattr(self, '_pa_flip', 0)
+                out = bufs[(T, flip)] = self.policy.rollout(self.env, T, bufs.get((T, flip)), memory=None, stats=stats)
+                self.memory.add_rollout(obs0.contiguous(), out)
+                obs0, self.last_chunk = out['obs'][T - 1], out
+            elif keep_outputs:
                 if getattr(self, '_chunk_T', None) != T:
                     self._chunk_T, self.last_chunk = T, None
                 self.last_chunk = self.policy.rollout(self.env, T, self.last_chunk, memory=self.memory, stats=stats)

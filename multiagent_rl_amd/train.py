@@ -110,7 +110,8 @@ def merge_histories(parts):
 
 def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discrete', cnt=0, arglist=None, memory=None,
                   out_dir='Models', log=print, chunk=100, max_updates_per_chunk=None, policy_seed=None,
-                  per_episode_history=True, gather=None, rank=0, world=1, make_rollout=None, ring='rows'):
+                  per_episode_history=True, gather=None, rank=0, world=1, make_rollout=None, ring='rows',
+                  per_agent_transition=False):
     """``experiments/run.py:run`` for a ``BatchedParticleEnv`` (auto_reset=True).  Runs until ``arglist.num_episodes`` episodes
     have finished (over all envs of this rank), then pickles the history with the reference's keys and saves the models.
     ``gather`` (a ``dist.FullTransitionGather``) switches to the multi-GPU form: every rank rolls out into the gather's wire
@@ -119,12 +120,19 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     observation, simple_tag): the rollout's ring sink fills a STATE ring -- {vel, pos} + the episode's landmarks per transition, a
     third of the bytes -- and ``sample_index`` rebuilds the rows the learner trains on (bit-identical batches).  Envs only the generic
     one-launch rollout serves (the full observation, L > N, landmark contact on simple_spread, ``policy_form=5``) take ``ring='rows'``:
-    their rollout refuses a STATE ring.  Returns the history
+    their rollout refuses a STATE ring.  ``per_agent_transition=True`` (the BiCNet baseline, ``experiments/run_BIC.py:46,50``): the ring
+    holds per-agent ``rew`` / ``done`` planes ([cap, N]) and every chunk is the policy rollout followed by ``memory.add_rollout`` (two
+    launches); single-rank row rings only -- with ``gather`` or ``ring='state'`` it raises.  Returns the history
     dict (with ``stats``: env-steps, updates, wall time)."""
     from .replay_buffer import ReplayBuffer
     cfg = _default_arglist if arglist is None else arglist
     if action_type not in ('Discrete', 'MultiDiscrete'):
         raise ValueError('action_type must be Discrete or MultiDiscrete, got %r' % (action_type,))
+    if per_agent_transition and gather is not None:
+        raise ValueError('per_agent_transition=True with gather=: the multi-rank gather carries the shared reward only (per-agent wire '
+                         'blocks are not served)')
+    if per_agent_transition and ring == 'state':
+        raise ValueError("per_agent_transition=True with ring='state': a STATE ring is a shared-reward ring (per-agent rewards are not served)")
     B, N = env.num_envs, env.n
     log('observation shape: ', env.observation_space)
     log('action shape: ', env.action_space)
@@ -140,6 +148,8 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
                     raise ValueError("ring='state' serves simple_spread (local observation) and simple_tag")
                 kw = dict(state_ring=dict(scenario=env.scenario_name, num_landmarks=env.num_landmarks,
                                           num_adversaries=env.cfg.num_adversaries if env.scenario_name == 'simple_tag' else 0))
+            if per_agent_transition:
+                kw['per_agent'] = True
             memory = ReplayBuffer(int(1e6), N, env.obs_dim, device_index=True, **kw)   # the batch's indices drawn on the device
     learner = Trainer(actor, critic, memory, action_type=action_type)
     seed = (cnt + 12345678 if policy_seed is None else policy_seed) + rank

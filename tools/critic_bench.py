@@ -16,6 +16,11 @@ Launch counts: kernels seen by torch.profiler in one call of each path.
         N = 48 before the actor took rows longer than 64 numbers (stock target actor + pw_critic_forward), then the actor alone
         (stock ActorNetwork forward against FusedActor.logits); exit status 1 if the mix is not slower than (b) by more than the
         spread of the mix's repeats.
+    python tools/critic_bench.py --bicnet [--out profiles/critic_steps_td_target.txt]   # the BiCNet baseline: per-step critic
+        (BiCNetCritic, q and y on [b, N], per-agent r and d) at N in {3, 6, 12, 24, 48, 64}, D = min(4 + 2 N, 104): (a) stock against (b)
+        pw_actor_fused + sampling + pw_critic_forward_steps, "stock - fused" beside the spread of stock's repeats; then, at N = 48 and 64,
+        FusedCritic.q alone on the per-step kernel (16 rows per workgroup) beside the attention kernel (8 rows), at b = 1024 and b = 8192.  A record,
+        not a gate.
 Then the example learner (examples/madr_learner.py Trainer with the attention critic) at N = 6: wall time per optimize() with and
 without accelerate_trainer(targets=True), five repeats each, alternating.
 Exit status 1 if at N = 6 path (b) is not faster than path (a) by more than the spread (max - min) of (a)'s five repeats.
@@ -35,13 +40,14 @@ import torch.nn.functional as F  # noqa: E402
 GAMMA, B, REPEATS = 0.95, 1024, 5
 
 
-def make_paths(N, D):
-    from multiagent_rl_amd.critic import CriticNetwork, FusedCritic
+def make_paths(N, D, bicnet=False):
+    from multiagent_rl_amd.critic import BiCNetCritic, CriticNetwork, FusedCritic
     from multiagent_rl_amd.policy import ActorNetwork, FusedActor
     torch.manual_seed(N)
-    actor, critic = ActorNetwork(D, 5).cuda().eval(), CriticNetwork(D + 5, 1).cuda().eval()
+    actor, critic = ActorNetwork(D, 5).cuda().eval(), (BiCNetCritic if bicnet else CriticNetwork)(D + 5, 1).cuda().eval()
     s1 = torch.randn(B, N, D, device='cuda')
-    r, d = torch.randn(B, device='cuda'), (torch.rand(B, device='cuda') < 0.1).float()
+    rd = (B, N) if bicnet else (B,)       # the BiCNet tuple: per-agent reward and done
+    r, d = torch.randn(rd, device='cuda'), (torch.rand(rd, device='cuda') < 0.1).float()
     fused_actor = FusedActor(actor)
     fc = FusedCritic(critic)
 
@@ -132,6 +138,59 @@ def wide_rows(args):
     return 0 if ok else 1
 
 
+def bicnet_rows(args):
+    """The per-step critic: the TD-target table, then the critic kernel alone beside the attention kernel at N = 48 / 64."""
+    from multiagent_rl_amd.critic import BiCNetCritic, CriticNetwork, FusedCritic
+    lines = ['BiCNet TD target of a batch (per-agent r, d, y [b, N]), b = %d, D = min(4 + 2 N, 104), A = 5: device-event us per call '
+             '(%d calls per repeat, %d repeats, paths alternating)' % (B, args.iters, REPEATS),
+             '(a) stock PyTorch-ROCm: target_actor, hard Gumbel one-hot, BiCNetCritic, y;  (b) pw_actor_fused + the same sampling + '
+             'pw_critic_forward_steps with the epilogue',
+             '%-4s %-5s %-38s %-38s %-8s %-26s %s' % ('N', 'D', '(a) mean [min, max]', '(b) mean [min, max]', 'a / b',
+                                                     '(a) - (b) | spread of (a)', 'launches a | b')]
+    for N in (3, 6, 12, 24, 48, 64):
+        D = min(4 + 2 * N, 104)
+        stock, fused, _ = make_paths(N, D, bicnet=True)
+        for _ in range(20):
+            stock()
+            fused()
+        torch.cuda.synchronize()
+        ta, tb = [], []
+        for _ in range(REPEATS):
+            ta.append(device_time_us(stock, args.iters))
+            tb.append(device_time_us(fused, args.iters))
+        ma, mb = sum(ta) / REPEATS, sum(tb) / REPEATS
+        lines.append('%-4d %-5d %8.1f [%8.1f, %8.1f] %9s %8.1f [%8.1f, %8.1f] %9s %-8.2f %8.1f | %-15.1f %s | %s' % (
+            N, D, ma, min(ta), max(ta), '', mb, min(tb), max(tb), '', ma / mb, ma - mb, max(ta) - min(ta), launches(stock), launches(fused)))
+    lines.append('')
+    lines.append('FusedCritic.q alone (index actions): the per-step kernel (pw_critic_forward_steps, 16 rows per workgroup for every N) beside the '
+                 'attention kernel (pw_critic_forward, 8 rows per workgroup for N > 32): device-event us per call; b = %d is %d / %d workgroups '
+                 'on the chip, b = %d fills it' % (B, B // 16, B // 8, 8 * B))
+    for b in (B, 8 * B):
+        for N in (48, 64):
+            D = min(4 + 2 * N, 104)
+            torch.manual_seed(N)
+            fs, fa = FusedCritic(BiCNetCritic(D + 5, 1).cuda().eval()), FusedCritic(CriticNetwork(D + 5, 1).cuda().eval())
+            s1 = torch.randn(b, N, D, device='cuda')
+            idx = torch.randint(0, 5, (b, N), device='cuda', dtype=torch.int32)
+            group = [('per-step', lambda: fs.q(s1, idx)), ('attention', lambda: fa.q(s1, idx))]
+            for _ in range(20):
+                for _, fn in group:
+                    fn()
+            torch.cuda.synchronize()
+            t = {name: [] for name, _ in group}
+            for _ in range(REPEATS):
+                for name, fn in group:
+                    t[name].append(device_time_us(fn, args.iters))
+            lines.append('  b = %-5d N = %-3d D = %-4d %s' % (b, N, D, '   '.join('%s mean %7.1f [%7.1f, %7.1f]' % (
+                name, sum(v) / len(v), min(v), max(v)) for name, v in t.items())))
+    text = '\n'.join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text + '\n')
+    return 0
+
+
 def learner_times(lines, iters):
     """Wall time per optimize() of the example learner at N = 6, with / without the fused targets."""
     import madr_learner
@@ -182,9 +241,13 @@ def main():
     ap.add_argument('--kernel-only', action='store_true', help='200 fused TD targets at --agents and nothing else (for rocprofv3)')
     ap.add_argument('--agents', type=int, default=6, help='N of --kernel-only')
     ap.add_argument('--wide', action='store_true', help='N = 48 (D = 100) alone: three TD-target paths and the actor alone')
+    ap.add_argument('--bicnet', action='store_true', help='the per-step (BiCNet) critic: TD-target table at N = 3 .. 64 and the kernel beside '
+                                                          "the attention critic's at N = 48 / 64 (a record, not a gate)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('critic_bench: needs a GPU (no fallback)')
+    if args.bicnet:
+        return bicnet_rows(args)
     if args.wide:
         return wide_rows(args)
     if args.kernel_only:
