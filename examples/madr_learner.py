@@ -11,6 +11,8 @@ soft updates, Adam, batches drawn through ``memory.make_index`` / ``memory.sampl
 and the TD target formed on ``[b, N]``.
 ``Trainer(..., fused_optimizer=True)``: each network's clip + Adam step + soft update is one HIP launch
 (``multiagent_rl_amd.optim.FusedAdam``); the default is the stock sequence.
+``Trainer(..., fused_lstm=True)``: the LSTMs of actor and critic (and of the target networks copied from them) run their recurrence,
+forward and backward, on the HIP kernels (``multiagent_rl_amd.lstm.fuse_lstm``); the default is ``nn.LSTM``.
 """
 import copy
 import os
@@ -39,9 +41,14 @@ class CriticNetwork(nn.Module):
 class Trainer(object):
     per_agent = False   # BiCNetTrainer: per-agent rewards / dones [b,N] and a critic that returns [b,N,1]
 
-    def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False):
+    def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
+                 fused_lstm=False):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
+        if fused_lstm:   # before the deep copies: a class swap survives them, so the target networks are fused too
+            from multiagent_rl_amd.lstm import fuse_lstm
+            fuse_lstm(self.actor)
+            fuse_lstm(self.critic)
         self.target_actor, self.target_critic = copy.deepcopy(self.actor).eval(), copy.deepcopy(self.critic).eval()
         self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr)
         self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr)

@@ -17,7 +17,8 @@ transitions (``train_batched(per_agent_transition=True)``), ``multiagent_rl_amd.
 (with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only.  ``--fused-targets`` runs its target networks'
 forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
 soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch, or ``accelerate_trainer(.., optimizer=True)`` with
-``--reference``).
+``--reference``), ``--fused-lstm`` runs the recurrence of the learner's LSTMs with gradient on the HIP kernels
+(``multiagent_rl_amd.lstm``: the learner's own ``fused_lstm`` switch, or ``accelerate_trainer(.., lstm=True)`` with ``--reference``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -61,6 +62,10 @@ def main(argv=None):
     ap.add_argument('--fused-optimizer', action='store_true',
                     help="each network's gradient clip + Adam step + soft update is one HIP launch (madr_learner's fused_optimizer "
                          'switch; with --reference: accelerate_trainer(.., optimizer=True))')
+    ap.add_argument('--fused-lstm', action='store_true',
+                    help="the learner's LSTMs run their recurrence, forward and backward, on the HIP kernels (madr_learner's fused_lstm "
+                         'switch; with --reference: accelerate_trainer(.., lstm=True)); off by default: losses differ from '
+                         "MIOpen's in the last bits")
     args = ap.parse_args(argv)
     if args.fused_targets and args.critic not in ('attention', 'bicnet') and not args.reference:
         ap.error('--fused-targets needs --critic attention or --critic bicnet (the HIP critics are the LSTM architectures)')
@@ -87,16 +92,19 @@ def main(argv=None):
         from madr_learner import CriticNetwork, Trainer
         if args.critic == 'attention':
             from multiagent_rl_amd.critic import CriticNetwork
-    if args.fused_targets or args.fused_optimizer:
+    if args.fused_targets or args.fused_optimizer or args.fused_lstm:
         from multiagent_rl_amd.policy import accelerate_trainer
         plain_trainer = Trainer
 
         def Trainer(*a, **k):   # train_batched builds the learner itself: patch the instance it gets
             if args.fused_optimizer and not args.reference:
                 k['fused_optimizer'] = True
+            if args.fused_lstm and not args.reference:
+                k['fused_lstm'] = True
             learner = plain_trainer(*a, **k)
             if args.fused_targets or args.reference:
-                accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference)
+                accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
+                                   lstm=args.fused_lstm and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

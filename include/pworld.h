@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 111 /* 0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 112 /* 0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -597,6 +597,28 @@ int pw_adam_step(const pw_opt_tensor *tensors, int32_t count, int64_t step, doub
  * rounded to float32 before the sum, bit for bit torch's `t * (1.0 - tau) + s * tau`.  tau == 1 copies (an infinity in the old
  * target does not become NaN).  The three arrays are HOST arrays of device pointers / sizes; limits as pw_adam_step. */
 int pw_soft_update(float *const *target, const float *const *source, const int64_t *numel, int32_t count, double tau, void *stream);
+
+/* The recurrent part of a one-layer LSTM WITH gradient (csrc/pw_kernels_lstm.hpp), one launch each, for the learner's three passes per
+ * update.  Gate order i, f, g, o as in PyTorch.  Shapes served: dirs = 1, H = 64 (CriticNetwork.lstm, BiCNetCritic.lstm) and dirs = 2,
+ * H = 32 (ActorNetwork.bilstm; direction 1 walks t = N - 1 .. 0); b >= 1 and N >= 1 arbitrary.  Everything else, a null or
+ * misaligned pointer, w_hh_bw null with dirs = 2 or set with dirs = 1: PW_EINVAL naming the argument, nothing launched.
+ * G [b,N,dirs,4H] = x W_ih^T + b_ih + b_hh (the caller's GEMM), w_hh_* [4H,H] as nn.LSTM keeps them
+ * (views into the flat buffer: any 4-byte aligned address), w_hh_bw NULL when dirs = 1.
+ * Y [b,N,dirs*H] = [h_forward | h_reverse].  saved: NULL (no gradient wanted: nothing is stored) or
+ * [b,N,dirs,5,H] = i, f, g, o (after activation) and c of every step.  Initial h and c are zero.  The saved gates are formed for the
+ * backward (accurate in 1 - gate where a gate saturates: csrc/pw_kernels_lstm.hpp) and may differ in the last bits from those behind Y.
+ * Activations are pw_lstm_math.hpp's (v_exp_f32 / v_rcp_f32): results differ from MIOpen's in the last bits.  No atomics, fixed
+ * summation order: the same inputs give the same bits. */
+int pw_lstm_train_forward(const float *G, const float *w_hh_fw, const float *w_hh_bw, int64_t b, int32_t N,
+                          int32_t dirs, int32_t H, float *Y, float *saved, void *stream);
+/* dY [b,N,dirs*H] contiguous -> dG [b,N,dirs,4H]: the gradient at the pre-activations.  The recurrent part only: per sequence and
+ * direction the steps in the reverse of their forward order, from dh = dc = 0, with c_prev the forward order's previous c and
+ * tc = tanh(c_t) recomputed with the forward's function:
+ *   dh_t = dY_t + dh;  do = dh_t tc o(1-o);  dc_t = dc + dh_t o (1-tc^2);  di = dc_t g i(1-i);  df = dc_t c_prev f(1-f);
+ *   dg = dc_t i (1-g^2);  dG_t = [di, df, dg, do];  dh = dG_t . W_hh;  dc = dc_t f.
+ * The gradients of W_hh (dG^T against the shifted Y), W_ih, the biases and x are GEMMs and the caller's (multiagent_rl_amd/lstm.py). */
+int pw_lstm_train_backward(const float *dY, const float *saved, const float *w_hh_fw, const float *w_hh_bw, int64_t b,
+                           int32_t N, int32_t dirs, int32_t H, float *dG, void *stream);
 
 #ifdef __cplusplus
 }

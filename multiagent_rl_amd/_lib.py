@@ -172,6 +172,8 @@ SIGNATURES = {
     'pw_adam_step': (C.c_int, [C.POINTER(PwOptTensor), C.c_int32, C.c_int64] + [C.c_double] * 7 + [C.c_void_p, C.c_void_p]),
     'pw_soft_update': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_double,
                                  C.c_void_p]),
+    'pw_lstm_train_forward': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    'pw_lstm_train_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
 }
 
 

@@ -323,7 +323,7 @@ class FusedExploration(object):
         return [eye[0][idx[..., 0]], eye[1][idx[..., 1]]]
 
 
-def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False):
+def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -339,7 +339,12 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False):
     ``trainer.actor_optimizer`` / ``trainer.critic_optimizer`` become ``FusedAdam`` objects with the hyper-parameters and state of
     the ``torch.optim.Adam`` they replace (one launch per ``step()``), and ``trainer.soft_update`` becomes the one-launch
     ``optim.soft_update``.  The Trainer's ``clip_grad_norm_`` calls stay torch's.  Works with and without ``targets``; the default
-    leaves optimisers and ``soft_update`` exactly as they are."""
+    leaves optimisers and ``soft_update`` exactly as they are.
+
+    ``lstm=True`` runs the recurrent part of every served ``nn.LSTM`` the trainer owns -- actor, critic, and the target networks unless
+    ``targets=True`` has already wrapped them -- on the HIP kernels with gradient (``multiagent_rl_amd.lstm.fuse_lstm``: a class swap,
+    parameters and ``state_dict`` keys unchanged).  Opt-in like the other two: the kernels' gate activations differ from MIOpen's in
+    the last bits, so a seeded run does not reproduce across the switch."""
     fx = FusedExploration(trainer.actor, getattr(trainer, 'action_type', 'Discrete'), seed=seed)
     trainer.get_exploration_action = fx.get_exploration_action
     target_actor = None
@@ -350,6 +355,9 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False):
     if optimizer:
         from .optim import fuse_optimizers
         fx.optimizers = fuse_optimizers(trainer)
+    if lstm:
+        from .lstm import fuse_trainer
+        fx.fused_lstms = fuse_trainer(trainer)
 
     def _wrap(name):
         inner = getattr(trainer, name, None)
