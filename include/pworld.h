@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 112 /* 0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 113 /* 0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -482,7 +482,10 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
 /* Optional direct sink of pw_policy_rollout: the chunk's transitions go straight into the replay ring (slot
  * (ring_start + t*B + env) % capacity -- the order of T pw_replay_add calls; next_obs = the PRE-reset observation)
  * and the episode returns are kept in the same launch (episode_return [B] running returns, finished_sum /
- * finished_count accumulated reproducibly; scratch = pw_policy_rollout_scratch_bytes(h) device bytes, zeroed once).
+ * finished_count accumulated reproducibly; scratch = pw_policy_rollout_scratch_bytes(h) device bytes, zeroed ONCE by the caller and
+ * then left to the launches: 0.1.13 -- it is valid for any sequence of launch forms on the handle (pw_set_dispatch policy_form,
+ * pw_actor_set_bf16x3 between launches) and for any handle of equal num_envs, one launch at a time; every launch leaves its ticket
+ * word zero again.  Word 0 is the ticket, [1, 1 + 2 * workgroups) the partial sums and counts of the last launch).
  * ring may be NULL (bookkeeping only) and episode_return may be NULL (ring only).  0.1.6: the ring may be a STATE ring
  * (pw_replay_store.state_rows) of the handle's scenario (simple_spread with the local observation, simple_tag): the launch then leaves
  * {vel, pos} of every agent before / after the step and the episode's landmarks per transition -- 254 B at C2 instead of 782 -- and

@@ -663,7 +663,7 @@ struct PolicyRolloutArgs {
     float *episode_return;          // [B] running return per env (or NULL)
     double *finished_sum;
     int64_t *finished_count;
-    unsigned long long *scratch;    // [2 * gridDim.x + 1] words, zero before first use
+    unsigned long long *scratch;    // [1 + 2 * gridDim.x] words (ticket, partial sums, partial counts: rollout_finish_stats), zeroed once
     int NP;                         // just-in-time form: row stride of an environment in LDS (>= N; odd: see pw_kernels_policy3j.hpp)
 };
 

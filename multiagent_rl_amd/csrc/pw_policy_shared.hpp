@@ -107,18 +107,21 @@ __device__ __forceinline__ size_t ring_slot(const int64_t ring_start, const int 
 }
 
 // Finished-episode statistics of a rollout launch (run.py:55-65 bookkeeping summed over all envs): every workgroup leaves its
-// partial (sum, count) in `scratch` ([gridDim.x] doubles, [gridDim.x] counts, one ticket word); the workgroup that takes the last
+// partial (sum, count) in `scratch` (word 0: the ticket; then [gridDim.x] doubles, [gridDim.x] counts); the workgroup that takes the last
 // ticket adds the partials up -- with ALL its threads: 512 partials per round through LDS and a fixed binary tree (deterministic:
-// the pairing depends on gridDim.x alone).  (Until round 4 one thread walked the partials one global load after the other: ~40 us at
+// the pairing depends on gridDim.x alone) -- and clears the ticket.  The ticket's place must not depend on the launch's grid: one scratch
+// serves every form a handle may launch (pw_dispatch.policy_form, bf16x3, two handles of equal B behind one actor), and behind a grid
+// of another size lie the previous launch's partials, not zeros.  (Until 0.1.13 the ticket sat at word 2 * gridDim.x: a launch with fewer
+// workgroups than its predecessor found a partial sum there, nobody drew the last ticket and the launch's episodes went uncounted.)  (Until round 4 one thread walked the partials one global load after the other: ~40 us at
 // the end of every launch with 256 workgroups -- 3 % of a 100-step C2 chunk.)  Call with the per-env partials in s_fs / s_fc
 // (LDS, complete: a barrier has passed); `red` = 8 KB of LDS that nothing else uses any more (the start of the block).
 __device__ __forceinline__ void rollout_finish_stats(const int envs_here, double *s_fs, int *s_fc, unsigned long long *scratch,
                                                      double *finished_sum, int64_t *finished_count, unsigned char *red)
 {
     const int tid = threadIdx.x;
-    double *part_sum = reinterpret_cast<double *>(scratch);
-    long long *part_cnt = reinterpret_cast<long long *>(scratch + gridDim.x);
-    unsigned long long *ticket = scratch + 2 * gridDim.x;
+    unsigned long long *ticket = scratch;
+    double *part_sum = reinterpret_cast<double *>(scratch + 1);
+    long long *part_cnt = reinterpret_cast<long long *>(scratch + 1 + gridDim.x);
     if (tid == 0) {
         double ws = 0.0;
         long long wc = 0;
