@@ -196,6 +196,57 @@ __device__ __forceinline__ void actor16_load(const ActorFusedArgs &A, const Acto
     for (int i = 0; i < 4; ++i) W.b2c[i] = 4 * kq + i < OUT ? A.b2[4 * kq + i] : 0.0f;
 }
 
+// ---- Pieces of one pass shared by the kernels on this core (actor16_forward below; pw_policy_rollout3_kernel and
+// pw_policy_rollout3j_kernel, which order them around their own environment step).  All of them are bit-critical: the tests demand
+// identical bits between every form and the three-launch chain.  What is NOT here although the three kernels repeat it -- the resident
+// weight load, the h exchange / head input / dense1 tile stores, policy3's recurrence -- moved some kernel's registers, spills or
+// step-loop instruction count when it was made a function (profiles/actor16_core_codegen.txt) and stays where it was.
+// Recurrence of step s2 > 0: acc += W_hh(tile) * h(ts - 1) out of exchange buffer (s2 - 1) & 1, k ascending, the two tiles alternating
+__device__ __forceinline__ void actor16_recur(const float4 *s_hx, const int s2, const int dir, const int lane,
+                                              const float (&ahh)[2][8], f32x4 (&acc)[2])
+{
+    const float4 *hx = s_hx + ((((s2 - 1) & 1) * 2 + dir) * 2) * 64 + lane;
+    const float4 h0 = hx[0], h1 = hx[64];
+    const float hk[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
+#pragma unroll
+    for (int sx = 0; sx < 8; ++sx) {
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][sx], hk[sx], acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][sx], hk[sx], acc[1], 0, 0, 0);
+    }
+}
+// Head chain: lg += W2 * x over the four k of one B fragment b (k steps s0 .. s0 + 3 of aw2) resp. over nj fragments read from
+// hx[0], hx[64], .. (the lane's own address), k ascending -- the chain of actor_forward_wg's head (b2 first, then one fused
+// multiply-add per hidden unit)
+__device__ __forceinline__ void actor16_head_frag(const float (&aw2)[16], const int s0, const float4 b, f32x4 &lg)
+{
+    lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 0], b.x, lg, 0, 0, 0);
+    lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 1], b.y, lg, 0, 0, 0);
+    lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 2], b.z, lg, 0, 0, 0);
+    lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 3], b.w, lg, 0, 0, 0);
+}
+__device__ __forceinline__ void actor16_head_chain(const float (&aw2)[16], const int s0, const int nj, const float4 *hx, const bool relu,
+                                                   f32x4 &lg)
+{
+#pragma unroll
+    for (int jx = 0; jx < nj; ++jx) {
+        float4 b = hx[jx * 64];
+        if (relu) { b.x = fmaxf(b.x, 0.0f); b.y = fmaxf(b.y, 0.0f); b.z = fmaxf(b.z, 0.0f); b.w = fmaxf(b.w, 0.0f); }
+        actor16_head_frag(aw2, s0 + 4 * jx, b, lg);
+    }
+}
+// Arg-max of one 5-logit head, first maximum wins: p0 .. p3 are the row's registers in row group 0, p4 register 0 of row group 1
+// (the caller fetches it across the lanes)
+__device__ __forceinline__ int actor16_argmax5(const float p0, const float p1, const float p2, const float p3, const float p4)
+{
+    int best = 0;
+    float bv = p0;
+    if (p1 > bv) { bv = p1; best = 1; }
+    if (p2 > bv) { bv = p2; best = 2; }
+    if (p3 > bv) { bv = p3; best = 3; }
+    if (p4 > bv) { bv = p4; best = 4; }
+    return best;
+}
+
 // dense1 by 16 x 16 TILES (optional; short agent axes): wave (w / 4, hq = w % 4) computes rows 16 hq .. 16 hq + 15 of relu(W1 x(ts) + b1) for
 // the 16 sequences of timestep ts = w / 4, w / 4 + 2, .. as ONE v_mfma_f32_16x16x4_f32 accumulator (K = D) -- pw_kernels_policy3j.hpp's
 // dense1, whose header has the argument for the bits: fed k = 4 s + kq the chain sums the same k in the same order as the 32x32x2 blocks.
@@ -224,9 +275,7 @@ __device__ __forceinline__ void actor16_load_d1(const ActorFusedArgs &A, Actor16
 
 // One pass for the rows of this workgroup (all 512 threads call it; E <= 16 environments, rows env-major r = e * N + agent).
 //   xrows, xstride  observation rows [rows_here][xstride >= A.D] -- global memory or LDS (readable on entry)
-//   step            Philox step of the Gumbel noise: value (row, logit o) = log(-log(u)), u = word (o & 3) of Philox block
-//                   (o >> 2) keyed (seed; step, global row), as pw_actor_head_kernel -- block rg is exactly what the lanes of
-//                   row group rg need for their four logits
+//   step            Philox step of the Gumbel noise (pw_gumbel_noise4: block rg serves the four logits of row group rg)
 //   act_g / act_l   sinks of the sampled indices [rows_here * nheads], global / LDS (either may be NULL); A.H, A.logits too
 //   noise_l         this pass's Gumbel noise in LDS (actor16_draw_noise, same step), or NULL: drawn here
 //   d1              W1 as 16 x 16 tile fragments (actor16_load_d1): dense1 runs as tiles on all eight waves (exact form only), or NULL: 32 x 32 blocks
@@ -239,9 +288,8 @@ struct Actor16NoHook {
 };
 
 // The Gumbel noise of ONE pass's head(s), drawn ahead of the pass into LDS [rows_here][NB = ceil(OUT / 4) blocks][4] (16-byte aligned; the
-// lanes of row group kq read block kq of their row as one float4): value (row, logit o) = log(-log(u)), u = word (o & 3) of Philox
-// block (o >> 2) keyed (seed; step, global row) -- the numbers actor16_forward draws inline when it is given no noise.  One thread
-// per (row, block); called by `nthr` threads with indices t0 = 0 .. nthr - 1.  A rollout kernel runs it for step t + 1 on the waves
+// lanes of row group kq read block kq of their row as one float4): pw_gumbel_noise4's values, the numbers actor16_forward draws
+// inline when it is given no noise.  One thread per (row, block); called by `nthr` threads with indices t0 = 0 .. nthr - 1.  A rollout kernel runs it for step t + 1 on the waves
 // that wait while the environment waves advance step t: ten Philox rounds and two logarithms per logit leave the head's dependent
 // chain (stamps, simple_reference: 3.8 k of a step's 16 k cycles sat there).
 __host__ __device__ constexpr int actor16_noise_blocks(int rows, int out) { return rows * ((out + 3) >> 2); }   // float4 each
@@ -251,17 +299,8 @@ __device__ __forceinline__ void actor16_draw_noise(const ActorFusedArgs &A, floa
     const int OUT = A.n_out0 + A.n_out1, NB = (OUT + 3) >> 2;
     for (int idx = t0; idx < rows_here * NB; idx += nthr) {
         const int rr = idx / NB;
-        const uint32_t blk = (uint32_t)(idx - rr * NB), tag = ((blk & 1u) << 31) | ((blk >> 1) << 30);
-        const long grow = row_base + rr;
-        uint32_t u[4];
-        pw_philox4x32_10((uint32_t)grow, (uint32_t)((uint64_t)grow >> 32) | tag, (uint32_t)step, (uint32_t)(step >> 32),
-                         (uint32_t)A.seed, (uint32_t)(A.seed >> 32), u);
-        float nz[4];
-#pragma unroll
-        for (int wq = 0; wq < 4; ++wq) {   // (the words past OUT serve no logit: their values are never looked at)
-            const float uo = pw_gumbel_uniform(u[wq]);  // in (0, 1)
-            nz[wq] = __logf(-__logf(uo));
-        }
+        float nz[4];   // (the words past OUT serve no logit: their values are never looked at)
+        pw_gumbel_noise4(A.seed, step, row_base + rr, (uint32_t)(idx - rr * NB), nz);
         reinterpret_cast<float4 *>(s_noise)[idx] = make_float4(nz[0], nz[1], nz[2], nz[3]);
     }
 }
@@ -358,26 +397,7 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
         inproj(dir ? N - 1 : 0, acc);
         for (int s2 = 0; s2 < N; ++s2) {
             const int ts = dir ? N - 1 - s2 : s2;
-            if (s2 > 0) {
-                const float4 *hx = S.s_hx + ((((s2 - 1) & 1) * 2 + dir) * 2) * 64 + lane;
-                const float4 h0 = hx[0], h1 = hx[64];
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][0], h0.x, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][0], h0.x, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][1], h0.y, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][1], h0.y, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][2], h0.z, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][2], h0.z, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][3], h0.w, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][3], h0.w, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][4], h1.x, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][4], h1.x, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][5], h1.y, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][5], h1.y, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][6], h1.z, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][6], h1.z, acc[1], 0, 0, 0);
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[0][7], h1.w, acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(W.ahh[1][7], h1.w, acc[1], 0, 0, 0);
-            }
+            if (s2 > 0) actor16_recur(S.s_hx, s2, dir, lane, W.ahh, acc);
             // the two cells of this lane: accumulator registers = gates i, f, g, o
             float h0v, h1v;
             lstm_cell(acc[0][0], acc[0][1], acc[0][2], acc[0][3], c0, h0v);
@@ -431,12 +451,7 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
         if (noise_l) nzv = reinterpret_cast<const float4 *>(noise_l)[(row_ok ? rr : 0) * NB + (kq < NB ? kq : 0)];
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int jx = 0; jx < 4; ++jx) {
-            lg = __builtin_amdgcn_mfma_f32_16x16x4f32(W.aw2[4 * jx + 0], hb[jx].x, lg, 0, 0, 0);
-            lg = __builtin_amdgcn_mfma_f32_16x16x4f32(W.aw2[4 * jx + 1], hb[jx].y, lg, 0, 0, 0);
-            lg = __builtin_amdgcn_mfma_f32_16x16x4f32(W.aw2[4 * jx + 2], hb[jx].z, lg, 0, 0, 0);
-            lg = __builtin_amdgcn_mfma_f32_16x16x4f32(W.aw2[4 * jx + 3], hb[jx].w, lg, 0, 0, 0);
-        }
+        for (int jx = 0; jx < 4; ++jx) actor16_head_frag(W.aw2, 4 * jx, hb[jx], lg);
         if (A.logits && row_ok) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -447,15 +462,10 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
             if (noise_l) {   // (logits past OUT: rows of W2 / b2 that are zero, never candidates below)
                 p[0] = lg[0] - nzv.x; p[1] = lg[1] - nzv.y; p[2] = lg[2] - nzv.z; p[3] = lg[3] - nzv.w;
             } else if (4 * kq < OUT) {  // wave-divergent only by row group
-                const uint32_t blk = (uint32_t)kq, tag = ((blk & 1u) << 31) | ((blk >> 1) << 30);
-                uint32_t u[4];
-                pw_philox4x32_10((uint32_t)grow, (uint32_t)((uint64_t)grow >> 32) | tag, (uint32_t)step, (uint32_t)(step >> 32),
-                                 (uint32_t)A.seed, (uint32_t)(A.seed >> 32), u);
+                float nz[4];
+                pw_gumbel_noise4(A.seed, step, grow, (uint32_t)kq, nz);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float uo = pw_gumbel_uniform(u[i]);  // in (0, 1)
-                    p[i] = lg[i] - __logf(-__logf(uo));
-                }
+                for (int i = 0; i < 4; ++i) p[i] = lg[i] - nz[i];
             }
             // one arg-max per head (first maximum wins), written as selects: both heads' scans and exchanges are straight-line code
             int bests[2] = {0, 0};

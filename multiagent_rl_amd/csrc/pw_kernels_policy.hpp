@@ -296,9 +296,26 @@ __global__ void __launch_bounds__(256) pw_actor_front_kernel(const float *__rest
     }
 }
 
+// The Gumbel noise of every actor head in the library: value (row, logit o) = log(-log(u)), u = word (o & 3) of Philox4x32-10 block
+// (o >> 2) keyed (seed; step, global row); the block index sits in the two top bits of counter word 1 (block 1 = 0x80000000).
+// -> the four values of block `blk` of row `grow`: exactly what the lanes of MFMA row group blk need for their four logits.
+__device__ __forceinline__ void pw_gumbel_noise4(const uint64_t seed, const uint64_t step, const long grow, const uint32_t blk,
+                                                 float (&nz)[4])
+{
+    const uint32_t tag = ((blk & 1u) << 31) | ((blk >> 1) << 30);
+    uint32_t u[4];
+    pw_philox4x32_10((uint32_t)grow, (uint32_t)((uint64_t)grow >> 32) | tag, (uint32_t)step, (uint32_t)(step >> 32),
+                     (uint32_t)seed, (uint32_t)(seed >> 32), u);
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const float uo = pw_gumbel_uniform(u[w]);  // in (0, 1)
+        nz[w] = __logf(-__logf(uo));
+    }
+}
+
 // Output head: logits = H * W2^T + b2 (64 -> 5) for one (env, agent) row per lane, then the hard
-// Gumbel-softmax sample of ddpg_gumbel_fix.py:109-116 as argmax(logits + g), g = -log(-log(u)),
-// u from Philox4x32-10 keyed (seed; step, row) -- the action stays an int32 index in HBM.
+// Gumbel-softmax sample of ddpg_gumbel_fix.py:109-116 as argmax(logits + g), g = -log(-log(u)) (pw_gumbel_noise4)
+// -- the action stays an int32 index in HBM.
 __global__ void __launch_bounds__(256) pw_actor_head_kernel(const float *__restrict__ H, const float *__restrict__ w2,
                                                             const float *__restrict__ b2, const long rows,
                                                             const uint64_t seed, uint64_t step,
@@ -328,17 +345,14 @@ __global__ void __launch_bounds__(256) pw_actor_head_kernel(const float *__restr
         for (int o = 0; o < 5; ++o) logits[(size_t)r * 5 + o] = acc[o];
     }
     if (act) {
-        uint32_t u[8];
-        pw_philox4x32_10((uint32_t)r, (uint32_t)((uint64_t)r >> 32), (uint32_t)step, (uint32_t)(step >> 32),
-                         (uint32_t)seed, (uint32_t)(seed >> 32), u);
-        pw_philox4x32_10((uint32_t)r, (uint32_t)((uint64_t)r >> 32) | 0x80000000u, (uint32_t)step, (uint32_t)(step >> 32),
-                         (uint32_t)seed, (uint32_t)(seed >> 32), u + 4);
+        float nz[2][4];
+        pw_gumbel_noise4(seed, step, r, 0, nz[0]);
+        pw_gumbel_noise4(seed, step, r, 1, nz[1]);
         int best = 0;
         float bv = 0.0f;
 #pragma unroll
         for (int o = 0; o < 5; ++o) {
-            const float uo = pw_gumbel_uniform(u[o]);  // in (0, 1)
-            const float v = acc[o] - __logf(-__logf(uo));
+            const float v = acc[o] - nz[o >> 2][o & 3];
             if (o == 0 || v > bv) { bv = v; best = o; }
         }
         act[r] = best;
@@ -595,8 +609,7 @@ __device__ __forceinline__ void actor_forward_wg(const ActorFusedArgs &A, const 
         const long grow = row_base + r;
         if (A.logits) A.logits[(size_t)grow * OUT + o] = acc;
         if (sample) {
-            // uniform o of a row = word (o & 3) of Philox block (o >> 2); the block index sits in the two top bits
-            // of counter word 1 (block 1 = 0x80000000, as pw_actor_head_kernel's second call)
+            // pw_gumbel_noise4's key and logarithms for ONE word of the block (all four logarithms here cost 96 instructions per row)
             const uint32_t blk = (uint32_t)o >> 2, tag = ((blk & 1u) << 31) | ((blk >> 1) << 30);
             uint32_t u[4];
             pw_philox4x32_10((uint32_t)grow, (uint32_t)((uint64_t)grow >> 32) | tag, (uint32_t)step, (uint32_t)(step >> 32),

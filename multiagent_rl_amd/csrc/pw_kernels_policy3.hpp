@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
     const uint64_t step0 = A.step_dev ? (uint64_t)*A.step_dev : A.step;
     constexpr int OUT = 5;  // one 5-logit head (checked on the host)
 
-    // ---- constants -> LDS (once)
+    // ---- constants -> LDS (once): actor16_load's LDS part, and b2
     {
         const float4 *src = reinterpret_cast<const float4 *>(A.frag + 8 * 2 * 4 * 64 * 4);
         for (int f = tid; f < (2 * S1 * 64) / 4; f += 512) reinterpret_cast<float4 *>(S.f_w1)[f] = src[f];
@@ -103,9 +103,9 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
         if (tid < OUT) S.s_b2[tid] = A.b2[tid];
     }
 
-    // Gumbel noise of one head evaluation: value (row, logit o) = log(-log(u)), u = word (o & 3) of Philox block (o >> 2) keyed
-    // (seed; step, global row) exactly as actor_forward_wg / pw_actor_head_kernel.  One thread per (row, block) -- the four
-    // words of a block serve four logits -- called by `nthr` threads (t0 = their index)
+    // Gumbel noise of one head evaluation into the plane [rows][5]: pw_gumbel_noise4's key and logarithms, the latter for the five words that
+    // serve a logit only (kept inline: profiles/actor16_core_codegen.txt).  One thread per (row, block) -- the four words of a block serve four
+    // logits -- called by `nthr` threads (t0 = their index)
     auto draw_noise = [&](const uint64_t step, const int t0, const int nthr) {
         constexpr int NB = (OUT + 3) / 4;
         for (int idx = t0; idx < rows_here * NB; idx += nthr) {
@@ -127,10 +127,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
     };
 
     // ---- environment lanes (as the other forms): wave w < n_env_waves owns local envs [w * epw, ...)
-    const int epw_max = E < kWave / N ? E : kWave / N;
-    const int waves_full = (E + epw_max - 1) / epw_max;
-    const int epw = (E + waves_full - 1) / waves_full;
-    const int n_env_waves = (envs_here + epw - 1) / epw;  // <= 8 (N <= 32)
+    const EnvWaves ewv = env_waves(E, N, envs_here);
+    const int epw = ewv.epw, n_env_waves = ewv.n_waves;  // <= 8 (N <= 32)
     // the LAST waves: after a step they finish its rewards and stores while the first waves (dense1 blocks are dealt from
     // wave 0 up) already work on the next one
     const int ew = wave - (8 - n_env_waves);
@@ -171,9 +169,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
     }
     const float k = V.contact_margin, cf = V.contact_force, dt = V.dt, damp = V.damp, mass = V.mass;
 
-    // ---- this wave's resident weights.  MFMA 16x16x4 lane roles: as A operand lane = (tile row ar = lane % 16, k quarter
-    // kq = lane / 16); as B operand / accumulator lane = (column n = lane % 16, kq resp. row group rg = lane / 16).
-    // Tile row ar = 4 * (unit within tile) + gate: W row gate * 32 + hq * 8 + 4 * tile + ar / 4 of direction dir.
+    // ---- this wave's resident weights: actor16_load's register part with OUT = 5 (lane roles: Actor16W) (kept inline: profiles/actor16_core_codegen.txt)
     const int dir = wave >> 2, hq = wave & 3;
     const int n16 = lane & 15, kq = lane >> 4;
     float aih[2][16], ahh[2][8], bias[2][4];
@@ -204,35 +200,20 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
     wg_lds_barrier();  // first observation rows and first noise in LDS
     PW_R2_DECL;
 
-    // the head on the matrix cores: logits^T [16 (5 used) x 16 rows] = W2 [16 x 64] * relu(h)^T per 16-row tile, C-in = b2, k
-    // ascending -- the chain of actor_forward_wg's head (b2, then one fused multiply-add per hidden unit) -- then minus the
-    // Gumbel noise and the arg-max (first maximum wins) in the lanes: row group 0 holds logits 0..3 of its row, row group 1
-    // logit 4.  Wave w serves tiles w, w + 8, ..; one barrier afterwards.
+    // the head on the matrix cores: logits^T [16 (5 used) x 16 rows] = W2 [16 x 64] * relu(h)^T per 16-row tile, C-in = b2
+    // (actor16_head_chain), then minus the Gumbel noise and the arg-max in the lanes (first maximum wins: row group 0 holds
+    // logits 0..3 of its row, row group 1 logit 4).  Wave w serves tiles w, w + 8, ..; one barrier afterwards.
     auto head = [&]() {
         const int ntile = (rows_here + 15) >> 4;
         for (int tile = wave; tile < ntile; tile += 8) {
             f32x4 lg;
 #pragma unroll
             for (int i = 0; i < 4; ++i) lg[i] = 4 * kq + i < OUT ? S.s_b2[4 * kq + i] : 0.0f;
-            const float4 *hf = S.s_hf + (tile * 4) * 64 + lane;
-#pragma unroll
-            for (int jx = 0; jx < 4; ++jx) {
-                const float4 b = hf[jx * 64];
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 0], b.x, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 1], b.y, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 2], b.z, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 3], b.w, lg, 0, 0, 0);
-            }
+            actor16_head_chain(aw2, 0, 4, S.s_hf + (tile * 4) * 64 + lane, false, lg);
             const int rr = tile * 16 + n16;
             const float *nz = S.s_noise + (rr < rows_here ? rr : 0) * OUT;
             const float p0 = lg[0] - nz[kq == 1 ? 4 : 0], p1 = lg[1] - nz[1], p2 = lg[2] - nz[2], p3 = lg[3] - nz[3];
-            const float p4 = __shfl(p0, n16 + 16, kWave);  // logit 4 lives in register 0 of row group 1
-            int best = 0;
-            float bv = p0;
-            if (p1 > bv) { bv = p1; best = 1; }
-            if (p2 > bv) { bv = p2; best = 2; }
-            if (p3 > bv) { bv = p3; best = 3; }
-            if (p4 > bv) { bv = p4; best = 4; }
+            const int best = actor16_argmax5(p0, p1, p2, p3, __shfl(p0, n16 + 16, kWave));   // logit 4 lives in register 0 of row group 1
             if (kq == 0 && rr < rows_here) S.s_act[rr] = best;
         }
         wg_lds_barrier();
@@ -282,10 +263,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
             else ep_ret = rsum;
         }
     };
-    // `opaque`: the lane's launch-invariant global index passes through an empty asm wherever it feeds an output address -- otherwise every
-    // `pointer + g` of the step's stores is computed once per launch and kept in a register pair for the whole kernel (what pushed the widest
-    // instantiations over the 256-register cap: pw_kernels_policy_tag.hpp has the same device).
-    auto opaque = [](const uint32_t v) { uint32_t x = v; asm volatile("" : "+v"(x)); return x; };
+    // the lane's launch-invariant global index goes through opaque() (pw_policy_shared.hpp) wherever it feeds an output address
     auto tail_stores = [&](const int t, const bool with_obs) {  // with_obs: V.obs too (no reset in between: the same row)
         const size_t tBN = (size_t)t * BN;
         const uint32_t g = opaque(g_lane);
@@ -395,7 +373,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
             inproj(dir ? N - 1 : 0, acc);
             for (int s2 = 0; s2 < N; ++s2) {
                 const int ts = dir ? N - 1 - s2 : s2;
-                if (s2 > 0) {
+                if (s2 > 0) {   // actor16_recur, kept inline here (profiles/actor16_core_codegen.txt)
                     const float4 *hx = S.s_hx + ((((s2 - 1) & 1) * 2 + dir) * 2) * 64 + lane;
                     const float4 h0 = hx[0], h1 = hx[64];
                     acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][0], h0.x, acc[0], 0, 0, 0);
@@ -419,10 +397,9 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
                 float h0v, h1v;
                 lstm_cell(acc[0][0], acc[0][1], acc[0][2], acc[0][3], c0, h0v);
                 lstm_cell(acc[1][0], acc[1][1], acc[1][2], acc[1][3], c1, h1v);
-                // h exchange: unit u = hq * 8 + 4 T + kq is k quarter kq of k step 2 hq + T: fragment j = hq / 2, elements
-                // (2 hq) % 4 + T of this very lane slot
+                // h exchange and head input: actor16_forward's two stores (kept inline: profiles/actor16_core_codegen.txt)
                 reinterpret_cast<float2 *>(S.s_hx + (((s2 & 1) * 2 + dir) * 2 + (hq >> 1)) * 64 + lane)[hq & 1] = make_float2(h0v, h1v);
-                if (seq_ok) {  // head input: row n16 * N + ts, k = dir * 32 + unit -> fragment 2 dir + hq / 2, same element pair
+                if (seq_ok) {
                     const int rr = n16 * N + ts;
                     reinterpret_cast<float2 *>(S.s_hf + ((rr >> 4) * 4 + 2 * dir + (hq >> 1)) * 64 + kq * 16 + (rr & 15))[hq & 1] =
                         make_float2(A.relu_out ? fmaxf(h0v, 0.0f) : h0v, A.relu_out ? fmaxf(h1v, 0.0f) : h1v);

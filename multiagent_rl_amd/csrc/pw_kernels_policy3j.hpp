@@ -118,10 +118,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
 
     // ---- environment lanes.  The environments of the workgroup are dealt to "virtual waves" of epw environments each (lane = (env, agent));
     // environment wave ew (the LAST n_env_waves waves) serves virtual waves ew, ew + 8, ... one after the other (slots).
-    const int epw_max = E < kWave / N ? E : kWave / N;
-    const int vwaves_full = (E + epw_max - 1) / epw_max;
-    const int epw = (E + vwaves_full - 1) / vwaves_full;
-    const int n_vwaves = (envs_here + epw - 1) / epw;
+    const EnvWaves ewv = env_waves(E, N, envs_here);
+    const int epw = ewv.epw, n_vwaves = ewv.n_waves;
     const int n_env_waves = n_vwaves < 8 ? n_vwaves : 8;
     const int ew = wave - (8 - n_env_waves);
     const bool env_wave = ew >= 0;
@@ -184,7 +182,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
         }
     }
 
-    // ---- this wave's resident weights (lane roles: pw_kernels_actor16.hpp)
+    // ---- this wave's resident weights: actor16_load's register part with OUT = 5 (lane roles: Actor16W) (kept inline: profiles/actor16_core_codegen.txt)
     const int dir = wave >> 2, hq = wave & 3;
     const int n16 = lane & 15, kq = lane >> 4;
     float aih[2][16], ahh[2][8], bias[2][4];
@@ -204,8 +202,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
     float aw2[16];
 #pragma unroll
     for (int sx = 0; sx < 16; ++sx) aw2[sx] = n16 < OUT ? A.w2[n16 * 64 + 4 * sx + kq] : 0.0f;
-    // dense1: A fragments of rows 16 hq .. 16 hq + 15 of W1 (lane = (row n16, k quarter kq)) out of the packed 32x32x2 image
-    // [2 m][S1][64 lane] (lane = row % 32 + 32 (k & 1), k step k / 2; zero beyond D), and the bias of this lane's accumulator rows
+    // dense1: W1's 16 x 16 tile fragments and the bias of this lane's accumulator rows -- actor16_load_d1's body (kept inline: profiles/actor16_core_codegen.txt)
     float a1[KS], b1v[4];
     {
         const float *w1p = A.frag + 8 * 2 * 4 * 64 * 4;
@@ -222,31 +219,13 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
     const int nseq = seq_ok ? n16 : 0;   // columns past the environments of this workgroup read env 0; nobody uses their results
     wg_lds_barrier();  // constants, first states and landmarks in LDS
 
-    // Gumbel noise of logits 4 kq .. 4 kq + 3 of global row `grow`, drawn IN the lanes that subtract it: value (row, logit o) = log(-log(u)),
-    // u = word (o & 3) of Philox block (o >> 2) keyed (seed; step, global row) -- the keying of every other form -- so row group 0 (logits
-    // 0..3) needs block 0 and row group 1 (logit 4) block 1 of its row: no noise plane in LDS.  Then the arg-max (first maximum wins).
+    // Gumbel noise of logits 4 kq .. 4 kq + 3 of global row `grow`, drawn IN the lanes that subtract it (pw_gumbel_noise4: row group 0
+    // needs block 0 and row group 1, for logit 4, block 1 of its row): no noise plane in LDS.  Then the arg-max (first maximum wins).
     auto sample = [&](const f32x4 lg, const long grow, const uint64_t step) {
         float nz[4] = {0.f, 0.f, 0.f, 0.f};
-        if (kq < 2) {  // wave-divergent only by row group
-            const uint32_t blk = (uint32_t)kq, tag = ((blk & 1u) << 31) | ((blk >> 1) << 30);
-            uint32_t u[4];
-            pw_philox4x32_10((uint32_t)grow, (uint32_t)((uint64_t)grow >> 32) | tag, (uint32_t)step, (uint32_t)(step >> 32),
-                             (uint32_t)A.seed, (uint32_t)(A.seed >> 32), u);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float uo = pw_gumbel_uniform(u[i]);  // in (0, 1)
-                nz[i] = __logf(-__logf(uo));
-            }
-        }
+        if (kq < 2) pw_gumbel_noise4(A.seed, step, grow, (uint32_t)kq, nz);  // wave-divergent only by row group
         const float p0 = lg[0] - nz[0], p1 = lg[1] - nz[1], p2 = lg[2] - nz[2], p3 = lg[3] - nz[3];
-        const float p4 = lane_xor16(p0);              // logit 4 lives in register 0 of row group 1
-        int bi = 0;
-        float bv = p0;
-        if (p1 > bv) { bv = p1; bi = 1; }
-        if (p2 > bv) { bv = p2; bi = 2; }
-        if (p3 > bv) { bv = p3; bi = 3; }
-        if (p4 > bv) { bv = p4; bi = 4; }
-        return bi;
+        return actor16_argmax5(p0, p1, p2, p3, lane_xor16(p0));   // logit 4 lives in register 0 of row group 1
     };
     auto head_b2 = [&]() {
         f32x4 lg;
@@ -259,15 +238,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
         const int ntile = (rows_here + 15) >> 4;
         for (int tile = wave; tile < ntile; tile += 8) {
             f32x4 lg = head_b2();
-            const float4 *hf = S.s_hf + (tile * 4) * 64 + lane;
-#pragma unroll
-            for (int jx = 0; jx < 4; ++jx) {
-                const float4 b = hf[jx * 64];
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 0], b.x, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 1], b.y, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 2], b.z, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[4 * jx + 3], b.w, lg, 0, 0, 0);
-            }
+            actor16_head_chain(aw2, 0, 4, S.s_hf + (tile * 4) * 64 + lane, false, lg);
             const int rr = tile * 16 + n16;
             const int rq = rr < rows_here ? rr : 0, re = rq / NP, ra = rq - re * NP;   // LDS row -> (environment, agent)
             const int bi = sample(lg, row_base + (long)re * N + (ra < N ? ra : 0), step);   // the TRUE global row keys the noise
@@ -278,19 +249,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
     // HALF: the head of ONE timestep (its 16 sequences are the 16 columns) from the two directions' h fragments ([2 j][64 lane] each)
     auto head_ts = [&](const int ts, const float4 *hF, const float4 *hB, const uint64_t step) {
         f32x4 lg = head_b2();
-        auto half = [&](const float4 *hx, const int s0) {
-#pragma unroll
-            for (int jx = 0; jx < 2; ++jx) {
-                float4 b = hx[jx * 64 + lane];
-                if (A.relu_out) { b.x = fmaxf(b.x, 0.0f); b.y = fmaxf(b.y, 0.0f); b.z = fmaxf(b.z, 0.0f); b.w = fmaxf(b.w, 0.0f); }
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 4 * jx + 0], b.x, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 4 * jx + 1], b.y, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 4 * jx + 2], b.z, lg, 0, 0, 0);
-                lg = __builtin_amdgcn_mfma_f32_16x16x4f32(aw2[s0 + 4 * jx + 3], b.w, lg, 0, 0, 0);
-            }
-        };
-        half(hF, 0);   // k = 0 .. 31: the forward direction's units
-        half(hB, 8);   // k = 32 .. 63: the backward direction's
+        actor16_head_chain(aw2, 0, 2, hF + lane, A.relu_out, lg);   // k = 0 .. 31: the forward direction's units
+        actor16_head_chain(aw2, 8, 2, hB + lane, A.relu_out, lg);   // k = 32 .. 63: the backward direction's
         // the logits replace the stored half (this wave just consumed it; nobody else reads it): [64 lane] float4 of the timestep's slot.
         // Noise and arg-max follow after the loop, on all eight waves at once (inside the loop they sat on the critical path of two).
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -323,7 +283,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
         float v[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = fmaxf(acc[i] + b1v[i], 0.0f);
-        float4 *dst = S.s_xf + ((buf * 2 + dir) * 4 + hq) * 64 + n16;
+        float4 *dst = S.s_xf + ((buf * 2 + dir) * 4 + hq) * 64 + n16;   // actor16_forward's tile store into slot buf * 2 + dir (kept inline: profiles/actor16_core_codegen.txt)
         reinterpret_cast<float2 *>(dst + (kq & 1) * 16)[kq >> 1] = make_float2(v[0], v[2]);
         reinterpret_cast<float2 *>(dst + (2 + (kq & 1)) * 16)[kq >> 1] = make_float2(v[1], v[3]);
     };
@@ -462,29 +422,11 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
                     if (2 * tsF > N - 1 && wave == ((2 * p) & 7)) head_ts(tsF, hxp, S.s_hf + tsF * 128, step);            // backward was there first
                     if (2 * tsB <= N - 1 && wave == ((2 * p + 5) & 7)) head_ts(tsB, S.s_hf + tsB * 128, hxp + 128, step);   // forward was there first
                 }
-                if (s2 > 0) {
-                    const float4 *hx = S.s_hx + ((((s2 - 1) & 1) * 2 + dir) * 2) * 64 + lane;
-                    const float4 h0 = hx[0], h1 = hx[64];
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][0], h0.x, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][0], h0.x, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][1], h0.y, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][1], h0.y, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][2], h0.z, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][2], h0.z, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][3], h0.w, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][3], h0.w, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][4], h1.x, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][4], h1.x, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][5], h1.y, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][5], h1.y, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][6], h1.z, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][6], h1.z, acc[1], 0, 0, 0);
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[0][7], h1.w, acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(ahh[1][7], h1.w, acc[1], 0, 0, 0);
-                }
+                if (s2 > 0) actor16_recur(S.s_hx, s2, dir, lane, ahh, acc);
                 float h0v, h1v;
                 lstm_cell(acc[0][0], acc[0][1], acc[0][2], acc[0][3], c0, h0v);
                 lstm_cell(acc[1][0], acc[1][1], acc[1][2], acc[1][3], c1, h1v);
+                // h exchange and (!HALF) head input: actor16_forward's two stores (kept inline: profiles/actor16_core_codegen.txt)
                 reinterpret_cast<float2 *>(S.s_hx + (((s2 & 1) * 2 + dir) * 2 + (hq >> 1)) * 64 + lane)[hq & 1] = make_float2(h0v, h1v);
                 if (HALF) {
                     // this direction is the FIRST visitor of ts (forward: 2 ts <= N - 1, backward: 2 ts > N - 1): its h(ts) is kept for the head

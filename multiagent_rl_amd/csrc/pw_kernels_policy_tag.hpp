@@ -67,10 +67,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
     const long row_base = env0 * N;
     const size_t BN = (size_t)A.B * N;
 
-    const int epw_max = A.E < kWave / N ? A.E : kWave / N;
-    const int waves_full = (A.E + epw_max - 1) / epw_max;
-    const int epw = (A.E + waves_full - 1) / waves_full;
-    const int n_env_waves = (envs_here + epw - 1) / epw;
+    const EnvWaves ewv = env_waves(A.E, N, envs_here);
+    const int epw = ewv.epw, n_env_waves = ewv.n_waves;
     // the LAST waves: the tail of an environment step (partner pass, rewards, stores) then runs beside the next actor pass's
     // dense1 blocks and head tiles, which are dealt from wave 0 up (actor16_forward's pre / mid windows)
     const int ewi = wave - (8 - n_env_waves);
@@ -200,11 +198,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
             else ep_ret = rsum;
         }
     };
-    // `opaque`: the lane's launch-invariant indices (g, r) pass through an empty asm wherever they feed an output address.  Without it
-    // the compiler computes every `pointer + g` of the step's stores once per launch and keeps the 64-bit results in registers for
-    // the whole kernel -- that is what pushed this kernel over the 256-register cap and into scratch memory; a few address
-    // additions per step are cheaper than three scratch reloads.
-    auto opaque = [](const uint32_t v) { uint32_t x = v; asm volatile("" : "+v"(x)); return x; };
+    // the lane's launch-invariant indices (g, r) go through opaque() (pw_policy_shared.hpp) wherever they feed an output address
     auto tail_stores = [&](const int t, const bool with_obs) {  // with_obs: V.obs too (no reset in between: the same row)
         const size_t tBN = (size_t)t * BN;
         const uint32_t g = opaque(g_lane);

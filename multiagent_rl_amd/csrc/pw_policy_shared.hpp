@@ -1,6 +1,7 @@
 // pw_policy_shared.hpp -- part of libpworld.so (translation unit csrc/pworld_policy.hip includes it).
-// Helpers shared by the one-launch policy rollout kernels (pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp): the LDS observation
-// row writer, the ordered shuffles, the ring-sink helpers and the stamp / debug macros of the PW_STAMPS probe builds.
+// Helpers shared by the one-launch policy rollout kernels (pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp, pw_kernels_policy_tag.hpp):
+// the LDS observation row writer, the environment-lane split, opaque(), the ordered shuffles, the ring-sink helpers and the stamp /
+// debug macros of the PW_STAMPS probe builds.
 #pragma once
 
 #include "pw_common.hpp"
@@ -36,6 +37,32 @@ __device__ __forceinline__ void lds_write_obs_row(float *o, const int L, const f
             o2[2 + l] = make_float2(q.x - px, q.y - py);
         }
     }
+}
+
+// Environment lanes of a workgroup of E environments with N agents each (lane = (environment, agent), whole environments per wave):
+// as few waves as hold E, the environments spread evenly over them -> epw environments per wave, and the waves that the
+// envs_here <= E environments of THIS workgroup occupy
+struct EnvWaves {
+    int epw, n_waves;
+};
+__device__ __forceinline__ EnvWaves env_waves(const int E, const int N, const int envs_here)
+{
+    const int epw_max = E < kWave / N ? E : kWave / N;
+    const int waves_full = (E + epw_max - 1) / epw_max;
+    EnvWaves w;
+    w.epw = (E + waves_full - 1) / waves_full;
+    w.n_waves = (envs_here + w.epw - 1) / w.epw;
+    return w;
+}
+
+// A lane's launch-invariant global index passes through this empty asm wherever it feeds an output address: otherwise every
+// `pointer + g` of a step's stores is computed once per launch and kept in a register pair for the whole kernel -- what pushed the
+// widest rollout instantiations over the 256-register cap and into scratch memory; a few address additions per step are cheaper
+__device__ __forceinline__ uint32_t opaque(const uint32_t v)
+{
+    uint32_t x = v;
+    asm volatile("" : "+v"(x));
+    return x;
 }
 
 #ifdef PW_STAMPS

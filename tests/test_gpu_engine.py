@@ -361,6 +361,49 @@ def test_bf16x3_mode_in_the_one_launch_rollout():
     assert abs(a['rew_shared'].mean().item() - b['rew_shared'].mean().item()) < 0.05 * abs(a['rew_shared'].mean().item())
 
 
+@pytest.mark.parametrize('B,N', [(33, 6), (37, 7), (9, 12)])
+def test_bf16x3_one_launch_rollout_equals_the_bf16x3_step_loop(B, N):
+    """The bf16x3 mode is not exact against float32, but it is ONE arithmetic: pw_policy_rollout3_kernel<.., BF3 = true> and the step
+    loop of pw_actor_fused16_kernel<.., true> + env.step() run the same input projection on the same operands, so sampled actions,
+    observations, rewards, terminals, pre-reset observations and the final world state must be IDENTICAL.  (33, 6): the NT = 6
+    instantiation; (37, 7): runtime N, ragged last workgroup; (9, 12): the largest N that keeps 16 columns, B < 16.  max_episode_len
+    = 25 and T = 27: a reset falls inside."""
+    from multiagent_rl_amd import _lib, make_batched_env
+    from multiagent_rl_amd.policy import ActorNetwork, FusedActor
+    lib = _lib.load()
+    T = 27
+    torch.manual_seed(4)
+    mk = lambda: make_batched_env('simple_spread', B, n=N, auto_reset=True, max_episode_len=25, seed=21)  # noqa: E731
+    env_a, env_b = mk(), mk()
+    env_b.set_actor_precision('bf16x3')
+    actor = ActorNetwork(env_a.obs_dim, 5).cuda().eval()
+    loop, one = FusedActor(actor, seed=9), FusedActor(actor, seed=9)
+    obs = env_a.reset()
+    env_b.reset()
+    want = dict(obs=[], act=[], rew=[], rew_shared=[], terminal=[], final_obs=[])
+    prev = lib.pw_actor_set_bf16x3(1)
+    try:
+        for t in range(T):
+            act = loop(obs)
+            obs, rew, done, info = env_a.step(act)
+            for k, v in (('obs', obs), ('act', act), ('rew', rew), ('rew_shared', info['rew_shared']),
+                         ('terminal', info['terminal']), ('final_obs', info['final_obs'])):
+                want[k].append(v.clone())
+        torch.cuda.synchronize()
+    finally:
+        lib.pw_actor_set_bf16x3(prev)
+    got = one.rollout(env_b, T)
+    assert env_b.last_kernel() == 'pw_policy_rollout3_kernel<bf16x3>'
+    for k in ('act', 'obs', 'rew', 'rew_shared', 'terminal'):
+        assert torch.equal(got[k], torch.stack(want[k])), k
+    term = got['terminal']
+    assert term.any()
+    assert torch.equal(got['final_obs'][term], torch.stack(want['final_obs'])[term])
+    sa, sb = env_a.get_state(), env_b.get_state()
+    for k in ('pos', 'vel', 'landmarks', 'ep_step', 'ep_count'):
+        assert torch.equal(sa[k], sb[k]), k
+
+
 def test_fused_gumbel_sampling_distribution():
     """act = argmax(logits + Gumbel): frequencies follow softmax(logits); streams differ per call and row."""
     from multiagent_rl_amd.policy import ActorNetwork, FusedActor
