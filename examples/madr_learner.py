@@ -13,6 +13,9 @@ and the TD target formed on ``[b, N]``.
 (``multiagent_rl_amd.optim.FusedAdam``); the default is the stock sequence.
 ``Trainer(..., fused_lstm=True)``: the LSTMs of actor and critic (and of the target networks copied from them) run their recurrence,
 forward and backward, on the HIP kernels (``multiagent_rl_amd.lstm.fuse_lstm``); the default is ``nn.LSTM``.
+``Trainer(..., fused_attention=True)``: the attention block of an attention critic (and of the target critic copied from it) runs,
+forward and backward, on the HIP kernels (``multiagent_rl_amd.attention.fuse_attention``); the default is the stock expression, and a
+critic without that block is left as it is.
 """
 import copy
 import os
@@ -42,9 +45,12 @@ class Trainer(object):
     per_agent = False   # BiCNetTrainer: per-agent rewards / dones [b,N] and a critic that returns [b,N,1]
 
     def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
-                 fused_lstm=False):
+                 fused_lstm=False, fused_attention=False):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
+        if fused_attention:   # before the deep copies, like fused_lstm
+            from multiagent_rl_amd.attention import fuse_attention
+            fuse_attention(self.critic)
         if fused_lstm:   # before the deep copies: a class swap survives them, so the target networks are fused too
             from multiagent_rl_amd.lstm import fuse_lstm
             fuse_lstm(self.actor)

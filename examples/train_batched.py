@@ -18,7 +18,9 @@ transitions (``train_batched(per_agent_transition=True)``), ``multiagent_rl_amd.
 forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
 soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch, or ``accelerate_trainer(.., optimizer=True)`` with
 ``--reference``), ``--fused-lstm`` runs the recurrence of the learner's LSTMs with gradient on the HIP kernels
-(``multiagent_rl_amd.lstm``: the learner's own ``fused_lstm`` switch, or ``accelerate_trainer(.., lstm=True)`` with ``--reference``).
+(``multiagent_rl_amd.lstm``: the learner's own ``fused_lstm`` switch, or ``accelerate_trainer(.., lstm=True)`` with ``--reference``),
+``--fused-attention`` runs the attention critic's attention block with gradient on the HIP kernels (``multiagent_rl_amd.attention``: the
+learner's own ``fused_attention`` switch, or ``accelerate_trainer(.., attention=True)`` with ``--reference``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -66,7 +68,13 @@ def main(argv=None):
                     help="the learner's LSTMs run their recurrence, forward and backward, on the HIP kernels (madr_learner's fused_lstm "
                          'switch; with --reference: accelerate_trainer(.., lstm=True)); off by default: losses differ from '
                          "MIOpen's in the last bits")
+    ap.add_argument('--fused-attention', action='store_true',
+                    help="the attention block of the learner's critic runs, forward and backward, on the HIP kernels (madr_learner's "
+                         'fused_attention switch; with --reference: accelerate_trainer(.., attention=True)); needs the attention '
+                         'critic; off by default: losses differ from the stock expression in the last bits')
     args = ap.parse_args(argv)
+    if args.fused_attention and args.critic != 'attention' and not args.reference:
+        ap.error('--fused-attention needs --critic attention (the block exists in the LSTM + attention critic only)')
     if args.fused_targets and args.critic not in ('attention', 'bicnet') and not args.reference:
         ap.error('--fused-targets needs --critic attention or --critic bicnet (the HIP critics are the LSTM architectures)')
     bicnet = args.critic == 'bicnet'
@@ -92,7 +100,7 @@ def main(argv=None):
         from madr_learner import CriticNetwork, Trainer
         if args.critic == 'attention':
             from multiagent_rl_amd.critic import CriticNetwork
-    if args.fused_targets or args.fused_optimizer or args.fused_lstm:
+    if args.fused_targets or args.fused_optimizer or args.fused_lstm or args.fused_attention:
         from multiagent_rl_amd.policy import accelerate_trainer
         plain_trainer = Trainer
 
@@ -101,10 +109,12 @@ def main(argv=None):
                 k['fused_optimizer'] = True
             if args.fused_lstm and not args.reference:
                 k['fused_lstm'] = True
+            if args.fused_attention and not args.reference:
+                k['fused_attention'] = True
             learner = plain_trainer(*a, **k)
             if args.fused_targets or args.reference:
                 accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
-                                   lstm=args.fused_lstm and args.reference)
+                                   lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

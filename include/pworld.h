@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 113 /* 0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 114 /* 0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -622,6 +622,20 @@ int pw_lstm_train_forward(const float *G, const float *w_hh_fw, const float *w_h
  * The gradients of W_hh (dG^T against the shifted Y), W_ih, the biases and x are GEMMs and the caller's (multiagent_rl_amd/lstm.py). */
 int pw_lstm_train_backward(const float *dY, const float *saved, const float *w_hh_fw, const float *w_hh_bw, int64_t b,
                            int32_t N, int32_t dirs, int32_t H, float *dG, void *stream);
+
+/* The attention block of CriticNetwork WITH gradient (csrc/pw_kernels_attention.hpp), one launch each, for the learner's two critic
+ * passes per update.  Y [b,N,H] is the LSTM's output; the query is its last step, q = Y[:, N-1] (h_n[-1] of a one-direction LSTM).
+ *   s_t = <Y_t, q>;  w = softmax_t(s) (maximum subtracted, expf as in pw_critic_forward);  c = sum_t w_t Y_t, t ascending;
+ *   out [b,H] = relu ? max(c, 0) : c;  weight [b,N] = w, or NULL: nothing is stored (no gradient wanted).
+ * Served: H = 64, 1 <= N <= 64 (pw_critic_forward's agent-axis bound), b >= 1.  Everything else, a null required pointer or a
+ * pointer that is not 4-byte aligned (all loads and stores are 4 bytes wide): PW_EINVAL naming the argument, nothing launched.
+ * No atomics, fixed summation order: the same inputs give the same bits, with and without weight, on any stream. */
+int pw_attention_pool_forward(const float *Y, int64_t b, int32_t N, int32_t H, int32_t relu, float *out, float *weight, void *stream);
+/* dOut [b,H] contiguous, Y, weight and out as the forward read and wrote them -> dY [b,N,H]:
+ *   dc = relu ? dOut [out > 0] : dOut;  dw_t = <Y_t, dc>;  ds_t = w_t (dw_t - sum_u w_u dw_u);  dY_t = w_t dc + ds_t q;
+ *   dY_{N-1} += dq = sum_t ds_t Y_t (t ascending): the last step receives its score's gradient as a step and as the query. */
+int pw_attention_pool_backward(const float *dOut, const float *Y, const float *weight, const float *out, int64_t b, int32_t N,
+                               int32_t H, int32_t relu, float *dY, void *stream);
 
 #ifdef __cplusplus
 }

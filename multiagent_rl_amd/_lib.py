@@ -174,6 +174,8 @@ SIGNATURES = {
                                  C.c_void_p]),
     'pw_lstm_train_forward': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     'pw_lstm_train_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
+    'pw_attention_pool_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    'pw_attention_pool_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
 }
 
 

@@ -323,7 +323,7 @@ class FusedExploration(object):
         return [eye[0][idx[..., 0]], eye[1][idx[..., 1]]]
 
 
-def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False):
+def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -344,7 +344,13 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     ``lstm=True`` runs the recurrent part of every served ``nn.LSTM`` the trainer owns -- actor, critic, and the target networks unless
     ``targets=True`` has already wrapped them -- on the HIP kernels with gradient (``multiagent_rl_amd.lstm.fuse_lstm``: a class swap,
     parameters and ``state_dict`` keys unchanged).  Opt-in like the other two: the kernels' gate activations differ from MIOpen's in
-    the last bits, so a seeded run does not reproduce across the switch."""
+    the last bits, so a seeded run does not reproduce across the switch.
+
+    ``attention=True`` runs the attention block of ``trainer.critic`` -- and of ``trainer.target_critic`` unless ``targets=True`` has
+    already wrapped it -- on the HIP kernels with gradient (``multiagent_rl_amd.attention.fuse_attention``: a class swap to a subclass
+    of the critic's own class, one launch forward and one backward instead of ``bmm`` / ``softmax`` / ``bmm`` / ``relu``).  A critic
+    without that block (the BiCNet critic, the model-learning variant) is left as it is.  Opt-in for the same reason: the sums run in
+    another order than rocBLAS's."""
     fx = FusedExploration(trainer.actor, getattr(trainer, 'action_type', 'Discrete'), seed=seed)
     trainer.get_exploration_action = fx.get_exploration_action
     target_actor = None
@@ -358,6 +364,9 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     if lstm:
         from .lstm import fuse_trainer
         fx.fused_lstms = fuse_trainer(trainer)
+    if attention:
+        from .attention import fuse_trainer as fuse_attention_trainer
+        fx.fused_attentions = fuse_attention_trainer(trainer)
 
     def _wrap(name):
         inner = getattr(trainer, name, None)
