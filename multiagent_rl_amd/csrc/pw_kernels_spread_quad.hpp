@@ -19,10 +19,11 @@ namespace {
 //                 LDS (wave shuffles were measured: slower); the env's 6 agent lanes then add their row in ascending partner order (the upstream
 //                 accumulation order, so the bits do not change; far pairs contribute +-0, which cannot change an
 //                 accumulator that is never -0), integrate and publish {pos, vel} into the ring.
-//   wave OA       8 envs, one step behind (as the duo kernel's O): collision masks, landmark minima, rewards, shared
-//                 reward, done / terminal stores.
+//   wave OA       8 envs, one step behind (as the duo kernel's O): landmark minima, rewards, shared reward.
 //   wave OB       8 envs, one step behind: observation rows, stored as one contiguous block per step
-//                 (stream_write_obs_block), and the pre-reset rows at episode ends.
+//                 (stream_write_obs_block), and the pre-reset rows at episode ends; done / terminal stores; the collision
+//                 tests (counts handed to OA through LDS one step later, masks stored) -- the two output waves issue
+//                 about the same number of vector instructions per step (profiles/r7_quad_loop_census.txt).
 // One s_barrier per step.  The ring slot sequence is WORKGROUP-uniform: in a step in which ANY of the 8 envs resets,
 // every env publishes a pre-reset and a post-reset slot (identical for the envs that do not reset), so no wave needs
 // another env's slot index; each wave follows all 8 episode clocks itself.  Envs out of step with each other can make
@@ -96,7 +97,28 @@ __device__ __forceinline__ void quad_pair_force(const float2 qi, const float2 qj
     }
 }
 
-// COLL: wave OA also stores the step's collision masks (pw_step_io.coll) -- it holds the six threshold tests anyway, so
+// The collision half of an output lane's step: the six threshold tests of the lane's agent `mine` against its env's agents
+// q6[0..5] (the self pair included: d2 = 0 passes, a NaN / inf position fails its own test), their number and, COLL, their
+// mask.  Wave OB runs it in every step, wave OA for a launch's last step only -- one body, so the two cannot drift apart.
+template <bool COLL>
+__device__ __forceinline__ void quad_coll_tests(const float2 mine, const float2 (&q6)[6], const float coll_thr2, int &cnt, uint32_t &cmask)
+{
+    cnt = 0; cmask = 0;
+#if defined(PW_EXPERIMENTS) && defined(PW_EXP_NO_COLL_TESTS)   // tools/experiments/pw_experiments.hpp: a timing-only build, which build_native.py refuses
+    cnt = 1;
+#else
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const float2 q = q6[j];
+        const float dx = q.x - mine.x, dy = q.y - mine.y;
+        const float d2 = dx * dx + dy * dy;
+        cnt += d2 < coll_thr2 ? 1 : 0;
+        if (COLL) cmask |= d2 < coll_thr2 ? 1u << j : 0u;
+    }
+#endif
+}
+
+// COLL: wave OB also stores the step's collision masks (pw_step_io.coll) -- it holds the six threshold tests anyway, so
 // the instantiation differs by one mask accumulation and one 8-byte store per lane and step; every other output is
 // bit-identical to the plain form (tests: the `quad+coll` path, and the bench-path test at C2 full size).
 // K1: the division by the contact margin inside the force runs as ONE Newton correction (pw_common.hpp div_chain1); the
@@ -121,7 +143,7 @@ __host__ __device__ inline SpreadQuadLds spread_quad_lds(unsigned char *raw = nu
     LdsCursor c{reinterpret_cast<float *>(raw)}; SpreadQuadLds o;
     o.s_ring = c.take<float4>(4 * kWave);                        // [4][64] {px, py, vx, vy}, index e_local * 6 + a
     o.s_ftab = c.take<float2>(2 * kQuadEPP * kQuadN * kQuadN);   // [2 P waves][24 agents][6 partners]
-    o.s_min = c.take<float>(kWave); o.s_rew = c.take<float>(kWave);   // [64] each, not used any more: they keep the offsets behind them
+    o.s_min = c.take<float>(kWave); o.s_rew = c.take<float>(kWave);   // [64] each: OB -> OA, a lane's collision count of even / odd steps (int32)
     o.s_lmB = c.take<float2>(kQuadEPW * kQuadL); o.s_act = c.take<int32_t>(2 * kQuadActAhead * kWave);   // [8 * 6] OB; [2 P waves][4 steps][64] action indices
     o.s_utab = c.take<float2>(2 * 8);                            // [2 P waves][8] action force per index
     o.bytes = 4 * c.at; return o;
@@ -140,6 +162,9 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
     // output wave: -2.2 % step time (A/B, profiles/r3_quad_waves.txt).
     const int wave = __builtin_amdgcn_readfirstlane((((int)threadIdx.x >> 6) + 2 * (((int)blockIdx.x >> 8) & 1)) & 3);
     const int lane = (int)threadIdx.x & 63;
+    // Measured and NOT kept (profiles/r7_quad_balance.txt): an XCD's env blocks contiguous -- block (j % 8) * (G / 8) + j / 8 for workgroup
+    // j, so that neighbouring blocks' pieces of the small output planes (rew 192, rew_shared 32, done 48, terminal 8 bytes per block and
+    // step share cache lines) meet in one L2: slower, on this kernel and on its predecessor.
     const int env0 = (int)blockIdx.x * EPW;
     const int envs_here = A.B - env0 < EPW ? A.B - env0 : EPW;
     const size_t BN = (size_t)A.B * N;
@@ -322,37 +347,39 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         // (round 2 ran this wave at priority 3 too, when it was as long as the physics waves; software-pipelined it has
         // several hundred cycles of slack per step and yields to them)
         // ---------------- OA: masks, rewards, small stores ----------------
-        // A step's work has two halves: A(t) -- read the published slot, the six collision tests, the owned landmark's
-        // minimum over the agents, its sqrt -- and B(t) -- the ordered per-env sums through two rounds of wave shuffles,
-        // the stores.  Each half is a chain of long-latency operations (LDS round trips, shuffles, sqrt) with little to
-        // issue in between, and B(t) needs nothing but A(t)'s three registers: so the loop is software-pipelined, iteration
+        // A step's work has two halves: A(t) -- read the published slot, the owned landmark's minimum over the agents, its
+        // sqrt -- and B(t) -- the ordered per-env sums through two rounds of wave shuffles, the stores.  Each half is a chain
+        // of long-latency operations (LDS round trips, shuffles, sqrt) with little to issue in between, and B(t) needs
+        // nothing but A(t)'s register and the step's collision count: so the loop is software-pipelined, iteration
         // t running B(t - 1) interleaved with A(t) (the shuffles of one fly while the arithmetic of the other issues).
         // Same operations on the same values: the bits do not change.
+        // The collision count of step t -- six threshold tests that need nothing this wave owns -- is wave OB's work (it has
+        // the issue slots: this wave and OB each share a SIMD with a physics wave of the CU's other workgroup, and the
+        // workgroup runs at the pace of the slower pair).  OB leaves it in word `lane` of s_min (t even) / s_rew (t odd)
+        // in its iteration t, i.e. before it arrives at barrier t + 1; B(t) reads the word here in iteration t + 1, behind
+        // that barrier, and has consumed it before this wave arrives at barrier t + 2; OB writes that buffer again in its
+        // iteration t + 2, behind barrier t + 2.  So the hand-over needs no meeting of its own.  Only the launch's last
+        // step has no barrier behind it: its count is computed here, after the loop (pre_last: that step's pre-reset slot).
         float own_p = 0.0f;   // A(t - 1): sqrt of the owned landmark's minimum squared distance
-        int cnt_p = 0;        //           number of agents within the collision threshold (self included)
-        uint32_t cmask_p = 0; //           their mask (COLL)
+        int cnt_p = 0;        // number of agents within the collision threshold in step t - 1 (self included)
+        const int *cnt_w = reinterpret_cast<const int *>(Y.s_min) + lane;
+        const int cnt_span = (int)(Y.s_rew - Y.s_min);
+        int cnt_at = 0;       // word offset of the buffer B(t - 1) reads: 0 <-> cnt_span, workgroup-uniform
+        int pre_last = 0;     // the pre-reset slot of the latest A
         // the pieces, in the order an iteration interleaves them
-        float2 mine, q6[N];
+        float2 q6[N];
         auto a_reads = [&](const int nxt) __attribute__((always_inline)) {
             const float4 *slot = Y.s_ring + nxt * kWave + base;
-            mine = *reinterpret_cast<const float2 *>(slot + a);
 #pragma unroll
             for (int j = 0; j < N; ++j) q6[j] = *reinterpret_cast<const float2 *>(slot + j);
+            pre_last = nxt;
         };
         float best, e0;
-        int cnt;
-        uint32_t cmask;
         auto a_dist = [&]() __attribute__((always_inline)) {
-            const float px = mine.x, py = mine.y;
             float e2[N];
-            cnt = 0; cmask = 0;
 #pragma unroll
             for (int j = 0; j < N; ++j) {
                 const float2 q = q6[j];
-                const float dx = q.x - px, dy = q.y - py;
-                const float d2 = dx * dx + dy * dy;
-                cnt += d2 < A.coll_thr2 ? 1 : 0;
-                if (COLL) cmask |= d2 < A.coll_thr2 ? 1u << j : 0u;
                 const float ex = q.x - olx, ey = q.y - oly;
                 e2[j] = ex * ex + ey * ey;
             }
@@ -397,16 +424,13 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         };
         // the planes of step tb: workgroup-uniform running pointers (b_store is called for tb = 0, 1, 2, ... in turn)
         float *rew_t = A.rew, *rsh_t = A.rew_shared;
-        uint64_t *coll_t = A.coll;
         auto b_store = [&]() __attribute__((always_inline)) {
             float acc = 0.0f;
 #pragma unroll
             for (int i = 0; i < N; ++i) acc += sh_r[i];
             nt_store(rew_t + g, r);
-            nt_store(rsh_t + env, acc);   // (done / terminal: wave OB, which has the slack)
-            if (COLL) nt_store(coll_t + g, (uint64_t)cmask_p);  // is_collision bits of the state step tb produced (pre-reset)
+            nt_store(rsh_t + env, acc);   // (done / terminal / coll: wave OB)
             rew_t += BN; rsh_t += A.B;
-            if (COLL) coll_t += BN;
         };
         PW_STAMP_DECL;
         // prologue: A(0)
@@ -417,7 +441,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             const int nxt = (cur + 1) & 3;
             a_reads(nxt);
             a_dist();
-            own_p = a_sqrt(); cnt_p = cnt; cmask_p = cmask;
+            own_p = a_sqrt();
             a_clock(0, nxt);
             PW_STAMP(1);
         }
@@ -426,17 +450,28 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             PW_QUAD_BARRIER(t);
             PW_STAMP(0);
             const int nxt = (cur + 1) & 3;
+            cnt_p = cnt_w[cnt_at];   // step t - 1's count, from wave OB
+            cnt_at = cnt_span - cnt_at;
             a_reads(nxt);
             b_shfl_own();
             a_dist();
             b_reward();
             const float own = a_sqrt();
             b_store();
-            own_p = own; cnt_p = cnt; cmask_p = cmask;
+            own_p = own;
             a_clock(t, nxt);
             PW_STAMP(1);
         }
-        b_shfl_own();  // epilogue: B(T - 1)
+        {   // epilogue: B(T - 1), with the count of this wave's own making (no barrier behind step T - 1; its slot stays as it is:
+            // the physics waves have published their last)
+            const float4 *slot = Y.s_ring + pre_last * kWave + base;
+            const float2 mine = *reinterpret_cast<const float2 *>(slot + a);
+#pragma unroll
+            for (int j = 0; j < N; ++j) q6[j] = *reinterpret_cast<const float2 *>(slot + j);
+            uint32_t cmask;
+            quad_coll_tests<false>(mine, q6, A.coll_thr2, cnt_p, cmask);
+        }
+        b_shfl_own();
         b_reward();
         b_store();
 #ifdef PW_STAMPS
@@ -488,6 +523,14 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
     // the terminal flag of step t is "t >= t_term": t + 1 + ep_off >= max_episode_len, solved for t (changes in reset steps only)
     const bool has_len = A.max_episode_len > 0;
     int t_term = has_len ? A.max_episode_len - 1 - ep_off : 0x7fffffff;
+    // The collision half of wave OA's step runs here (see there: who waits for what): in every step this lane -- in its (env, agent)
+    // mapping, idle lanes shadowing lane 0 -- tests its agent against the env's six in the PRE-reset slot, the slot OA's A(t) reads,
+    // and leaves the count in word `lane` of s_min / s_rew (even / odd steps; the offset toggles, nothing is selected).  COLL: the
+    // step's mask plane leaves from here as well.  Straight-line: seven broadcast reads, selects, one LDS write.
+    int *cnt_w = reinterpret_cast<int *>(Y.s_min) + lane;
+    const int cnt_span = (int)(Y.s_rew - Y.s_min);
+    int cnt_at = 0;
+    uint64_t *coll_t = A.coll;
     PW_STAMP_DECL;
     for (int t = 0; t < T; ++t) {
         PW_STAMP_START;
@@ -495,6 +538,13 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         PW_QUAD_BARRIER(t);
         PW_STAMP(0);
         int nxt = (cur + 1) & 3;
+        float2 cmine, cq6[N];
+        {
+            const float4 *pre = Y.s_ring + nxt * kWave + base;
+            cmine = *reinterpret_cast<const float2 *>(pre + a);
+#pragma unroll
+            for (int j = 0; j < N; ++j) cq6[j] = *reinterpret_cast<const float2 *>(pre + j);
+        }
         nt_store(term_t + env, (uint8_t)(t >= t_term ? 1 : 0));
         if (t == t_reset) {  // workgroup-uniform, once per episode
             const bool rst = t >= t_term;
@@ -520,6 +570,17 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         float4 st[3];
 #pragma unroll
         for (int u = 0; u < 3; ++u) st[u] = slot[row_u[u]];
+        {   // (the tests' operands were read first: they run while the rows arrive)
+            int cnt;
+            uint32_t cmask;
+            quad_coll_tests<COLL>(cmine, cq6, A.coll_thr2, cnt, cmask);
+            cnt_w[cnt_at] = cnt;   // complete before this wave arrives at the next barrier (its s_waitcnt)
+            cnt_at = cnt_span - cnt_at;
+            if (COLL) {
+                nt_store(coll_t + g, (uint64_t)cmask);   // is_collision bits of the state step t produced (pre-reset)
+                coll_t += BN;
+            }
+        }
         // anchor: the rows arrive whole behind one wait (otherwise the compiler splits row 0's read between the two sides of an
         // exec-masked region it makes of the selects)
         asm volatile("" :: "v"(st[0].x), "v"(st[0].y), "v"(st[0].z), "v"(st[0].w), "v"(st[1].x), "v"(st[1].y), "v"(st[1].z),

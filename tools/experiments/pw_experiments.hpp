@@ -13,6 +13,9 @@
 //   PW_EXP_PAD_OB=<n>     n x `s_nop 0` in the step loop of the quad kernel's wave OB (the results stay right; an experiment build all the
 //   PW_EXP_PAD_P=<n>      same) / of its physics waves: does a step pay for every instruction a SIMD issues, or only for the physics
 //                         wave's dependent chain?  (profiles/r6_quad_issue_budget.txt)
+//   PW_EXP_NO_COLL_TESTS  the quad kernel's six collision tests per output lane and step compiled out, the count fixed at 1 (read by
+//                         pw_kernels_spread_quad.hpp quad_coll_tests): the bound of taking that work off a SIMD altogether.  Measured
+//                         on the kernel whose wave OA still held the tests (profiles/r7_quad_balance.txt); now they are wave OB's
 //   (PW_QUAD_ACT_AHEAD=8|16 is a plain parameter of pw_kernels_spread_quad.hpp, not an experiment: results stay exact)
 #pragma once
 #ifndef PW_EXPERIMENTS
