@@ -4,6 +4,7 @@
 
 #include "pw_kernels_spread.hpp"   // StreamParams of the rollout block, the PW_STAMP probe macros
 #include "pw_lstm_math.hpp"
+#include "pw_policy_shared.hpp"    // RolloutSink of the rollout block
 
 namespace {
 
@@ -667,16 +668,7 @@ struct PolicyRolloutArgs {
     StreamParams V;     // world constants, state planes, outputs (V.act unused)
     int T;
     int32_t *act_out;   // [T,B,N] sampled action indices (or NULL)
-    // optional direct sink: the transitions go straight into the replay ring (slot (ring_start + t*B + env) %
-    // capacity, the order of T pw_replay_add calls) and the episode returns are kept here, so no second launch
-    // has to re-read the step outputs (which then may all be NULL)
-    pw_replay_store ring;
-    int has_ring;
-    int64_t ring_start;
-    float *episode_return;          // [B] running return per env (or NULL)
-    double *finished_sum;
-    int64_t *finished_count;
-    unsigned long long *scratch;    // [1 + 2 * gridDim.x] words (ticket, partial sums, partial counts: rollout_finish_stats), zeroed once
+    RolloutSink sink;   // optional direct sink (pw_policy_shared.hpp)
     int NP;                         // just-in-time form: row stride of an environment in LDS (>= N; odd: see pw_kernels_policy3j.hpp)
 };
 

@@ -153,7 +153,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
     double fin_sum = 0.0;
     int fin_cnt = 0;
     if (env_wave) {
-        if (SINK && P.episode_return && live && a == 0) ep_ret = P.episode_return[env];
+        if (SINK && P.sink.episode_return && live && a == 0) ep_ret = P.sink.episode_return[env];
         px = V.pos_x[g]; py = V.pos_y[g]; vx = V.vel_x[g]; vy = V.vel_y[g];
         ep_step = V.ep_step[env];
         ep_count = V.ep_count[env];
@@ -257,11 +257,9 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
         t_term = V.max_episode_len > 0 && ep_step >= V.max_episode_len;
         t_rw = rw;
         t_acc = acc;
-        if (SINK && live && a == 0 && P.episode_return) {  // run.py:55-65, per env
-            const float rsum = ep_ret + acc;
-            if (t_term) { fin_sum += (double)rsum; fin_cnt += 1; ep_ret = 0.0f; }
-            else ep_ret = rsum;
-        }
+        // into registers, published after the loop: into LDS (rollout_zero_episodes / rollout_finish_episodes, as tag, generic and 3j)
+        // <2,6,true,false> goes from 162 to 164 SGPR spills and its step loop from 2669 to 2675 instructions
+        if (SINK && live && a == 0 && P.sink.episode_return) episode_account(ep_ret, acc, t_term, fin_sum, fin_cnt);
     };
     // the lane's launch-invariant global index goes through opaque() (pw_policy_shared.hpp) wherever it feeds an output address
     auto tail_stores = [&](const int t, const bool with_obs) {  // with_obs: V.obs too (no reset in between: the same row)
@@ -275,10 +273,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
                 if (V.rew_shared) V.rew_shared[(size_t)t * A.B + env] = t_acc;
                 if (V.terminal) V.terminal[(size_t)t * A.B + env] = t_term ? 1 : 0;
             }
-            if (SINK && P.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
-                if (P.ring.state_rows) sink_state_next(P.ring, slot, N, a, px, py, vx, vy);
-                else stream_write_obs<LT>(P.ring.next_obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
-                if (a == 0) { P.ring.rew[slot] = t_acc; P.ring.done[slot] = 0.0f; }
+            if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
+                if (P.sink.ring.state_rows) sink_state_next(P.sink.ring, slot, N, a, px, py, vx, vy);
+                else stream_write_obs<LT>(P.sink.ring.next_obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
+                if (a == 0) { P.sink.ring.rew[slot] = t_acc; P.sink.ring.done[slot] = 0.0f; }
             }
             if (with_obs && V.obs) stream_write_obs<LT>(V.obs + (tBN + g) * D, L, lmv, px, py, vx, vy);
         }
@@ -311,6 +309,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
             lds_write_obs_row<LT>(S.s_obs + r * DS, L, lmv, px, py, vx, vy);
         }
     };
+    // StepTail (pw_policy_shared.hpp), inline: the pending step is always t - 1 here, and with the struct's t <2,6,*,false> take 4 .. 6 VGPRs more
     int tail_stage = 0;  // 0 nothing pending; 1: tail_compute of step t - 1 pending; 2: its tail_stores pending
 
     // dense1 blocks of this wave (bit = block), dealt once per launch: the environment waves run the previous step's tail_compute in the
@@ -423,17 +422,15 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
         if (t + 1 < P.T && noise_t0 < noise_thr) draw_noise(step0 + (uint64_t)(t + 1), noise_t0, noise_thr);  // this step's is consumed
         if (env_wave) {
             ai = S.s_act[r];
-            if (SINK && P.has_ring) {  // the observation the policy acted on (still in LDS) -> ring.obs
-                slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
+            if (SINK && P.sink.has_ring) {  // the observation the policy acted on (still in LDS) -> ring.obs
+                slot = ring_slot(P.sink.ring_start, t, A.B, (long)env, P.sink.ring.capacity);
                 if (live) {
-                    if (P.ring.state_rows) {   // the state the policy acted on (still in the registers) + the episode's landmarks
-                        sink_state_obs(P.ring, slot, N, a, L, lmv, px, py, vx, vy);
+                    if (P.sink.ring.state_rows) {   // the state the policy acted on (still in the registers) + the episode's landmarks
+                        sink_state_obs(P.sink.ring, slot, N, a, L, lmv, px, py, vx, vy);
                     } else {
-                        const float2 *src = reinterpret_cast<const float2 *>(S.s_obs + r * DS);
-                        float2 *dst = reinterpret_cast<float2 *>(P.ring.obs + (slot * N + a) * D);
-                        for (int c = 0; c < D / 2; ++c) dst[c] = src[c];
+                        copy_row2(P.sink.ring.obs + (slot * N + a) * D, S.s_obs + r * DS, D / 2);
                     }
-                    P.ring.act[slot * N + a] = (uint8_t)ai;
+                    P.sink.ring.act[slot * N + a] = (uint8_t)ai;
                 }
             }
             float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
@@ -474,14 +471,14 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
         if (a == 0) {
             V.ep_step[env] = ep_step;
             V.ep_count[env] = ep_count;
-            if (SINK && P.episode_return) P.episode_return[env] = ep_ret;
+            if (SINK && P.sink.episode_return) P.sink.episode_return[env] = ep_ret;
         }
     }
-    if (SINK && P.episode_return) {
+    if (SINK && P.sink.episode_return) {
         wg_lds_barrier();
         if (live && a == 0) { S.s_fs[el] = fin_sum; S.s_fc[el] = fin_cnt; }
         wg_lds_barrier();
-        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.scratch, P.finished_sum, P.finished_count, S.red);
+        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.sink.scratch, P.sink.finished_sum, P.sink.finished_count, S.red);
     }
 }
 

@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
     float2 *s_pos = S.s_posb + (env_wave ? ew : 0) * kWave;
     const float k = V.contact_margin, cf = V.contact_force, dt = V.dt, damp = V.damp, mass = V.mass;
 
-    // one slot's lane coordinates
+    // one slot's lane coordinates (environment slots: a wave serves several virtual waves, rows have stride NP).  Undeferred: no StepTail.
     struct EnvLane {
         int e_loc, a, el, base, r, la;
         bool live;
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
                 if (q.a == 0) {
                     S.s_eps[q.el] = V.ep_step[q.env];
                     S.s_epc[q.el] = V.ep_count[q.env];
-                    S.s_ret[q.el] = (SINK && P.episode_return) ? P.episode_return[q.env] : 0.0f;
+                    S.s_ret[q.el] = (SINK && P.sink.episode_return) ? P.sink.episode_return[q.env] : 0.0f;
                     S.s_fs[q.el] = 0.0;
                     S.s_fc[q.el] = 0;
                 }
@@ -318,12 +318,12 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
         wave_lds_sync();
         const int ai = S.s_act[r];
         size_t slot = 0;
-        if (SINK && P.has_ring) {  // the observation the policy acted on: rebuilt from the (still pre-step) state
-            slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
+        if (SINK && P.sink.has_ring) {  // the observation the policy acted on: rebuilt from the (still pre-step) state
+            slot = ring_slot(P.sink.ring_start, t, A.B, (long)env, P.sink.ring.capacity);
             if (live) {
-                if (P.ring.state_rows) sink_state_obs(P.ring, slot, N, a, L, lmv, px, py, vx, vy);
-                else stream_write_obs<0>(P.ring.obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
-                P.ring.act[slot * N + a] = (uint8_t)ai;
+                if (P.sink.ring.state_rows) sink_state_obs(P.sink.ring, slot, N, a, L, lmv, px, py, vx, vy);
+                else stream_write_obs<0>(P.sink.ring.obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
+                P.sink.ring.act[slot * N + a] = (uint8_t)ai;
             }
         }
         float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
@@ -347,11 +347,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
         const float acc = shfl_add_ordered(0.0f, rw, base, N);
         ep_step += 1;
         const bool term = V.max_episode_len > 0 && ep_step >= V.max_episode_len;
-        if (SINK && live && a == 0 && P.episode_return) {  // run.py:55-65, per env
-            const float rsum = S.s_ret[el] + acc;
-            if (term) { S.s_fs[el] += (double)rsum; S.s_fc[el] += 1; S.s_ret[el] = 0.0f; }
-            else S.s_ret[el] = rsum;
-        }
+        if (SINK && live && a == 0 && P.sink.episode_return) episode_account(S.s_ret[el], acc, term, S.s_fs[el], S.s_fc[el]);
         if (live) {
             if (P.act_out) P.act_out[tBN + g] = ai;
             if (V.rew) V.rew[tBN + g] = rw;
@@ -360,10 +356,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
                 if (V.rew_shared) V.rew_shared[(size_t)t * A.B + env] = acc;
                 if (V.terminal) V.terminal[(size_t)t * A.B + env] = term ? 1 : 0;
             }
-            if (SINK && P.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
-                if (P.ring.state_rows) sink_state_next(P.ring, slot, N, a, px, py, vx, vy);
-                else stream_write_obs<0>(P.ring.next_obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
-                if (a == 0) { P.ring.rew[slot] = acc; P.ring.done[slot] = 0.0f; }
+            if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
+                if (P.sink.ring.state_rows) sink_state_next(P.sink.ring, slot, N, a, px, py, vx, vy);
+                else stream_write_obs<0>(P.sink.ring.next_obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
+                if (a == 0) { P.sink.ring.rew[slot] = acc; P.sink.ring.done[slot] = 0.0f; }
             }
         }
         if (term && V.auto_reset) {  // same for every lane of an env
@@ -477,15 +473,12 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
                 if (q.a == 0) {
                     V.ep_step[q.env] = S.s_eps[q.el];
                     V.ep_count[q.env] = S.s_epc[q.el];
-                    if (SINK && P.episode_return) P.episode_return[q.env] = S.s_ret[q.el];
+                    if (SINK && P.sink.episode_return) P.sink.episode_return[q.env] = S.s_ret[q.el];
                 }
             }
         }
     }
-    if (SINK && P.episode_return) {
-        wg_lds_barrier();
-        rollout_finish_stats(envs_here, S.s_fs, S.s_fc, P.scratch, P.finished_sum, P.finished_count, S.red);
-    }
+    if (SINK) rollout_finish_episodes(P.sink, envs_here, S.s_fs, S.s_fc, S.red);
 }
 
 }  // namespace

@@ -18,13 +18,7 @@ struct PolicyRolloutGenericArgs {
     uint8_t *done, *terminal;
     int T;
     int32_t *act_out;   // [T,B,N] sampled action indices (or NULL)
-    pw_replay_store ring;
-    int has_ring;
-    int64_t ring_start;
-    float *episode_return;
-    double *finished_sum;
-    int64_t *finished_count;
-    unsigned long long *scratch;
+    RolloutSink sink;   // optional direct sink (pw_policy_shared.hpp)
 };
 
 // The actor16 block, then the rollout's own regions.  Whole environments per environment wave: epw = min(E, 64 / N) of them, each
@@ -95,10 +89,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
     uint32_t ep_count = 0;
     float my_size = 0.f, my_sens = 0.f, my_fscale = 1.f, my_maxspeed = -1.f;
     float ep_ret = 0.f;
-    if (SINK && tid < 16) { Y.s_fs[tid] = 0.0; Y.s_fc[tid] = 0; }   // per-env finished-episode (sum, count) of this launch
+    if (SINK) rollout_zero_episodes(Y.s_fs, Y.s_fc);
     if (env_wave) {
         if (live) {
-            if (SINK && P.episode_return && ln.a == 0) ep_ret = P.episode_return[ln.env];
+            if (SINK && P.sink.episode_return && ln.a == 0) ep_ret = P.sink.episode_return[ln.env];
             px = K.pos_x[ln.g]; py = K.pos_y[ln.g];
             vx = K.vel_x[ln.g]; vy = K.vel_y[ln.g];
             ep_step = K.ep_step[ln.env];
@@ -128,6 +122,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
     //   tail_stores   every global store of the step
     // In a step that ends no episode of the wave both run inside the NEXT actor pass (before its dense1 blocks / before its head tiles:
     // actor16_forward's pre / mid windows); a wave with an episode ending runs both, final_obs and the reset before it publishes the rows.
+    // StepTail (pw_policy_shared.hpp), inline: with the struct the step loops grow by 1 .. 2 instructions (<0,0,2,true> 6046 -> 6047)
     int ai = 0, tail_t = 0, tail_stage = 0;  // tail_stage: 0 nothing pending, 1 tail_compute pending, 2 tail_stores pending
     float t_rw = 0.f, t_acc = 0.f;
     bool t_term = false;
@@ -140,11 +135,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
         t_term = K.max_episode_len > 0 && ep_step >= K.max_episode_len;
         t_rw = rw;
         t_acc = acc;
-        if (SINK && live && ln.a == 0 && P.episode_return) {
-            const float rsum = ep_ret + acc;
-            if (t_term) { Y.s_fs[ln.env - (int)env0] += (double)rsum; Y.s_fc[ln.env - (int)env0] += 1; ep_ret = 0.0f; }
-            else ep_ret = rsum;
-        }
+        if (SINK && live && ln.a == 0 && P.sink.episode_return)
+            episode_account(ep_ret, acc, t_term, Y.s_fs[ln.env - (int)env0], Y.s_fc[ln.env - (int)env0]);
     };
     auto tail_stores = [&](const int t, const bool with_obs) {  // with_obs: the obs output too (no reset in between: the same row)
         const size_t row = (size_t)t * BN + ln.g;
@@ -157,13 +149,14 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
                 if (P.terminal) P.terminal[(size_t)t * A.B + ln.env] = t_term ? 1 : 0;
             }
             // with_obs: next_obs and obs are both the row this lane published in LDS -- copied, not rebuilt
+            // (copy_row2, inline at the three sites of this kernel: with the function 11 of 48 instantiations miss the codegen rule)
             const float2 *src = reinterpret_cast<const float2 *>(Y.s_obs + r_lane * D);
-            if (SINK && P.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
-                const size_t slot = ring_slot(P.ring_start, t, A.B, (long)ln.env, P.ring.capacity);
-                float *dst = P.ring.next_obs + (slot * N + ln.a) * D;
+            if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
+                const size_t slot = ring_slot(P.sink.ring_start, t, A.B, (long)ln.env, P.sink.ring.capacity);
+                float *dst = P.sink.ring.next_obs + (slot * N + ln.a) * D;
                 if (with_obs) for (int c = 0; c < D / 2; ++c) reinterpret_cast<float2 *>(dst)[c] = src[c];
                 else write_obs<SCEN, OBS>(K, ln, dst, px, py, vx, vy, s_pos, s_vel, s_lm);
-                if (ln.a == 0) { P.ring.rew[slot] = t_acc; P.ring.done[slot] = 0.0f; }
+                if (ln.a == 0) { P.sink.ring.rew[slot] = t_acc; P.sink.ring.done[slot] = 0.0f; }
             }
             if (with_obs && P.obs) {
                 float2 *dst = reinterpret_cast<float2 *>(P.obs + row * D);
@@ -181,12 +174,12 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
         if (env_wave) {
             const size_t row = (size_t)t * BN + ln.g;  // flattened [t, env, agent]
             ai = Y.s_act[r_lane];
-            if (SINK && P.has_ring && live) {  // the observation the policy acted on (still in LDS) -> ring.obs
-                const size_t slot = ring_slot(P.ring_start, t, A.B, (long)ln.env, P.ring.capacity);
+            if (SINK && P.sink.has_ring && live) {  // the observation the policy acted on (still in LDS) -> ring.obs
+                const size_t slot = ring_slot(P.sink.ring_start, t, A.B, (long)ln.env, P.sink.ring.capacity);
                 const float2 *src = reinterpret_cast<const float2 *>(Y.s_obs + r_lane * D);
-                float2 *dst = reinterpret_cast<float2 *>(P.ring.obs + (slot * N + ln.a) * D);
+                float2 *dst = reinterpret_cast<float2 *>(P.sink.ring.obs + (slot * N + ln.a) * D);
                 for (int c = 0; c < D / 2; ++c) dst[c] = src[c];
-                P.ring.act[slot * N + ln.a] = (uint8_t)ai;
+                P.sink.ring.act[slot * N + ln.a] = (uint8_t)ai;
             }
             // ---- U2 _set_action + U4 apply_action_force
             if (live) {
@@ -285,13 +278,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
         if (ln.a == 0) {
             K.ep_step[ln.env] = ep_step;
             K.ep_count[ln.env] = ep_count;
-            if (SINK && P.episode_return) P.episode_return[ln.env] = ep_ret;
+            if (SINK && P.sink.episode_return) P.sink.episode_return[ln.env] = ep_ret;
         }
     }
-    if (SINK && P.episode_return) {
-        wg_lds_barrier();
-        rollout_finish_stats(envs_here, Y.s_fs, Y.s_fc, P.scratch, P.finished_sum, P.finished_count, Y.red);
-    }
+    if (SINK) rollout_finish_episodes(P.sink, envs_here, Y.s_fs, Y.s_fc, Y.red);
 }
 
 }  // namespace

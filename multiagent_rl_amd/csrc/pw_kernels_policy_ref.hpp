@@ -26,15 +26,7 @@ struct PolicyRolloutRefArgs {
     int32_t *act_out;   // [T,B,N,2] (or NULL)
     float *obs, *final_obs, *rew, *rew_shared;
     uint8_t *done, *terminal;
-    // optional direct sink (round 4, as the simple_spread / simple_tag rollouts): the transitions go straight into the TWO-HEAD replay
-    // ring (act [cap,N,2] u8; slot (ring_start + t*B + env) % capacity) and the episode returns are kept here -- no second launch
-    pw_replay_store ring;
-    int has_ring;
-    int64_t ring_start;
-    float *episode_return;
-    double *finished_sum;
-    int64_t *finished_count;
-    unsigned long long *scratch;
+    RolloutSink sink;   // optional direct sink (pw_policy_shared.hpp): the TWO-HEAD replay ring (act [cap,N,2] u8)
 };
 
 // The actor16 block (N = 2, 16 environments), then the rollout's own regions
@@ -80,7 +72,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
     const long row_base = env0 * N;
     const size_t BN = (size_t)A.B * N;
 
-    // ---- environment lanes: the LAST wave, lane = el * 2 + a (E <= 16 envs: 32 lanes) -- the tail of a step (reward, stores) then runs
+    // ---- environment lanes (one wave, the partner is lane ^ 1: its own mapping, not env_waves' split): the LAST wave, lane = el * 2 + a
+    // (E <= 16 envs: 32 lanes) -- the tail of a step (reward, stores) then runs
     // beside the next actor pass's dense1 blocks and head tiles, which sit on waves 0 and 1 (actor16_forward's pre / mid windows)
     const bool env_wave = wave == 7;
     int el = lane >> 1;
@@ -98,7 +91,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
     int fin_cnt = 0;
     size_t slot = 0;
     if (env_wave) {
-        if (SINK && P.episode_return && live && a == 0) ep_ret = P.episode_return[env];
+        if (SINK && P.sink.episode_return && live && a == 0) ep_ret = P.sink.episode_return[env];
         ref_load<DC>(V, env, a, s);
         ep_step = V.ep_step[env];
         ep_count = V.ep_count[env];
@@ -113,9 +106,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
 
     // the rest of a step once the agents are advanced and the next observation rows published: rewards + episode step count
     // (tail_compute), every global store (tail_stores); a wave with an episode ending in this step does everything at once
-    int ai = 0, ci = 0, tail_t = 0, tail_stage = 0;
-    float t_rw = 0.f, t_acc = 0.f;
-    bool t_term = false;
+    int ai = 0, ci = 0;
+    StepTail tail;
     float co[DC];  // the other agent's symbol (this step's)
     auto tail_compute = [&]() {
         const float ox = __shfl_xor(s.px, 1, kWave), oy = __shfl_xor(s.py, 1, kWave);
@@ -124,35 +116,33 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
         const float dx = ox - glx, dy = oy - gly;
         const float rw = -(dx * dx + dy * dy);
         const float r_other = __shfl_xor(rw, 1, kWave);
-        t_rw = rw;
-        t_acc = (0.0f + (a == 0 ? rw : r_other)) + (a == 0 ? r_other : rw);  // agent order
+        tail.rw = rw;
+        tail.acc = (0.0f + (a == 0 ? rw : r_other)) + (a == 0 ? r_other : rw);  // agent order
         ep_step += 1;
-        t_term = V.max_episode_len > 0 && ep_step >= V.max_episode_len;
-        if (SINK && live && a == 0 && P.episode_return) {  // run.py:55-65, per env
-            const float rsum = ep_ret + t_acc;
-            if (t_term) { fin_sum += (double)rsum; fin_cnt += 1; ep_ret = 0.0f; }
-            else ep_ret = rsum;
-        }
+        tail.term = V.max_episode_len > 0 && ep_step >= V.max_episode_len;
+        // into registers, published after the loop: into LDS (rollout_zero_episodes / rollout_finish_episodes, as tag, generic and 3j) the
+        // sink instantiation goes from 179 to 187 SGPR spills and its step loop from 2514 to 2536 instructions
+        if (SINK && live && a == 0 && P.sink.episode_return) episode_account(ep_ret, tail.acc, tail.term, fin_sum, fin_cnt);
     };
     auto tail_stores = [&](const int t, const bool with_obs) {
         const size_t row = (size_t)t * BN + g;
         if (live) {
             if (P.act_out) { P.act_out[2 * row] = ai; P.act_out[2 * row + 1] = ci; }
-            if (P.rew) P.rew[row] = t_rw;
+            if (P.rew) P.rew[row] = tail.rw;
             if (P.done) P.done[row] = 0;
             if (a == 0) {
-                if (P.rew_shared) P.rew_shared[(size_t)t * A.B + env] = t_acc;
-                if (P.terminal) P.terminal[(size_t)t * A.B + env] = t_term ? 1 : 0;
+                if (P.rew_shared) P.rew_shared[(size_t)t * A.B + env] = tail.acc;
+                if (P.terminal) P.terminal[(size_t)t * A.B + env] = tail.term ? 1 : 0;
             }
             if (with_obs && P.obs) ref_write_obs<DC, false>(V, s, co, a, P.obs + row * D);
-            if (SINK && P.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
-                ref_write_obs<DC, false>(V, s, co, a, P.ring.next_obs + (slot * N + a) * D);
-                if (a == 0) { P.ring.rew[slot] = t_acc; P.ring.done[slot] = 0.0f; }
+            if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
+                ref_write_obs<DC, false>(V, s, co, a, P.sink.ring.next_obs + (slot * N + a) * D);
+                if (a == 0) { P.sink.ring.rew[slot] = tail.acc; P.sink.ring.done[slot] = 0.0f; }
             }
         }
     };
-    auto pre_hook = [&]() { if (tail_stage == 1) { tail_compute(); tail_stage = 2; } };
-    auto mid_hook = [&]() { if (tail_stage == 2) { tail_stores(tail_t, true); tail_stage = 0; } };
+    auto pre_hook = [&]() { tail.pre(tail_compute); };
+    auto mid_hook = [&]() { tail.mid(tail_stores); };
 
 #ifdef PW_STAMPS
     unsigned long long rs[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, r0_ = 0, r1_ = 0;
@@ -169,12 +159,12 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
                                     mid_hook, Y.s_noise, &T1 PW_REF_STAMP_ARGS);  // a barrier at its end
         // the noise of the NEXT step's heads: by the seven waves that wait for the environment wave
         if (t + 1 < P.T && !env_wave) actor16_draw_noise(A, Y.s_noise, rows_here, row_base, step0 + (uint64_t)(t + 1), tid, 7 * kWave);
-        if (SINK && P.has_ring && !env_wave) {
+        if (SINK && P.sink.has_ring && !env_wave) {
             // the observations the policy acted on -> ring.obs, by the seven waves that would otherwise wait for the environment wave
             for (int idx = tid; idx < rows_here * D; idx += 448) {
                 const int rr = idx / D, c = idx - rr * D;
-                const size_t sl = ring_slot(P.ring_start, t, A.B, env0 + (rr >> 1), P.ring.capacity);
-                P.ring.obs[(sl * N + (rr & 1)) * D + c] = s_obs[idx];
+                const size_t sl = ring_slot(P.sink.ring_start, t, A.B, env0 + (rr >> 1), P.sink.ring.capacity);
+                P.sink.ring.obs[(sl * N + (rr & 1)) * D + c] = s_obs[idx];
             }
         }
         PW_R2_STAMP(7);
@@ -182,11 +172,11 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
         if (env_wave) {
             const size_t row = (size_t)t * BN + g;
             ai = Y.s_act[2 * r]; ci = Y.s_act[2 * r + 1];
-            if (SINK && P.has_ring) {  // the pair the policy sampled -> ring.act (the observation rows: the idle waves, above)
-                slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
+            if (SINK && P.sink.has_ring) {  // the pair the policy sampled -> ring.act (the observation rows: the idle waves, above)
+                slot = ring_slot(P.sink.ring_start, t, A.B, (long)env, P.sink.ring.capacity);
                 if (live) {
-                    P.ring.act[(slot * N + a) * 2] = (uint8_t)ai;
-                    P.ring.act[(slot * N + a) * 2 + 1] = (uint8_t)ci;
+                    P.sink.ring.act[(slot * N + a) * 2] = (uint8_t)ai;
+                    P.sink.ring.act[(slot * N + a) * 2 + 1] = (uint8_t)ci;
                 }
             }
             const float a1 = ai == 1, a2 = ai == 2, a3 = ai == 3, a4 = ai == 4;
@@ -211,7 +201,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
             if (__any(ends)) {
                 tail_compute();
                 tail_stores(t, false);
-                if (t_term && V.auto_reset) {
+                if (tail.term && V.auto_reset) {
                     if (live && P.final_obs) ref_write_obs<DC, false>(V, s, co, a, P.final_obs + row * D);
                     ep_count += 1;
                     ep_step = 0;
@@ -225,8 +215,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
                 }
             } else {
                 if (live) ref_write_obs<DC, false>(V, s, co, a, s_next + r * D);
-                tail_stage = 1;
-                tail_t = t;
+                tail.defer(t);
             }
         }
         PW_R2_STAMP(8);
@@ -237,20 +226,19 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
     if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 7 || wave == 3))
         for (int i_ = 0; i_ < 10; ++i_) g_pw_ref_stamps[(wave == 0 ? 0 : wave == 7 ? 1 : 2) * 10 + i_] = rs[i_];
 #endif
-    if (tail_stage == 1) tail_compute();
-    if (tail_stage != 0) tail_stores(tail_t, true);
+    tail.flush(tail_compute, tail_stores);
     if (live) {
         ref_store<DC>(V, env, a, s);
         if (a == 0) {
             V.ep_step[env] = ep_step; V.ep_count[env] = ep_count;
-            if (SINK && P.episode_return) P.episode_return[env] = ep_ret;
+            if (SINK && P.sink.episode_return) P.sink.episode_return[env] = ep_ret;
         }
     }
-    if (SINK && P.episode_return) {  // finished-episode statistics: per-workgroup partials, the last workgroup adds them up in order
+    if (SINK && P.sink.episode_return) {  // finished-episode statistics: per-workgroup partials, the last workgroup adds them up in order
         wg_lds_barrier();
         if (live && a == 0) { Y.s_fs[el] = fin_sum; Y.s_fc[el] = fin_cnt; }
         wg_lds_barrier();
-        rollout_finish_stats(envs_here, Y.s_fs, Y.s_fc, P.scratch, P.finished_sum, P.finished_count, Y.red);
+        rollout_finish_stats(envs_here, Y.s_fs, Y.s_fc, P.sink.scratch, P.sink.finished_sum, P.sink.finished_count, Y.red);
     }
 }
 

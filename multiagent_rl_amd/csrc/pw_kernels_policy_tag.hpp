@@ -14,13 +14,7 @@ struct PolicyRolloutTagArgs {
     TagParams V;        // world constants (2x2 class tables), state planes, outputs (V.act unused)
     int T;
     int32_t *act_out;   // [T,B,N] sampled action indices (or NULL)
-    pw_replay_store ring;
-    int has_ring;
-    int64_t ring_start;
-    float *episode_return;
-    double *finished_sum;
-    int64_t *finished_count;
-    unsigned long long *scratch;
+    RolloutSink sink;   // optional direct sink (pw_policy_shared.hpp)
 };
 
 // The actor16 block, then the rollout's own regions
@@ -131,9 +125,9 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
         }
         near_a &= ~(1u << a);
     };
-    if (SINK && tid < 16) { Y.s_fs[tid] = 0.0; Y.s_fc[tid] = 0; }   // per-env finished-episode (sum, count) of this launch
+    if (SINK) rollout_zero_episodes(Y.s_fs, Y.s_fc);
     if (env_wave) {
-        if (SINK && P.episode_return && live && a == 0) ep_ret = P.episode_return[env];
+        if (SINK && P.sink.episode_return && live && a == 0) ep_ret = P.sink.episode_return[env];
         px = V.pos_x[g]; py = V.pos_y[g]; vx = V.vel_x[g]; vy = V.vel_y[g];
         ep_step = V.ep_step[env];
         ep_count = V.ep_count[env];
@@ -157,9 +151,8 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
     //   tail_stores   every global store of the step
     // run by the environment waves inside the NEXT actor pass (before its dense1 blocks / before its head tiles).  A wave with an
     // episode ending in this step runs both, the reset and the post-reset partner pass before it publishes the rows.
-    int ai = 0, tail_t = 0, tail_stage = 0;  // tail_stage: 0 nothing pending, 1 tail_compute pending, 2 tail_stores pending
-    float t_rw = 0.f, t_acc = 0.f;
-    bool t_term = false;
+    int ai = 0;
+    StepTail tail;
     auto tail_compute = [&]() {
         partner_pass();
         // simple_tag.reward
@@ -189,14 +182,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
             for (int i = 0; i < N; ++i) acc += s_rew[base + i];
         }
         ep_step += 1;
-        t_term = V.max_episode_len > 0 && ep_step >= V.max_episode_len;
-        t_rw = rw;
-        t_acc = acc;
-        if (SINK && live && a == 0 && P.episode_return) {
-            const float rsum = ep_ret + acc;
-            if (t_term) { Y.s_fs[el] += (double)rsum; Y.s_fc[el] += 1; ep_ret = 0.0f; }   // once per episode: LDS, not registers
-            else ep_ret = rsum;
-        }
+        tail.term = V.max_episode_len > 0 && ep_step >= V.max_episode_len;
+        tail.rw = rw;
+        tail.acc = acc;
+        if (SINK && live && a == 0 && P.sink.episode_return) episode_account(ep_ret, acc, tail.term, Y.s_fs[el], Y.s_fc[el]);
     };
     // the lane's launch-invariant indices (g, r) go through opaque() (pw_policy_shared.hpp) wherever they feed an output address
     auto tail_stores = [&](const int t, const bool with_obs) {  // with_obs: V.obs too (no reset in between: the same row)
@@ -205,30 +194,27 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
         const int r = (int)opaque((uint32_t)r_lane);
         if (live) {
             if (P.act_out) P.act_out[tBN + g] = ai;
-            if (V.rew) V.rew[tBN + g] = t_rw;
+            if (V.rew) V.rew[tBN + g] = tail.rw;
             if (V.done) V.done[tBN + g] = 0;
             if (a == 0) {
-                if (V.rew_shared) V.rew_shared[(size_t)t * A.B + env] = t_acc;
-                if (V.terminal) V.terminal[(size_t)t * A.B + env] = t_term ? 1 : 0;
+                if (V.rew_shared) V.rew_shared[(size_t)t * A.B + env] = tail.acc;
+                if (V.terminal) V.terminal[(size_t)t * A.B + env] = tail.term ? 1 : 0;
             }
             // with_obs: no reset in between, so next_obs and obs are both the row this lane published in LDS -- copied, not rebuilt
-            const float2 *row = reinterpret_cast<const float2 *>(Y.s_obs + r * D);
-            if (SINK && P.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
-                const size_t slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
-                float *dst = P.ring.next_obs + (slot * N + a) * D;
-                if (P.ring.state_rows) sink_state_next(P.ring, slot, N, a, px, py, vx, vy);
-                else if (with_obs) for (int c = 0; c < D / 2; ++c) reinterpret_cast<float2 *>(dst)[c] = row[c];
+            const float *row = Y.s_obs + r * D;
+            if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
+                const size_t slot = ring_slot(P.sink.ring_start, t, A.B, (long)env, P.sink.ring.capacity);
+                float *dst = P.sink.ring.next_obs + (slot * N + a) * D;
+                if (P.sink.ring.state_rows) sink_state_next(P.sink.ring, slot, N, a, px, py, vx, vy);
+                else if (with_obs) copy_row2(dst, row, D / 2);
                 else write_row(dst);
-                if (a == 0) { P.ring.rew[slot] = t_acc; P.ring.done[slot] = 0.0f; }
+                if (a == 0) { P.sink.ring.rew[slot] = tail.acc; P.sink.ring.done[slot] = 0.0f; }
             }
-            if (with_obs && V.obs) {
-                float2 *dst = reinterpret_cast<float2 *>(V.obs + (tBN + g) * D);
-                for (int c = 0; c < D / 2; ++c) dst[c] = row[c];
-            }
+            if (with_obs && V.obs) copy_row2(V.obs + (tBN + g) * D, row, D / 2);
         }
     };
-    auto pre_hook = [&]() { if (tail_stage == 1) { tail_compute(); tail_stage = 2; } };
-    auto mid_hook = [&]() { if (tail_stage == 2) { tail_stores(tail_t, true); tail_stage = 0; } };
+    auto pre_hook = [&]() { tail.pre(tail_compute); };
+    auto mid_hook = [&]() { tail.mid(tail_stores); };
 
 #ifdef PW_STAMPS
     unsigned long long rs[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, r0_ = 0, r1_ = 0;
@@ -247,17 +233,15 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
             const uint32_t g = opaque(g_lane);
             const int r = (int)opaque((uint32_t)r_lane);
             ai = Y.s_act[r];
-            if (SINK && P.has_ring) {  // the observation the policy acted on (still in LDS) -> ring.obs
-                const size_t slot = ring_slot(P.ring_start, t, A.B, (long)env, P.ring.capacity);
+            if (SINK && P.sink.has_ring) {  // the observation the policy acted on (still in LDS) -> ring.obs
+                const size_t slot = ring_slot(P.sink.ring_start, t, A.B, (long)env, P.sink.ring.capacity);
                 if (live) {
-                    if (P.ring.state_rows) {
-                        sink_state_obs(P.ring, slot, N, a, L, lmv, px, py, vx, vy);
+                    if (P.sink.ring.state_rows) {
+                        sink_state_obs(P.sink.ring, slot, N, a, L, lmv, px, py, vx, vy);
                     } else {
-                        const float2 *src = reinterpret_cast<const float2 *>(Y.s_obs + r * D);
-                        float2 *dst = reinterpret_cast<float2 *>(P.ring.obs + (slot * N + a) * D);
-                        for (int c = 0; c < D / 2; ++c) dst[c] = src[c];
+                        copy_row2(P.sink.ring.obs + (slot * N + a) * D, Y.s_obs + r * D, D / 2);
                     }
-                    P.ring.act[slot * N + a] = (uint8_t)ai;
+                    P.sink.ring.act[slot * N + a] = (uint8_t)ai;
                 }
             }
             float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
@@ -295,7 +279,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
             if (__any(ends)) {
                 tail_compute();
                 tail_stores(t, false);
-                const bool term = t_term;
+                const bool term = tail.term;
                 if (term && V.auto_reset) {  // same for every lane of an env
                     if (live && V.final_obs)
                         write_row(V.final_obs + (tBN + g) * D);
@@ -321,8 +305,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
                 }
             } else {
                 if (live) write_row(Y.s_obs + r * D);
-                tail_stage = 1;
-                tail_t = t;
+                tail.defer(t);
             }
         }
         PW_R2_STAMP(8);
@@ -333,8 +316,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
     if (blockIdx.x == 0 && lane == 0 && (wave == 0 || wave == 7 || wave == 3))
         for (int i_ = 0; i_ < 10; ++i_) g_pw_tag_stamps[(wave == 0 ? 0 : wave == 7 ? 1 : 2) * 10 + i_] = rs[i_];
 #endif
-    if (tail_stage == 1) tail_compute();
-    if (tail_stage != 0) tail_stores(tail_t, true);
+    tail.flush(tail_compute, tail_stores);
 
     if (live) {
         V.pos_x[g] = px; V.pos_y[g] = py;
@@ -347,13 +329,10 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
         if (a == 0) {
             V.ep_step[env] = ep_step;
             V.ep_count[env] = ep_count;
-            if (SINK && P.episode_return) P.episode_return[env] = ep_ret;
+            if (SINK && P.sink.episode_return) P.sink.episode_return[env] = ep_ret;
         }
     }
-    if (SINK && P.episode_return) {
-        wg_lds_barrier();
-        rollout_finish_stats(envs_here, Y.s_fs, Y.s_fc, P.scratch, P.finished_sum, P.finished_count, Y.red);
-    }
+    if (SINK) rollout_finish_episodes(P.sink, envs_here, Y.s_fs, Y.s_fc, Y.red);
 }
 
 }  // namespace

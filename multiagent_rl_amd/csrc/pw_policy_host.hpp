@@ -36,15 +36,13 @@ int sink_fits(const pw_rollout_sink *sink, int N, int D, int64_t rows)
     return PW_OK;
 }
 
-// The sink into the argument block of a one-launch rollout (PolicyRolloutArgs / PolicyRolloutTagArgs / PolicyRolloutRefArgs: the
-// same fields under the same names; the block is zeroed, so without a sink nothing is set).
-template <typename Args>
-void sink_into(Args &P, const pw_rollout_sink *sink)
+// The sink into the argument block of a one-launch rollout (its RolloutSink member; the block is zeroed, so without a sink nothing is set).
+void sink_into(RolloutSink &K, const pw_rollout_sink *sink)
 {
-    if (sink && sink->ring) { P.ring = *sink->ring; P.has_ring = 1; P.ring_start = sink->ring_start; }
+    if (sink && sink->ring) { K.ring = *sink->ring; K.has_ring = 1; K.ring_start = sink->ring_start; }
     if (sink && sink->episode_return) {
-        P.episode_return = sink->episode_return; P.finished_sum = sink->finished_sum;
-        P.finished_count = sink->finished_count; P.scratch = static_cast<unsigned long long *>(sink->scratch);
+        K.episode_return = sink->episode_return; K.finished_sum = sink->finished_sum;
+        K.finished_count = sink->finished_count; K.scratch = static_cast<unsigned long long *>(sink->scratch);
     }
 }
 

@@ -1,7 +1,8 @@
-// pw_policy_shared.hpp -- part of libpworld.so (translation unit csrc/pworld_policy.hip includes it).
-// Helpers shared by the one-launch policy rollout kernels (pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp, pw_kernels_policy_tag.hpp):
-// the LDS observation row writer, the environment-lane split, opaque(), the ordered shuffles, the ring-sink helpers and the stamp /
-// debug macros of the PW_STAMPS probe builds.
+// pw_policy_shared.hpp -- part of libpworld.so (translation units csrc/pworld_policy.hip and csrc/pworld_policy_generic.hip include it).
+// Helpers shared by the five one-launch policy rollout kernels (pw_kernels_policy3.hpp, pw_kernels_policy3j.hpp, pw_kernels_policy_tag.hpp,
+// pw_kernels_policy_ref.hpp, pw_kernels_policy_generic.hpp): the LDS observation row writer and row copy, the environment-wave split,
+// opaque(), the ordered shuffles, the rollout sink and its ring helpers, the deferred step tail, the episode accounting and the stamp /
+// debug macros of the PW_STAMPS probe builds.  profiles/rollout_tail_codegen.txt: what the compiler made of each, and what stayed inline.
 #pragma once
 
 #include "pw_common.hpp"
@@ -53,6 +54,12 @@ __device__ __forceinline__ EnvWaves env_waves(const int E, const int N, const in
     w.epw = (E + waves_full - 1) / waves_full;
     w.n_waves = (envs_here + w.epw - 1) / w.epw;
     return w;
+}
+
+// LDS row -> global row, n2 = D / 2 8-byte words (the LDS rows are only 8-byte aligned)
+__device__ __forceinline__ void copy_row2(float *dst, const float *src, const int n2)
+{
+    for (int c = 0; c < n2; ++c) reinterpret_cast<float2 *>(dst)[c] = reinterpret_cast<const float2 *>(src)[c];
 }
 
 // A lane's launch-invariant global index passes through this empty asm wherever it feeds an output address: otherwise every
@@ -110,6 +117,19 @@ __device__ __forceinline__ float shfl_add_ordered(float acc, const float v, cons
     return acc;
 }
 
+// Optional direct sink of a one-launch rollout (one member of every kernel's argument block; zeroed = no sink): the transitions go
+// straight into the replay ring (slot (ring_start + t*B + env) % capacity, the order of T pw_replay_add calls; simple_reference: the
+// TWO-HEAD ring, act [cap,N,2] u8) and the episode returns are kept here, so no second launch has to re-read the step outputs (which then
+// may all be NULL)
+struct RolloutSink {
+    pw_replay_store ring;
+    int has_ring;
+    int64_t ring_start;
+    float *episode_return;          // [B] running return per env (or NULL)
+    double *finished_sum;
+    int64_t *finished_count;
+    unsigned long long *scratch;    // [1 + 2 * gridDim.x] words (ticket, partial sums, partial counts: rollout_finish_stats), zeroed once
+};
 // Ring sink of the one-launch rollouts into a STATE ring (pw_replay_store.state_rows: the planes hold {vx, vy, px, py} per agent and the episode's
 // landmarks per transition; pw_replay_gather rebuilds the rows): the pre-step state + this lane's landmarks, and the post-step (pre-reset) state.
 __device__ __forceinline__ void sink_state_obs(const pw_replay_store &ring, const size_t slot, const int N, const int a, const int L,
@@ -132,6 +152,26 @@ __device__ __forceinline__ size_t ring_slot(const int64_t ring_start, const int 
     const int64_t x = ring_start + (int64_t)t * B + env;
     return (size_t)(x >= capacity ? x - capacity : x);
 }
+
+// The rest of an environment step once the agents are advanced and the next observation rows published, in two pieces that the
+// environment waves run inside the NEXT actor pass (actor16_forward's pre / mid windows):
+//   compute()            partner pass / rewards / episode bookkeeping of step t -> rw, acc, term
+//   stores(t, with_obs)  every global store of the step
+// defer(t) leaves both pending; pre() runs the first, mid() the second, flush() after the step loop whatever is left.  A wave with an
+// episode ending in the step runs both at once, with_obs = false, and defers nothing.
+struct StepTail {
+    int stage = 0, t = 0;   // stage: 0 nothing pending, 1 compute pending, 2 stores pending
+    float rw = 0.f, acc = 0.f;
+    bool term = false;
+    __device__ __forceinline__ void defer(const int t_) { stage = 1; t = t_; }
+    template <class C> __device__ __forceinline__ void pre(C &&compute) { if (stage == 1) { compute(); stage = 2; } }
+    template <class S> __device__ __forceinline__ void mid(S &&stores) { if (stage == 2) { stores(t, true); stage = 0; } }
+    template <class C, class S> __device__ __forceinline__ void flush(C &&compute, S &&stores)
+    {
+        if (stage == 1) compute();
+        if (stage != 0) stores(t, true);
+    }
+};
 
 // Finished-episode statistics of a rollout launch (run.py:55-65 bookkeeping summed over all envs): every workgroup leaves its
 // partial (sum, count) in `scratch` (word 0: the ticket; then [gridDim.x] doubles, [gridDim.x] counts); the workgroup that takes the last
@@ -182,6 +222,29 @@ __device__ __forceinline__ void rollout_finish_stats(const int envs_here, double
         *finished_count += scnt;
         *ticket = 0;
     }
+}
+
+// Episode-return accounting of one env and step (run.py:55-65), by the env's agent-0 lane: acc = the step's shared reward; a finished
+// episode's return goes to the env's (sum, count) pair and the running return starts over.  The pair lives in LDS (tag, generic, 3j:
+// touched once per episode) or in registers that are published after the step loop (form 3, simple_reference).
+__device__ __forceinline__ void episode_account(float &ep_ret, const float acc, const bool term, double &fs, int &fc)
+{
+    const float rsum = ep_ret + acc;
+    if (term) { fs += (double)rsum; fc += 1; ep_ret = 0.0f; }
+    else ep_ret = rsum;
+}
+// The per-env (sum, count) pairs of this launch start at zero (a workgroup barrier before the first episode_account)
+__device__ __forceinline__ void rollout_zero_episodes(double *s_fs, int *s_fc)
+{
+    if (threadIdx.x < 16) { s_fs[threadIdx.x] = 0.0; s_fc[threadIdx.x] = 0; }
+}
+// ... and after the last step every workgroup hands them to rollout_finish_stats.  Workgroup-uniform; call with SINK only.
+__device__ __forceinline__ void rollout_finish_episodes(const RolloutSink &K, const int envs_here, double *s_fs, int *s_fc,
+                                                        unsigned char *red)
+{
+    if (!K.episode_return) return;
+    wg_lds_barrier();
+    rollout_finish_stats(envs_here, s_fs, s_fc, K.scratch, K.finished_sum, K.finished_count, red);
 }
 
 }  // namespace

@@ -147,7 +147,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         const int rS1C = (kp.D + 7) / 8;
         if (rS1C != 3) return fail(PW_EINVAL, "simple_reference one-launch rollout: the observation is 21 numbers (3 landmarks)");
         const size_t rshm = policy_ref_lds(4 * rS1C, kp.D, R.A.E).bytes;
-        sink_into(R, sink);
+        sink_into(R.sink, sink);
         if (sink) {
             static unsigned long long attr_sets = 0; /* bit = device */
             PW_LDS_OPTIN(&attr_sets, (pw_policy_rollout_ref_kernel<3, true>));
@@ -206,7 +206,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         if (h->actor_bf16x3) return fail(PW_EINVAL, "PW_ACTOR_BF16X3 serves the simple_spread rollout (and pw_actor_fused) only");
         Q.V = tag_params(h, io);
         Q.T = num_steps; Q.act_out = act_out;
-        sink_into(Q, sink);
+        sink_into(Q.sink, sink);
         const int tS1C = (kp.D + 7) / 8;
         const size_t tshm = policy_tag_lds(4 * tS1C, kp.D, qa.E, kp.L, kp.N).bytes;
         if (tshm > 160 * 1024 || tS1C < 2 || tS1C > 6)
@@ -234,7 +234,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     a.bf16x3 = h->actor_bf16x3;
     P.V = stream_params(h, io);
     P.T = num_steps; P.act_out = act_out;
-    sink_into(P, sink);
+    sink_into(P.sink, sink);
     const int S1C = (kp.D + 7) / 8, S1 = 4 * S1C;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // Kernel forms.  pw_policy_rollout3_kernel (pw_kernels_policy3.hpp): the whole BiLSTM on v_mfma_f32_16x16x4_f32, one timestep

@@ -70,7 +70,7 @@ int pw_internal_policy_rollout_generic(pw_handle *h, const float *frag, const fl
     P.obs = io->obs; P.final_obs = io->final_obs; P.rew = io->rew; P.rew_shared = io->rew_shared;
     P.done = io->done; P.terminal = io->terminal;
     P.T = num_steps; P.act_out = act_out;
-    sink_into(P, sink);
+    sink_into(P.sink, sink);
     const int S1C = (kp.D + 7) / 8;
     const size_t shm = policy_generic_lds(4 * S1C, kp.D, E, kp.N, kp.L).bytes;
     const unsigned grid = (unsigned)((kp.B + E - 1) / E);
