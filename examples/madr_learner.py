@@ -9,6 +9,8 @@ soft updates, Adam, batches drawn through ``memory.make_index`` / ``memory.sampl
 ``BiCNetTrainer`` is the per-agent variant (the BiCNet baseline's tuple, ``experiments/run_BIC.py:46,50`` and
 ``BIC_gumbel_fix.py:155-160``): a ``per_agent`` ring, a critic that returns one Q per agent (``multiagent_rl_amd.critic.BiCNetCritic``)
 and the TD target formed on ``[b, N]``.
+``ModelTrainer`` is the model-learning variant (``model_ddpg_gumbel_fix.py``): networks that return pairs (``ModelActorNetwork`` /
+``ModelCriticNetwork``) and an L1 model loss on each of the two losses.
 ``Trainer(..., fused_optimizer=True)``: each network's clip + Adam step + soft update is one HIP launch
 (``multiagent_rl_amd.optim.FusedAdam``); the default is the stock sequence.
 ``Trainer(..., fused_lstm=True)``: the LSTMs of actor and critic (and of the target networks copied from them) run their recurrence,
@@ -49,8 +51,7 @@ class Trainer(object):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
         if fused_attention:   # before the deep copies, like fused_lstm
-            from multiagent_rl_amd.attention import fuse_attention
-            fuse_attention(self.critic)
+            self._fuse_attention(self.critic)
         if fused_lstm:   # before the deep copies: a class swap survives them, so the target networks are fused too
             from multiagent_rl_amd.lstm import fuse_lstm
             fuse_lstm(self.actor)
@@ -65,6 +66,11 @@ class Trainer(object):
             self.critic_optimizer = FusedAdam(self.critic.parameters(), lr, max_norm=0.5, targets=self.target_critic.parameters(), tau=TAU)
         self.memory, self.action_type, self.batch_size = memory, action_type, batch_size
         self.iter = 0
+
+    @staticmethod
+    def _fuse_attention(critic):
+        from multiagent_rl_amd.attention import fuse_attention
+        fuse_attention(critic)
 
     @staticmethod
     def _sample(logits):
@@ -119,6 +125,59 @@ class Trainer(object):
         self.critic.load_state_dict(torch.load(os.path.join(out_dir, name + '_critic.pt')))
         self.target_actor.load_state_dict(self.actor.state_dict())
         self.target_critic.load_state_dict(self.critic.state_dict())
+
+
+class ModelTrainer(Trainer):
+    """The learner of the model-learning variant (``rls/agent/multiagent/model_ddpg_gumbel_fix.py``): ``actor`` returns ``(policy,
+    next_state)`` and ``critic`` ``(Q, r)`` (``multiagent_rl_amd.policy.ModelActorNetwork`` / ``multiagent_rl_amd.critic.ModelCriticNetwork``);
+    the critic loss gains ``L1(pred_r, r)`` (:171) and the actor loss ``L1(pred_s1, s1)`` (:204).  The no-gradient half keeps the first
+    value of each pair (:150, :158).  Same switches as ``Trainer``; ``fused_attention`` is the swap without the ReLU
+    (``fuse_model_attention``).  The reference's ``l2_reg`` term stays out, as in ``Trainer``."""
+
+    @staticmethod
+    def _fuse_attention(critic):
+        from multiagent_rl_amd.attention import fuse_model_attention
+        fuse_model_attention(critic)
+
+    @torch.no_grad()
+    def get_exploration_action(self, state):
+        import numpy as np
+        obs = torch.from_numpy(np.array([np.stack(state)], dtype='float32')).to(self.device)
+        logits, _ = self.actor(obs)
+        if isinstance(logits, (list, tuple)):
+            return [F.gumbel_softmax(x, hard=True, dim=-1).cpu().numpy() for x in logits]
+        return F.gumbel_softmax(logits, hard=True, dim=-1).cpu().numpy()
+
+    def optimize(self):
+        s0, a0, r, s1, d = (torch.as_tensor(x, dtype=torch.float32, device=self.device)
+                            for x in self.memory.sample_index(self.memory.make_index(self.batch_size)))
+        if r.dim() != 1:
+            raise ValueError('ModelTrainer needs a ring with shared rewards')
+        with torch.no_grad():
+            logits1, _ = self.target_actor(s1)
+            q_next, _ = self.target_critic(s1, self._sample(logits1))
+            y = r.unsqueeze(-1) + GAMMA * (1.0 - d.unsqueeze(-1)) * q_next
+        q, pred_r = self.critic(s0, a0)
+        loss_critic = F.smooth_l1_loss(q, y) + F.l1_loss(pred_r.squeeze(-1), r)
+        self.critic_optimizer.zero_grad()
+        loss_critic.backward()
+        if not self.fused_optimizer:
+            nn.utils.clip_grad_norm_(self.critic.parameters(), 0.5)
+        self.critic_optimizer.step()
+        pred_logits0, pred_s1 = self.actor(s0)
+        loss_actor = -self.critic(s0, self._sample(pred_logits0))[0].mean() + F.l1_loss(pred_s1, s1)
+        self.actor_optimizer.zero_grad()
+        loss_actor.backward()
+        if not self.fused_optimizer:
+            nn.utils.clip_grad_norm_(self.actor.parameters(), 0.5)
+        self.actor_optimizer.step()
+        if not self.fused_optimizer:
+            with torch.no_grad():
+                for tgt, src in ((self.target_actor, self.actor), (self.target_critic, self.critic)):
+                    for pt, ps in zip(tgt.parameters(), src.parameters()):
+                        pt.mul_(1.0 - TAU).add_(ps, alpha=TAU)
+        self.iter += 1
+        return float(loss_actor.detach()), float(loss_critic.detach())
 
 
 class BiCNetTrainer(Trainer):

@@ -14,7 +14,9 @@ critic from the reference checkout on ``sys.path`` (``rls.agent.multiagent.ddpg_
 learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).  ``--critic attention`` gives
 it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``); ``--critic bicnet`` is the BiCNet baseline: per-agent
 transitions (``train_batched(per_agent_transition=True)``), ``multiagent_rl_amd.critic.BiCNetCritic`` and the per-agent stand-in learner
-(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only.  ``--fused-targets`` runs its target networks'
+(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only; ``--critic model`` is the
+paper's own method, the model-learning variant: ``ModelActorNetwork`` / ``ModelCriticNetwork`` and ``madr_learner.ModelTrainer`` (with
+``--reference``: ``model_ddpg_gumbel_fix.Trainer`` and ``ac_network_model_multi_gumbel``) on the shared-reward ring, any number of ranks.  ``--fused-targets`` runs its target networks'
 forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
 soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch, or ``accelerate_trainer(.., optimizer=True)`` with
 ``--reference``), ``--fused-lstm`` runs the recurrence of the learner's LSTMs with gradient on the HIP kernels
@@ -54,13 +56,15 @@ def main(argv=None):
                     help='process group of a multi-rank run: nccl (= RCCL, one GPU per rank) or gloo (the blocks of the full gather '
                          'travel through pinned host buffers; ranks may share a GPU -- RCCL refuses that)')
     ap.add_argument('--reference', action='store_true', help="use the reference's Trainer / CriticNetwork (rls on sys.path)")
-    ap.add_argument('--critic', default='standin', choices=['standin', 'attention', 'bicnet'],
+    ap.add_argument('--critic', default='standin', choices=['standin', 'attention', 'bicnet', 'model'],
                     help="standin: madr_learner's mean-pooling critic; attention: multiagent_rl_amd.critic.CriticNetwork, the "
                          "reference's LSTM + attention architecture (its saved *_critic.pt files load into it); bicnet: the BiCNet "
-                         'baseline -- one Q per agent (multiagent_rl_amd.critic.BiCNetCritic) and per-agent transitions')
+                         'baseline -- one Q per agent (multiagent_rl_amd.critic.BiCNetCritic) and per-agent transitions; model: the '
+                         'model-learning variant -- ModelActorNetwork / ModelCriticNetwork (an actor that also predicts the next '
+                         'observation, an attention critic that also predicts the reward) and the learner with the two L1 model losses')
     ap.add_argument('--fused-targets', action='store_true',
                     help='target actor and target critic of the learner run on the HIP kernels (accelerate_trainer(.., targets=True); '
-                         'needs the attention or the bicnet critic)')
+                         'needs the attention, the bicnet or the model critic)')
     ap.add_argument('--fused-optimizer', action='store_true',
                     help="each network's gradient clip + Adam step + soft update is one HIP launch (madr_learner's fused_optimizer "
                          'switch; with --reference: accelerate_trainer(.., optimizer=True))')
@@ -70,14 +74,14 @@ def main(argv=None):
                          "MIOpen's in the last bits")
     ap.add_argument('--fused-attention', action='store_true',
                     help="the attention block of the learner's critic runs, forward and backward, on the HIP kernels (madr_learner's "
-                         'fused_attention switch; with --reference: accelerate_trainer(.., attention=True)); needs the attention '
-                         'critic; off by default: losses differ from the stock expression in the last bits')
+                         'fused_attention switch; with --reference: accelerate_trainer(.., attention=True)); needs the attention or '
+                         'the model critic; off by default: losses differ from the stock expression in the last bits')
     args = ap.parse_args(argv)
-    if args.fused_attention and args.critic != 'attention' and not args.reference:
-        ap.error('--fused-attention needs --critic attention (the block exists in the LSTM + attention critic only)')
-    if args.fused_targets and args.critic not in ('attention', 'bicnet') and not args.reference:
-        ap.error('--fused-targets needs --critic attention or --critic bicnet (the HIP critics are the LSTM architectures)')
-    bicnet = args.critic == 'bicnet'
+    if args.fused_attention and args.critic not in ('attention', 'model') and not args.reference:
+        ap.error('--fused-attention needs --critic attention or --critic model (the block exists in the LSTM + attention critics only)')
+    if args.fused_targets and args.critic not in ('attention', 'bicnet', 'model') and not args.reference:
+        ap.error('--fused-targets needs --critic attention, bicnet or model (the HIP critics are the LSTM architectures)')
+    bicnet, model = args.critic == 'bicnet', args.critic == 'model'
     if bicnet and int(os.environ.get('WORLD_SIZE', '1')) > 1:
         ap.error('--critic bicnet is single-rank: the multi-rank gather carries the shared reward only')
 
@@ -87,7 +91,14 @@ def main(argv=None):
     from multiagent_rl_amd import arglist, make_batched_env
     from multiagent_rl_amd.policy import ActorNetwork
     from multiagent_rl_amd.train import dims_from_env, seed_everything, train_batched
-    if args.reference and bicnet:
+    if args.reference and model:
+        from rls.agent.multiagent.model_ddpg_gumbel_fix import Trainer
+        from rls.model.ac_network_model_multi_gumbel import ActorNetwork, CriticNetwork
+    elif model:
+        from madr_learner import ModelTrainer as Trainer
+        from multiagent_rl_amd.critic import ModelCriticNetwork as CriticNetwork
+        from multiagent_rl_amd.policy import ModelActorNetwork as ActorNetwork
+    elif args.reference and bicnet:
         from rls.agent.multiagent.BIC_gumbel_fix import Trainer
         from rls.model.ac_network_multi_gumbel_BIC import CriticNetwork
     elif args.reference:

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 114 /* 0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 115 /* 0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -569,6 +569,19 @@ int pw_critic_forward_steps(const float *obs, const int32_t *act_idx, const floa
                             const float *b_hh, const float *w2, const float *b2, int64_t b, int32_t N, int32_t obs_dim,
                             const float *rew /* [b,N] or NULL */, const float *done /* [b,N] or NULL */, float gamma,
                             float *q /* [b,N] */, float *y /* [b,N] or NULL */, void *stream);
+
+/* The model-learning variant's critic (rls/model/ac_network_model_multi_gumbel.py CriticNetwork) and, optionally, the TD target of
+ * model_ddpg_gumbel_fix.py:158-163 as ONE launch: the attention critic of pw_critic_forward WITHOUT the ReLU on the context and with
+ * two heads on it, q [b] = <w2, ctx> + b2 and r_pred [b] = <w3, ctx> + b3 (w3 [1,64] / b3 [1] = dense3), both summed in one order:
+ * equal heads give equal bits.  r_pred == NULL stores no reward prediction, and then w3 / b3 may be NULL (the target critic); r_pred
+ * without w3 / b3 is PW_EINVAL.  y as in pw_critic_forward, from this launch's q.  Action forms, weight layout and every limit as
+ * pw_critic_forward. */
+int pw_critic_forward_model(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
+                            const float *w1, const float *b1, const float *w_ih, const float *w_hh, const float *b_ih,
+                            const float *b_hh, const float *w2, const float *b2, const float *w3 /* or NULL */,
+                            const float *b3 /* or NULL */, int64_t b, int32_t N, int32_t obs_dim, const float *rew /* or NULL */,
+                            const float *done /* or NULL */, float gamma, float *q, float *r_pred /* or NULL */,
+                            float *y /* or NULL */, void *stream);
 
 /* The tail of a network's update as ONE launch (csrc/pw_kernels_optim.hpp states the float32 operation order):
  *   total_norm = sqrt(sum g^2) over ALL tensors of the call; coef = min(1, max_norm / (total_norm + 1e-6))   [torch.nn.utils.clip_grad_norm_]

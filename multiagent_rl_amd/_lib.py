@@ -169,6 +169,10 @@ SIGNATURES = {
     'pw_critic_forward_steps': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32,
                                                                                                 C.c_void_p, C.c_void_p, C.c_float,
                                                                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    'pw_critic_forward_model': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 10 + [C.c_int64, C.c_int32, C.c_int32,
+                                                                                                 C.c_void_p, C.c_void_p, C.c_float,
+                                                                                                 C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                                                 C.c_void_p]),
     'pw_adam_step': (C.c_int, [C.POINTER(PwOptTensor), C.c_int32, C.c_int64] + [C.c_double] * 7 + [C.c_void_p, C.c_void_p]),
     'pw_soft_update': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_double,
                                  C.c_void_p]),

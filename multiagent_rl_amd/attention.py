@@ -11,6 +11,9 @@ Served: float32 on the GPU, 64 hidden units, an agent axis of 1 to ``MAX_STEPS``
 agent axis the kernels do not serve (or one listed in ``HANDED_BACK``) to the forward of the class it was swapped from.  Sums run in
 another order than rocBLAS's, so results differ from the stock expression in the last bits and a seeded run does not reproduce
 across the switch -- which is why it is opt-in everywhere (``accelerate_trainer(trainer, attention=True)``).
+
+The critic of the model-learning variant (``critic.ModelCriticNetwork``: the same block WITHOUT the ReLU, then two heads) is served by
+``fuse_model_attention`` / ``unfuse_model_attention``: the same swap, ``attention_pool(steps, relu=False)``, a pair returned.
 """
 import ctypes as C
 
@@ -133,24 +136,54 @@ class FusedAttention(object):
         return self.dense2(attention_pool(steps, relu=True))
 
 
-_classes = {}   # original class -> its fused subclass
+class FusedModelAttention(object):
+    """What ``fuse_model_attention`` mixes in front of a model-learning critic's class (``critic.ModelCriticNetwork`` or the reference's
+    ``ac_network_model_multi_gumbel.CriticNetwork``): its ``forward`` with the attention lines replaced by
+    ``attention_pool(steps, relu=False)`` -- that critic has no ReLU on the context -- and both heads on the result: ``(dense2(c),
+    dense3(c))``.  Handing back as ``FusedAttention``."""
+    _unfused = None
+
+    def forward(self, obs, action):
+        if not 1 <= obs.shape[-2] <= MAX_STEPS or obs.shape[-2] in HANDED_BACK:
+            return self._unfused.forward(self, obs, action)
+        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
+        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
+        steps, _ = self.lstm(hid, None)
+        ctx = attention_pool(steps, relu=False)
+        return self.dense2(ctx), self.dense3(ctx)
 
 
-def _fused_class(cls):
-    if cls not in _classes:
-        _classes[cls] = type('FusedAttention' + cls.__name__, (FusedAttention, cls), {'_unfused': cls, '__module__': cls.__module__})
-    return _classes[cls]
+_classes = {}   # (mixin, original class) -> its fused subclass
+
+
+def _fused_class(cls, mixin=FusedAttention):
+    if (mixin, cls) not in _classes:
+        _classes[mixin, cls] = type(mixin.__name__ + cls.__name__, (mixin, cls), {'_unfused': cls, '__module__': cls.__module__})
+    return _classes[mixin, cls]
 
 
 def _is_attention_critic(m):
     """By structure, as ``FusedCritic`` reads it: ``dense1`` wrapping ``Linear(., 64)``, a one-layer one-direction batch_first ``lstm`` of 64
-    hidden units, a plain ``Linear(64, .)`` ``dense2`` and no ``dense3`` (the model-learning variant: no ReLU, a second head)."""
+    hidden units, a plain ``Linear(64, .)`` ``dense2`` and no ``dense3`` (the model-learning variant: no ReLU, a second head --
+    ``fuse_model_attention``'s)."""
+    return not hasattr(m, 'dense3') and _has_attention_trunk(m)
+
+
+def _has_attention_trunk(m):
     lin1 = getattr(getattr(m, 'dense1', None), 'module', None)
     lstm, lin2 = getattr(m, 'lstm', None), getattr(m, 'dense2', None)
-    if hasattr(m, 'dense3') or not isinstance(lin1, nn.Linear) or not isinstance(lstm, nn.LSTM) or type(lin2) is not nn.Linear:
+    if not isinstance(lin1, nn.Linear) or not isinstance(lstm, nn.LSTM) or type(lin2) is not nn.Linear:
         return False
     return (lin1.out_features == HIDDEN and lstm.input_size == HIDDEN and lstm.hidden_size == HIDDEN and lstm.num_layers == 1
             and not lstm.bidirectional and lstm.batch_first and not getattr(lstm, 'proj_size', 0) and lin2.in_features == HIDDEN)
+
+
+def _is_model_critic(m):
+    """The model-learning critic by structure: the attention critic's trunk and, beside ``dense2``, a plain ``Linear(64, k)`` ``dense3`` of
+    ``dense2``'s width (a ``dense3`` of another width is some other network: left alone)."""
+    lin3 = getattr(m, 'dense3', None)
+    return (type(lin3) is nn.Linear and _has_attention_trunk(m) and lin3.in_features == HIDDEN
+            and lin3.out_features == m.dense2.out_features)
 
 
 def _modules(module):
@@ -180,7 +213,31 @@ def unfuse_attention(module):
     return n
 
 
+def fuse_model_attention(module):
+    """``fuse_attention`` for the model-learning variant: every model critic inside ``module`` (``module`` itself included) gets
+    ``FusedModelAttention.forward`` by the same swap of ``__class__``.  ``fuse_attention`` leaves such a critic alone and this function
+    leaves an attention critic alone, so both may run over one container.  Returns the number of critics swapped."""
+    n = 0
+    for m in _modules(module):
+        if not isinstance(m, (FusedAttention, FusedModelAttention)) and _is_model_critic(m):
+            m.__class__ = _fused_class(type(m), FusedModelAttention)
+            n += 1
+    return n
+
+
+def unfuse_model_attention(module):
+    """The reverse of ``fuse_model_attention``.  Returns the number swapped back."""
+    n = 0
+    for m in _modules(module):
+        if isinstance(m, FusedModelAttention):
+            m.__class__ = type(m)._unfused
+            n += 1
+    return n
+
+
 def fuse_trainer(trainer):
-    """``fuse_attention`` on ``trainer.critic``, and on ``trainer.target_critic`` while it is still a module (``accelerate_trainer(
-    targets=True)`` replaces it by a wrapper on the no-gradient kernel, which has its own attention).  Returns the number swapped."""
-    return sum(fuse_attention(getattr(trainer, name, None)) for name in ('critic', 'target_critic'))
+    """``fuse_attention`` and ``fuse_model_attention`` on ``trainer.critic``, and on ``trainer.target_critic`` while it is still a module
+    (``accelerate_trainer(targets=True)`` replaces it by a wrapper on the no-gradient kernel, which has its own attention).  Returns the
+    number swapped."""
+    return sum(fuse_attention(getattr(trainer, name, None)) + fuse_model_attention(getattr(trainer, name, None))
+               for name in ('critic', 'target_critic'))

@@ -13,7 +13,7 @@ SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pw
         os.path.join(HERE, 'csrc', 'pworld_attention.hip')]
 OUT = os.path.join(HERE, 'libpworld.so')
 OBJ_DIR = os.path.join(HERE, 'csrc', '_obj')  # git-ignored (*.o); objects are kept so that one unit rebuilds alone
-DEPS = [os.path.join(HERE, 'csrc', f) for f in sorted(os.listdir(os.path.join(HERE, 'csrc'))) if f.endswith(('.hip', '.hpp'))] + \
+DEPS = [os.path.join(HERE, 'csrc', f) for f in sorted(os.listdir(os.path.join(HERE, 'csrc'))) if f.endswith(('.hip', '.hpp', '.inc'))] + \
        [os.path.join(ROOT, 'include', 'pworld.h'), os.path.join(ROOT, 'include', 'pworld_math.h')]
 
 # -ffp-contract=off + correctly rounded div/sqrt: the kernels must reproduce the float32

@@ -15,6 +15,12 @@ Trainer to the HIP kernels.
 ``TimeDistributed(Linear(64, 1))`` on every step's output -- one Q per agent, ``[b, N, 1]``, no attention.  ``FusedCritic`` serves
 it with ``pw_critic_forward_steps`` (q and the per-agent TD target of ``BIC_gumbel_fix.py:155-160`` on ``[b, N]``); which of the
 two critics it wraps is read off the structure: ``dense2`` is a ``TimeDistributed`` there and a plain ``Linear`` here.
+
+``ModelCriticNetwork`` is the critic of the paper's own method, the model-learning variant
+(``rls/model/ac_network_model_multi_gumbel.py:69-143``): the attention critic without the ReLU on the context and with a second head,
+``dense3``, that predicts the reward -- ``forward`` returns ``(Q, r)``.  ``FusedCritic`` serves it with ``pw_critic_forward_model``
+(``model``: a plain ``dense3 = Linear(64, 1)`` beside a plain ``dense2``): ``q``, ``reward``, ``td_target`` from the launch's own q
+(``model_ddpg_gumbel_fix.py:158-163``), and ``forward`` -> the pair.
 """
 import torch
 import torch.nn as nn
@@ -63,10 +69,34 @@ class BiCNetCritic(nn.Module):
         return self.dense2(steps)
 
 
+class ModelCriticNetwork(nn.Module):
+    """Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis -> the attention of ``CriticNetwork`` -> two heads on the
+    context itself (no ReLU): ``dense2`` = Q, ``dense3`` = the predicted reward.  Layer names as the reference's (``dense1.module``,
+    ``lstm``, ``dense2``, ``dense3``).  ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``(Q [b, out_dim], r [b, out_dim])``."""
+
+    def __init__(self, input_dim, out_dim=1):
+        super().__init__()
+        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
+        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+        self.dense2 = nn.Linear(64, out_dim)
+        self.dense3 = nn.Linear(64, out_dim)
+
+    def forward(self, obs, action):
+        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
+        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
+        steps, (h_n, _) = self.lstm(hid, None)
+        score = torch.bmm(steps, h_n[-1].unsqueeze(2)).squeeze(2)
+        weight = F.softmax(score, dim=1)
+        ctx = torch.bmm(steps.transpose(1, 2), weight.unsqueeze(2)).squeeze(2)
+        return self.dense2(ctx), self.dense3(ctx)
+
+
 class FusedCritic(object):
-    """``critic`` (a ``CriticNetwork`` or a ``BiCNetCritic`` -- this module's or the reference's -- on the GPU) evaluated by
-    ``pw_critic_forward`` / ``pw_critic_forward_steps``.  ``per_step`` says which: True where ``critic.dense2`` wraps its Linear in a
-    ``.module`` (the per-step critic: ``q`` / ``td_target`` are ``[b, N]``, ``forward`` ``[b, N, 1]``, ``rew`` / ``done`` ``[b, N]``).
+    """``critic`` (a ``CriticNetwork``, a ``BiCNetCritic`` or a ``ModelCriticNetwork`` -- this module's or the reference's -- on the
+    GPU) evaluated by ``pw_critic_forward`` / ``pw_critic_forward_steps`` / ``pw_critic_forward_model``.  ``per_step`` says which: True
+    where ``critic.dense2`` wraps its Linear in a ``.module`` (the per-step critic: ``q`` / ``td_target`` are ``[b, N]``, ``forward``
+    ``[b, N, 1]``, ``rew`` / ``done`` ``[b, N]``).  ``model``: True where the critic has a ``dense3`` (it must be a plain ``Linear(64, 1)``
+    beside a plain ``dense2``): no ReLU on the context, ``reward(obs, act)`` is the second head and ``forward`` returns ``(q, r)``.
 
     The kernel reads the parameters where the module keeps them (``nn.Module`` layout, no packed image), so every call computes
     with the module's CURRENT values: a soft update in place between two calls needs no ``refresh()``.  No gradient flows through
@@ -81,11 +111,15 @@ class FusedCritic(object):
         self.heads = None if heads is None else tuple(int(h) for h in heads)
         self.per_step = not isinstance(critic.dense2, nn.Linear) and hasattr(critic.dense2, 'module')
         lin1, lstm, lin2 = critic.dense1.module, critic.lstm, self._dense2()
+        lin3 = getattr(critic, 'dense3', None)
+        self.model = lin3 is not None
+        ok3 = not self.model or (not self.per_step and type(lin3) is nn.Linear and lin3.in_features == 64 and lin3.out_features == 1)
         if not (lin1.out_features == 64 and lstm.input_size == 64 and lstm.hidden_size == 64 and lstm.num_layers == 1
-                and not lstm.bidirectional and lstm.batch_first and lin2.in_features == 64 and lin2.out_features == 1):
-            raise ValueError('FusedCritic serves Linear(D + A, 64) -> LSTM(64 -> 64) -> attention -> Linear(64, 1) and the per-step '
-                             'form Linear(D + A, 64) -> LSTM(64 -> 64) -> TimeDistributed(Linear(64, 1)); other heads (e.g. the '
-                             "model-learning variant's dense3) are not served")
+                and not lstm.bidirectional and lstm.batch_first and lin2.in_features == 64 and lin2.out_features == 1 and ok3):
+            raise ValueError('FusedCritic serves Linear(D + A, 64) -> LSTM(64 -> 64) -> attention -> Linear(64, 1), the per-step '
+                             'form Linear(D + A, 64) -> LSTM(64 -> 64) -> TimeDistributed(Linear(64, 1)) and the model-learning form '
+                             'LSTM(64 -> 64) -> attention -> Linear(64, 1) twice (dense2, dense3); other heads (a dense3 that is '
+                             'not a plain Linear(64, 1), or one beside a per-step dense2) are not served')
         self._params()
 
     def _dense2(self):
@@ -95,6 +129,8 @@ class FusedCritic(object):
         c = self.critic
         lin1, lstm, lin2 = c.dense1.module, c.lstm, self._dense2()
         ps = (lin1.weight, lin1.bias, lstm.weight_ih_l0, lstm.weight_hh_l0, lstm.bias_ih_l0, lstm.bias_hh_l0, lin2.weight, lin2.bias)
+        if self.model:
+            ps += (c.dense3.weight, c.dense3.bias)
         dev = ps[0].device
         if dev.type != 'cuda':
             raise RuntimeError('FusedCritic needs the critic on the GPU (no CPU fallback)')
@@ -105,7 +141,8 @@ class FusedCritic(object):
         return ps
 
     @torch.no_grad()
-    def _run(self, obs, act, rew=None, done=None, gamma=0.0):
+    def _run(self, obs, act, rew=None, done=None, gamma=0.0, want_reward=False):
+        """-> (q, y or None); the model form: (q, y or None, r_pred or None)."""
         ps = self._params()
         if obs.dim() != 3:
             raise ValueError('obs must be [b, N, D]')
@@ -146,6 +183,11 @@ class FusedCritic(object):
             y = torch.empty(shape, dtype=torch.float32, device=self.device)
         p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
         stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.model:   # the second head only where it is asked for: the target critic's launch stores no reward prediction
+            rp = torch.empty(shape, dtype=torch.float32, device=self.device) if want_reward else None
+            self._lib_mod.check(self.lib.pw_critic_forward_model(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d),
+                                                                 float(gamma), p(q), p(rp), p(y), stream))
+            return q, y, rp
         entry = self.lib.pw_critic_forward_steps if self.per_step else self.lib.pw_critic_forward
         self._lib_mod.check(entry(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d), float(gamma), p(q), p(y), stream))
         return q, y
@@ -157,11 +199,21 @@ class FusedCritic(object):
     def td_target(self, next_obs, act, rew, done, gamma, return_q=False):
         """-> y [b] = rew + gamma * q(next_obs, act) * (1 - done) from one launch (``return_q``: also that launch's q).  The per-step
         critic: rew, done and y are per agent, [b,N]."""
-        q, y = self._run(next_obs, act, rew, done, gamma)
+        q, y = self._run(next_obs, act, rew, done, gamma)[:2]
         return (y, q) if return_q else y
 
+    def reward(self, obs, act):
+        """The model form's second head: the predicted reward [b] (from a launch that also forms q)."""
+        if not self.model:
+            raise ValueError('reward() needs a model-learning critic (one with dense3)')
+        return self._run(obs, act, want_reward=True)[2]
+
     def forward(self, obs, action):
-        """As the module: ``[b, 1]`` (``[b, N, 1]`` for the per-step critic); a list of action tensors is concatenated along the last axis."""
+        """As the module: ``[b, 1]`` (``[b, N, 1]`` for the per-step critic; the pair ``(q [b, 1], r [b, 1])`` for the model form); a
+        list of action tensors is concatenated along the last axis."""
+        if self.model:
+            q, _, rp = self._run(obs, action, want_reward=True)
+            return q.unsqueeze(-1), rp.unsqueeze(-1)
         return self._run(obs, action)[0].unsqueeze(-1)
 
     __call__ = forward
@@ -184,9 +236,12 @@ class _FusedTarget(object):
 
 def fuse_targets(trainer):
     """``trainer.target_actor`` / ``trainer.target_critic`` -> wrappers on ``FusedActor.logits`` / ``FusedCritic``.
-    Returns ``(fused_target_actor, fused_target_critic)``; the caller refreshes the actor's snapshot after the target moves."""
+    Returns ``(fused_target_actor, fused_target_critic)``; the caller refreshes the actor's snapshot after the target moves.
+    The model-learning variant: a target actor with ``dense3`` returns ``(logits, None)`` -- the no-gradient half discards the
+    predicted next state (``model_ddpg_gumbel_fix.py:150``), so the launch does not form it -- and a model critic the pair ``(q, r)``."""
     fa = FusedActor(trainer.target_actor, seed=0)
     fc = FusedCritic(trainer.target_critic)
-    trainer.target_actor = _FusedTarget(trainer.target_actor, fa.logits)
+    actor_forward = (lambda obs: (fa.logits(obs), None)) if hasattr(trainer.target_actor, 'dense3') else fa.logits
+    trainer.target_actor = _FusedTarget(trainer.target_actor, actor_forward)
     trainer.target_critic = _FusedTarget(trainer.target_critic, fc.forward)
     return fa, fc

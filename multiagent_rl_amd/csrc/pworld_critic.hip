@@ -1,6 +1,7 @@
 // libpworld.so, third translation unit -- the learner's critic forward and TD target (rls/model/ac_network_multi_gumbel.py
 // CriticNetwork, ddpg_gumbel_fix.py:148-154): pw_critic_forward; and the BiCNet baseline's per-step critic with its per-agent TD
-// target (ac_network_multi_gumbel_BIC.py CriticNetwork, BIC_gumbel_fix.py:155-160): pw_critic_forward_steps.  The kernel is csrc/pw_kernels_critic.hpp; the gate functions
+// target (ac_network_multi_gumbel_BIC.py CriticNetwork, BIC_gumbel_fix.py:155-160): pw_critic_forward_steps; and the model-learning
+// variant's two-head critic (ac_network_model_multi_gumbel.py CriticNetwork, model_ddpg_gumbel_fix.py:158-163): pw_critic_forward_model.  The kernel is csrc/pw_kernels_critic.hpp; the gate functions
 // and the LDS barrier are the actor's (pw_lstm_math.hpp: included, not copied).  Declared in include/pworld.h; the error text
 // is shared with pworld.hip.
 #include "pw_host.hpp"
@@ -35,7 +36,20 @@ int critic_steps_launch(const CriticArgs &C, hipStream_t stream)
     return PW_OK;
 }
 
-// the arguments both entry points share; fills everything of C but R
+template <int KO, int KA>
+int critic_model_launch(const CriticModelArgs &C, hipStream_t stream)
+{
+    static unsigned long long optin_mask = 0;
+    void (*const kernel)(const CriticModelArgs) = pw_critic_forward_kernel<KO, KA>;
+    const size_t lds = critic_lds(C.N, C.R).bytes;
+    PW_LDS_OPTIN(&optin_mask, kernel);
+    const long groups = (C.b + C.R - 1) / C.R;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);
+    PW_HIP_CHECK(hipGetLastError());
+    return PW_OK;
+}
+
+// the arguments all entry points share; fills everything of C but R
 int critic_args(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1, const float *w1,
                 const float *b1, const float *w_ih, const float *w_hh, const float *b_ih, const float *b_hh, const float *w2,
                 const float *b2, int64_t b, int32_t N, int32_t obs_dim, const float *rew, const float *done, float gamma, float *q,
@@ -94,6 +108,29 @@ int pw_critic_forward_steps(const float *obs, const int32_t *act_idx, const floa
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;
 #define PW_CRITIC_GO(KO) return sa <= 2 ? critic_steps_launch<KO, 2>(C, s) : critic_steps_launch<KO, 4>(C, s)
+    if (so <= 4) PW_CRITIC_GO(4);
+    if (so <= 8) PW_CRITIC_GO(8);
+    if (so <= 16) PW_CRITIC_GO(16);
+    PW_CRITIC_GO(26);
+#undef PW_CRITIC_GO
+}
+
+int pw_critic_forward_model(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
+                            const float *w1, const float *b1, const float *w_ih, const float *w_hh, const float *b_ih,
+                            const float *b_hh, const float *w2, const float *b2, const float *w3, const float *b3, int64_t b,
+                            int32_t N, int32_t obs_dim, const float *rew, const float *done, float gamma, float *q, float *r_pred,
+                            float *y, void *stream)
+{
+    CriticModelArgs C;
+    if (int rc = critic_args(obs, act_idx, act_vec, n_act0, n_act1, w1, b1, w_ih, w_hh, b_ih, b_hh, w2, b2, b, N, obs_dim, rew, done,
+                             gamma, q, y, C))
+        return rc;
+    if (r_pred && (!w3 || !b3)) return fail(PW_EINVAL, "the reward prediction needs w3 and b3");
+    C.w3 = w3; C.b3 = b3; C.r_pred = r_pred;
+    C.R = N <= 32 ? 16 : 8;  // pw_critic_forward's rule: the same LDS layout
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;
+#define PW_CRITIC_GO(KO) return sa <= 2 ? critic_model_launch<KO, 2>(C, s) : critic_model_launch<KO, 4>(C, s)
     if (so <= 4) PW_CRITIC_GO(4);
     if (so <= 8) PW_CRITIC_GO(8);
     if (so <= 16) PW_CRITIC_GO(16);

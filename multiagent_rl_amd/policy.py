@@ -59,6 +59,28 @@ class ActorNetwork(nn.Module):
         return self.dense2(hid)
 
 
+class ModelActorNetwork(ActorNetwork):
+    """The actor of the model-learning variant (``rls/model/ac_network_model_multi_gumbel.py:23-66``): ``ActorNetwork`` with a third
+    head, ``dense3`` = TimeDistributed(Linear(64, input_dim)), that predicts the next observation from the same ReLU'd BiLSTM output.
+    ``forward`` returns ``(policy, next_state)``; ``policy`` is what ``ActorNetwork.forward`` returns.  Parameter names as the
+    reference's (``dense3.module`` behind the policy head(s)), so its Trainer's ``*_actor.pt`` files load unchanged.  ``FusedActor``
+    serves it as it is: the rollout and the target half read the policy head(s) only."""
+
+    def __init__(self, input_dim, out_dim):
+        super().__init__(input_dim, out_dim)
+        self.dense3 = TimeDistributed(nn.Linear(64, input_dim))
+
+    def forward(self, obs):
+        hid = F.relu(self.dense1(obs))
+        hid, _ = self.bilstm(hid, None)
+        hid = F.relu(hid)
+        if type(self.out_dim) is list:
+            policy = [self.dense2_1(hid), self.dense2_2(hid)]
+        else:
+            policy = self.dense2(hid)
+        return policy, self.dense3(hid)
+
+
 class GumbelPolicy(object):
     """obs [B,N,D] (device) -> action index [B,N] int32 (device)."""
 
@@ -348,9 +370,13 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
 
     ``attention=True`` runs the attention block of ``trainer.critic`` -- and of ``trainer.target_critic`` unless ``targets=True`` has
     already wrapped it -- on the HIP kernels with gradient (``multiagent_rl_amd.attention.fuse_attention``: a class swap to a subclass
-    of the critic's own class, one launch forward and one backward instead of ``bmm`` / ``softmax`` / ``bmm`` / ``relu``).  A critic
-    without that block (the BiCNet critic, the model-learning variant) is left as it is.  Opt-in for the same reason: the sums run in
-    another order than rocBLAS's."""
+    of the critic's own class, one launch forward and one backward instead of ``bmm`` / ``softmax`` / ``bmm`` / ``relu``).  The critic
+    of the model-learning variant (a ``dense3`` beside ``dense2``) gets the same block without the ReLU (``fuse_model_attention``); a
+    critic without that block (the BiCNet critic) is left as it is.  Opt-in for the same reason: the sums run in another order than
+    rocBLAS's.
+
+    The model-learning variant's Trainer (``model_ddpg_gumbel_fix.py``) is served by every switch: with ``targets=True`` the target
+    actor's wrapper returns ``(logits, None)`` and the target critic's ``(q, r)``, as that Trainer unpacks them."""
     fx = FusedExploration(trainer.actor, getattr(trainer, 'action_type', 'Discrete'), seed=seed)
     trainer.get_exploration_action = fx.get_exploration_action
     target_actor = None

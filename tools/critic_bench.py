@@ -21,6 +21,11 @@ Launch counts: kernels seen by torch.profiler in one call of each path.
         pw_actor_fused + sampling + pw_critic_forward_steps, "stock - fused" beside the spread of stock's repeats; then, at N = 48 and 64,
         FusedCritic.q alone on the per-step kernel (16 rows per workgroup) beside the attention kernel (8 rows), at b = 1024 and b = 8192.  A record,
         not a gate.
+    python tools/critic_bench.py --model [--out profiles/critic_model_td_target.txt]   # the model-learning variant: target
+        ModelActorNetwork (the first of its pair), sampling, target ModelCriticNetwork (the first of its pair), y, at N in {3, 6, 12, 24}:
+        (a) stock against (b) pw_actor_fused + sampling + pw_critic_forward_model (no reward head in that launch), "stock - fused"
+        beside the spread of stock's repeats; then one optimize() of examples/madr_learner.py's ModelTrainer at N = 6, unpatched against
+        all four switches.  A record, not a gate.
 Then the example learner (examples/madr_learner.py Trainer with the attention critic) at N = 6: wall time per optimize() with and
 without accelerate_trainer(targets=True), five repeats each, alternating.
 Exit status 1 if at N = 6 path (b) is not faster than path (a) by more than the spread (max - min) of (a)'s five repeats.
@@ -191,6 +196,127 @@ def bicnet_rows(args):
     return 0
 
 
+def make_model_paths(N, D):
+    """The no-gradient half of model_ddpg_gumbel_fix.py:150-163."""
+    from multiagent_rl_amd.critic import FusedCritic, ModelCriticNetwork
+    from multiagent_rl_amd.policy import FusedActor, ModelActorNetwork
+    torch.manual_seed(N)
+    actor, critic = ModelActorNetwork(D, 5).cuda().eval(), ModelCriticNetwork(D + 5, 1).cuda().eval()
+    s1 = torch.randn(B, N, D, device='cuda')
+    r, d = torch.randn(B, device='cuda'), (torch.rand(B, device='cuda') < 0.1).float()
+    fused_actor, fc = FusedActor(actor), FusedCritic(critic)
+
+    def sample(logits):
+        return F.gumbel_softmax(logits.reshape(B * N, -1), hard=True).reshape(B, N, -1)
+
+    @torch.no_grad()
+    def stock():
+        logits1, _ = actor(s1)
+        q_next, _ = critic(s1, sample(logits1))
+        return r + GAMMA * torch.squeeze(q_next) * (1. - d)
+
+    @torch.no_grad()
+    def fused():
+        return fc.td_target(s1, sample(fused_actor.logits(s1)), r, d, GAMMA)
+    return stock, fused
+
+
+def model_rows(args):
+    """The model-learning variant: the TD-target table, then ModelTrainer.optimize() unpatched against all four switches at N = 6."""
+    import madr_learner
+    from multiagent_rl_amd import make_batched_env
+    from multiagent_rl_amd.critic import ModelCriticNetwork
+    from multiagent_rl_amd.policy import ActorNetwork, FusedActor, ModelActorNetwork, accelerate_trainer
+    from multiagent_rl_amd.replay_buffer import ReplayBuffer
+    lines = ['Model-learning variant, TD target of a batch, b = %d, D = 4 + 2 N, A = 5: device-event us per call (%d calls per repeat, '
+             '%d repeats, paths alternating)' % (B, args.iters, REPEATS),
+             '(a) stock PyTorch-ROCm: ModelActorNetwork, hard Gumbel one-hot, ModelCriticNetwork, y;  (b) pw_actor_fused + the same '
+             'sampling + pw_critic_forward_model with the epilogue (r_pred = NULL)',
+             '%-4s %-5s %-38s %-38s %-8s %-26s %s' % ('N', 'D', '(a) mean [min, max]', '(b) mean [min, max]', 'a / b',
+                                                     '(a) - (b) | spread of (a)', 'launches a | b')]
+    for N in (3, 6, 12, 24):
+        D = 4 + 2 * N
+        stock, fused = make_model_paths(N, D)
+        for _ in range(20):
+            stock()
+            fused()
+        torch.cuda.synchronize()
+        ta, tb = [], []
+        for _ in range(REPEATS):
+            ta.append(device_time_us(stock, args.iters))
+            tb.append(device_time_us(fused, args.iters))
+        ma, mb = sum(ta) / REPEATS, sum(tb) / REPEATS
+        lines.append('%-4d %-5d %8.1f [%8.1f, %8.1f] %9s %8.1f [%8.1f, %8.1f] %9s %-8.2f %8.1f | %-15.1f %s | %s  %s' % (
+            N, D, ma, min(ta), max(ta), '', mb, min(tb), max(tb), '', ma / mb, ma - mb, max(ta) - min(ta), launches(stock), launches(fused),
+            'gain beyond the spread' if ma - mb > max(ta) - min(ta) else 'gain NOT beyond the spread'))
+    lines.append('')
+    lines.append('The critic launch alone (index actions, TD-target epilogue), b = %d: device-event us per call, launch overhead included: the '
+                 'attention form (pw_critic_forward) beside the model form without and with the reward head' % B)
+    from multiagent_rl_amd.critic import CriticNetwork, FusedCritic
+    for N in (3, 6, 12, 24):
+        D = 4 + 2 * N
+        torch.manual_seed(N)
+        fa, fm = FusedCritic(CriticNetwork(D + 5, 1).cuda().eval()), FusedCritic(ModelCriticNetwork(D + 5, 1).cuda().eval())
+        s1 = torch.randn(B, N, D, device='cuda')
+        idx = torch.randint(0, 5, (B, N), device='cuda', dtype=torch.int32)
+        r, d = torch.randn(B, device='cuda'), (torch.rand(B, device='cuda') < 0.1).float()
+        group = [('attention', lambda: fa.td_target(s1, idx, r, d, GAMMA)), ('model, q and y', lambda: fm.td_target(s1, idx, r, d, GAMMA)),
+                 ('model, q, r_pred and y', lambda: fm._run(s1, idx, r, d, GAMMA, want_reward=True))]
+        for _ in range(20):
+            for _, fn in group:
+                fn()
+        torch.cuda.synchronize()
+        t = {name: [] for name, _ in group}
+        for _ in range(REPEATS):
+            for name, fn in group:
+                t[name].append(device_time_us(fn, args.iters))
+        lines.append('  N = %-3d D = %-4d %s' % (N, D, '   '.join('%s mean %6.1f [%6.1f, %6.1f]' % (
+            name, sum(v) / len(v), min(v), max(v)) for name, v in t.items())))
+    N = 6
+    env = make_batched_env('simple_spread', 1024, auto_reset=True, max_episode_len=25, seed=1, n=N)
+    env.reset()
+    D = env.obs_dim
+    memory = ReplayBuffer(int(1e5), N, D, device_index=True)
+    torch.manual_seed(0)
+    FusedActor(ActorNetwork(D, 5).cuda().eval(), seed=1).rollout(env, 50, out=False, memory=memory)
+    trainers = {}
+    for name in ('unpatched', 'all four switches'):
+        torch.manual_seed(1)
+        on = name != 'unpatched'
+        tr = madr_learner.ModelTrainer(ModelActorNetwork(D, 5), ModelCriticNetwork(D + 5, 1), memory, batch_size=B, fused_optimizer=on,
+                                       fused_lstm=on, fused_attention=on)
+        if on:
+            accelerate_trainer(tr, targets=True)
+        trainers[name] = tr
+    res = {k: [] for k in trainers}
+    for tr in trainers.values():
+        for _ in range(10):
+            tr.optimize()
+    iters = 30
+    for _ in range(REPEATS):
+        for name, tr in trainers.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                tr.optimize()
+            torch.cuda.synchronize()
+            res[name].append((time.perf_counter() - t0) / iters * 1e3)
+    lines.append('')
+    lines.append('examples/madr_learner.py ModelTrainer, simple_spread N = 6, b = %d: wall ms per optimize() (%d calls per repeat)' % (B, iters))
+    for name, v in res.items():
+        lines.append('  %-28s mean %.3f  min %.3f  max %.3f   [%s]' % (name, sum(v) / len(v), min(v), max(v), ' '.join('%.3f' % x for x in v)))
+    a, b = res['unpatched'], res['all four switches']
+    gain, spread = sum(a) / len(a) - sum(b) / len(b), max(a) - min(a)
+    lines.append('  unpatched - switched = %.3f ms against the spread of the unpatched repeats %.3f ms: the gain %s' % (
+        gain, spread, 'counts' if gain > spread else 'does NOT count'))
+    text = '\n'.join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(text + '\n')
+    return 0
+
+
 def learner_times(lines, iters):
     """Wall time per optimize() of the example learner at N = 6, with / without the fused targets."""
     import madr_learner
@@ -243,9 +369,13 @@ def main():
     ap.add_argument('--wide', action='store_true', help='N = 48 (D = 100) alone: three TD-target paths and the actor alone')
     ap.add_argument('--bicnet', action='store_true', help='the per-step (BiCNet) critic: TD-target table at N = 3 .. 64 and the kernel beside '
                                                           "the attention critic's at N = 48 / 64 (a record, not a gate)")
+    ap.add_argument('--model', action='store_true', help='the model-learning variant: TD-target table at N = 3 .. 24 and ModelTrainer.optimize() '
+                                                         'unpatched against all four switches (a record, not a gate)')
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('critic_bench: needs a GPU (no fallback)')
+    if args.model:
+        return model_rows(args)
     if args.bicnet:
         return bicnet_rows(args)
     if args.wide:
