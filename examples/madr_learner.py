@@ -72,6 +72,19 @@ class Trainer(object):
         from multiagent_rl_amd.attention import fuse_attention
         fuse_attention(critic)
 
+    # What ModelTrainer overrides: its networks return pairs, and each loss gains an L1 term on the pair's second value.
+    @staticmethod
+    def _first(out):
+        return out
+
+    @staticmethod
+    def _with_reward_loss(loss, out, r):
+        return loss
+
+    @staticmethod
+    def _with_state_loss(loss, out, s1):
+        return loss
+
     @staticmethod
     def _sample(logits):
         if isinstance(logits, (list, tuple)):       # MultiDiscrete: one one-hot per head, concatenated (run.py:39-41)
@@ -82,7 +95,7 @@ class Trainer(object):
     def get_exploration_action(self, state):
         import numpy as np
         obs = torch.from_numpy(np.array([np.stack(state)], dtype='float32')).to(self.device)
-        logits = self.actor(obs)
+        logits = self._first(self.actor(obs))
         if isinstance(logits, (list, tuple)):
             return [F.gumbel_softmax(x, hard=True, dim=-1).cpu().numpy() for x in logits]
         return F.gumbel_softmax(logits, hard=True, dim=-1).cpu().numpy()
@@ -93,14 +106,17 @@ class Trainer(object):
         if r.dim() != (2 if self.per_agent else 1):
             raise ValueError('%s needs a ring with %s rewards' % (type(self).__name__, 'per-agent' if self.per_agent else 'shared'))
         with torch.no_grad():   # shared: [b,1]; per agent: [b,N,1] (q_next one per agent, y formed on [b,N])
-            y = r.unsqueeze(-1) + GAMMA * (1.0 - d.unsqueeze(-1)) * self.target_critic(s1, self._sample(self.target_actor(s1)))
-        loss_critic = F.smooth_l1_loss(self.critic(s0, a0), y)
+            q_next = self._first(self.target_critic(s1, self._sample(self._first(self.target_actor(s1)))))
+            y = r.unsqueeze(-1) + GAMMA * (1.0 - d.unsqueeze(-1)) * q_next
+        out = self.critic(s0, a0)
+        loss_critic = self._with_reward_loss(F.smooth_l1_loss(self._first(out), y), out, r)
         self.critic_optimizer.zero_grad()
         loss_critic.backward()
         if not self.fused_optimizer:
             nn.utils.clip_grad_norm_(self.critic.parameters(), 0.5)
         self.critic_optimizer.step()
-        loss_actor = -self.critic(s0, self._sample(self.actor(s0))).mean()
+        out = self.actor(s0)
+        loss_actor = self._with_state_loss(-self._first(self.critic(s0, self._sample(self._first(out)))).mean(), out, s1)
         self.actor_optimizer.zero_grad()
         loss_actor.backward()
         if not self.fused_optimizer:
@@ -139,45 +155,17 @@ class ModelTrainer(Trainer):
         from multiagent_rl_amd.attention import fuse_model_attention
         fuse_model_attention(critic)
 
-    @torch.no_grad()
-    def get_exploration_action(self, state):
-        import numpy as np
-        obs = torch.from_numpy(np.array([np.stack(state)], dtype='float32')).to(self.device)
-        logits, _ = self.actor(obs)
-        if isinstance(logits, (list, tuple)):
-            return [F.gumbel_softmax(x, hard=True, dim=-1).cpu().numpy() for x in logits]
-        return F.gumbel_softmax(logits, hard=True, dim=-1).cpu().numpy()
+    @staticmethod
+    def _first(out):
+        return out[0]
 
-    def optimize(self):
-        s0, a0, r, s1, d = (torch.as_tensor(x, dtype=torch.float32, device=self.device)
-                            for x in self.memory.sample_index(self.memory.make_index(self.batch_size)))
-        if r.dim() != 1:
-            raise ValueError('ModelTrainer needs a ring with shared rewards')
-        with torch.no_grad():
-            logits1, _ = self.target_actor(s1)
-            q_next, _ = self.target_critic(s1, self._sample(logits1))
-            y = r.unsqueeze(-1) + GAMMA * (1.0 - d.unsqueeze(-1)) * q_next
-        q, pred_r = self.critic(s0, a0)
-        loss_critic = F.smooth_l1_loss(q, y) + F.l1_loss(pred_r.squeeze(-1), r)
-        self.critic_optimizer.zero_grad()
-        loss_critic.backward()
-        if not self.fused_optimizer:
-            nn.utils.clip_grad_norm_(self.critic.parameters(), 0.5)
-        self.critic_optimizer.step()
-        pred_logits0, pred_s1 = self.actor(s0)
-        loss_actor = -self.critic(s0, self._sample(pred_logits0))[0].mean() + F.l1_loss(pred_s1, s1)
-        self.actor_optimizer.zero_grad()
-        loss_actor.backward()
-        if not self.fused_optimizer:
-            nn.utils.clip_grad_norm_(self.actor.parameters(), 0.5)
-        self.actor_optimizer.step()
-        if not self.fused_optimizer:
-            with torch.no_grad():
-                for tgt, src in ((self.target_actor, self.actor), (self.target_critic, self.critic)):
-                    for pt, ps in zip(tgt.parameters(), src.parameters()):
-                        pt.mul_(1.0 - TAU).add_(ps, alpha=TAU)
-        self.iter += 1
-        return float(loss_actor.detach()), float(loss_critic.detach())
+    @staticmethod
+    def _with_reward_loss(loss, out, r):
+        return loss + F.l1_loss(out[1].squeeze(-1), r)
+
+    @staticmethod
+    def _with_state_loss(loss, out, s1):
+        return loss + F.l1_loss(out[1], s1)
 
 
 class BiCNetTrainer(Trainer):

@@ -14,6 +14,9 @@ across the switch -- which is why it is opt-in everywhere (``accelerate_trainer(
 
 The critic of the model-learning variant (``critic.ModelCriticNetwork``: the same block WITHOUT the ReLU, then two heads) is served by
 ``fuse_model_attention`` / ``unfuse_model_attention``: the same swap, ``attention_pool(steps, relu=False)``, a pair returned.
+
+What every critic of the family shares lives here too, once, and ``critic.py`` imports it (this module imports only ``_lib``): the trunk
+``lstm_trunk``, the stock attention expression ``attend`` and the structural classifier ``critic_form``.
 """
 import ctypes as C
 
@@ -112,82 +115,119 @@ def attention_pool(Y, relu=True):
     return _Pool.apply(Y, bool(relu))
 
 
-def stock_attention(steps, relu=True):
-    """The same block as ``CriticNetwork.forward`` writes it (two ``bmm``s and a softmax): the expression the kernels replace."""
-    score = torch.bmm(steps, steps[:, -1].unsqueeze(2)).squeeze(2)
+def attend(steps, query, relu):
+    """The stock attention expression (two ``bmm``s and a softmax): every step scored against ``query``, softmax over the agent axis,
+    weighted sum, ReLU if asked.  The critic modules pass ``h_n[-1]`` as the reference writes it; ``stock_attention`` the last step."""
+    score = torch.bmm(steps, query.unsqueeze(2)).squeeze(2)
     weight = F.softmax(score, dim=1)
     ctx = torch.bmm(steps.transpose(1, 2), weight.unsqueeze(2)).squeeze(2)
     return F.relu(ctx) if relu else ctx
 
 
+def stock_attention(steps, relu=True):
+    """The same block as ``CriticNetwork.forward`` writes it, on the LSTM's output alone: the expression the kernels replace."""
+    return attend(steps, steps[:, -1], relu)
+
+
+# ---- what every critic of the family shares: the trunk and the question which form a module is ----------------------------------
+def lstm_trunk(m, obs, action):
+    """``m.dense1`` on ``[obs, action...]`` (``action`` a tensor or a list of them), ReLU, ``m.lstm`` over the agent axis
+    -> ``(steps [b,N,64], h_n [1,b,64])``.  ``m``: any module with the family's ``dense1`` and ``lstm``, this project's or not."""
+    parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
+    hid = F.relu(m.dense1(torch.cat(parts, dim=-1)))
+    steps, (h_n, _) = m.lstm(hid, None)
+    return steps, h_n
+
+
+def _linear(m, wrapped=False):
+    """``m`` (``wrapped``: ``m.module``, the TimeDistributed form) if it is a Linear, else None."""
+    if wrapped:
+        m = None if isinstance(m, nn.Linear) else getattr(m, 'module', None)
+    return m if isinstance(m, nn.Linear) else None
+
+
+def critic_form(m):
+    """Which critic ``m`` is, by structure -> ``(form, head widths)``.  The trunk of all three: ``dense1`` wrapping ``Linear(., 64)`` and a
+    one-layer one-direction batch_first ``lstm`` of 64 hidden units.  Then ``'attention'``: a plain ``Linear(64, k)`` ``dense2`` and no
+    ``dense3``, widths ``(k,)``; ``'steps'``: ``dense2`` wraps its Linear in a ``.module`` (the per-step critic), no ``dense3``, ``(k,)``;
+    ``'model'``: beside a plain ``dense2`` a plain ``Linear(64, k)`` ``dense3`` of the same width, ``(k, k)``.  Anything else (a wrapped
+    ``dense3``, one beside a per-step ``dense2``, one of another width) is some other network: ``(None, ())``."""
+    lin1, lstm = _linear(getattr(m, 'dense1', None), wrapped=True), getattr(m, 'lstm', None)
+    if lin1 is None or lin1.out_features != HIDDEN or not isinstance(lstm, nn.LSTM):
+        return None, ()
+    if not (lstm.input_size == HIDDEN and lstm.hidden_size == HIDDEN and lstm.num_layers == 1 and not lstm.bidirectional
+            and lstm.batch_first and not getattr(lstm, 'proj_size', 0)):
+        return None, ()
+    dense2, dense3 = getattr(m, 'dense2', None), getattr(m, 'dense3', None)
+    plain, step = _linear(dense2), _linear(dense2, wrapped=True)
+    lin2 = plain or step
+    if lin2 is None or lin2.in_features != HIDDEN:
+        return None, ()
+    if dense3 is None:
+        return ('attention' if plain else 'steps'), (lin2.out_features,)
+    if plain and type(dense3) is nn.Linear and dense3.in_features == HIDDEN and dense3.out_features == lin2.out_features:
+        return 'model', (lin2.out_features, dense3.out_features)
+    return None, ()
+
+
 # ---- the module surface ---------------------------------------------------------------------------------------------------------
-class FusedAttention(object):
-    """What ``fuse_attention`` mixes in front of a critic's class: ``CriticNetwork.forward`` with the three attention lines and the
-    ReLU replaced by ``attention_pool(steps, relu=True)``.  Everything else, parameters and ``state_dict`` keys included, is the
-    original class's (``_unfused``), to whose ``forward`` an agent axis that is not served (or is in ``HANDED_BACK``) goes."""
+class _Fused(object):
+    """The one ``forward`` of the two mixins: the trunk, ``attention_pool`` in place of the attention lines, the head(s).  Everything
+    else, parameters and ``state_dict`` keys included, is the original class's (``_unfused``), to whose ``forward`` an agent axis that
+    is not served (or is in ``HANDED_BACK``) goes."""
     _unfused = None
+    _model = False
 
     def forward(self, obs, action):
         if not 1 <= obs.shape[-2] <= MAX_STEPS or obs.shape[-2] in HANDED_BACK:
             return self._unfused.forward(self, obs, action)
-        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
-        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
-        steps, _ = self.lstm(hid, None)   # the query is steps[:, -1] = h_n[-1] (nn.LSTM computes the same number; FusedLSTM slices it)
-        return self.dense2(attention_pool(steps, relu=True))
+        steps, _ = lstm_trunk(self, obs, action)   # the query is steps[:, -1] = h_n[-1] (nn.LSTM computes the same number; FusedLSTM slices it)
+        ctx = attention_pool(steps, relu=not self._model)
+        return (self.dense2(ctx), self.dense3(ctx)) if self._model else self.dense2(ctx)
 
 
-class FusedModelAttention(object):
+class FusedAttention(_Fused):
+    """What ``fuse_attention`` mixes in front of a critic's class: ``CriticNetwork.forward`` with the three attention lines and the
+    ReLU replaced by ``attention_pool(steps, relu=True)``."""
+
+
+class FusedModelAttention(_Fused):
     """What ``fuse_model_attention`` mixes in front of a model-learning critic's class (``critic.ModelCriticNetwork`` or the reference's
     ``ac_network_model_multi_gumbel.CriticNetwork``): its ``forward`` with the attention lines replaced by
     ``attention_pool(steps, relu=False)`` -- that critic has no ReLU on the context -- and both heads on the result: ``(dense2(c),
-    dense3(c))``.  Handing back as ``FusedAttention``."""
-    _unfused = None
-
-    def forward(self, obs, action):
-        if not 1 <= obs.shape[-2] <= MAX_STEPS or obs.shape[-2] in HANDED_BACK:
-            return self._unfused.forward(self, obs, action)
-        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
-        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
-        steps, _ = self.lstm(hid, None)
-        ctx = attention_pool(steps, relu=False)
-        return self.dense2(ctx), self.dense3(ctx)
+    dense3(c))``."""
+    _model = True
 
 
+_MIXIN = {'attention': FusedAttention, 'model': FusedModelAttention}   # the per-step form has no attention block
 _classes = {}   # (mixin, original class) -> its fused subclass
 
 
-def _fused_class(cls, mixin=FusedAttention):
+def _fused_class(cls, mixin):
     if (mixin, cls) not in _classes:
         _classes[mixin, cls] = type(mixin.__name__ + cls.__name__, (mixin, cls), {'_unfused': cls, '__module__': cls.__module__})
     return _classes[mixin, cls]
 
 
-def _is_attention_critic(m):
-    """By structure, as ``FusedCritic`` reads it: ``dense1`` wrapping ``Linear(., 64)``, a one-layer one-direction batch_first ``lstm`` of 64
-    hidden units, a plain ``Linear(64, .)`` ``dense2`` and no ``dense3`` (the model-learning variant: no ReLU, a second head --
-    ``fuse_model_attention``'s)."""
-    return not hasattr(m, 'dense3') and _has_attention_trunk(m)
+def _reclass(module, new_class):
+    """Every module inside ``module`` (itself included; nothing if it is no module) for which ``new_class(m)`` names a class gets it."""
+    n = 0
+    for m in (module.modules() if isinstance(module, nn.Module) else ()):
+        cls = new_class(m)
+        if cls is not None:
+            m.__class__ = cls
+            n += 1
+    return n
 
 
-def _has_attention_trunk(m):
-    lin1 = getattr(getattr(m, 'dense1', None), 'module', None)
-    lstm, lin2 = getattr(m, 'lstm', None), getattr(m, 'dense2', None)
-    if not isinstance(lin1, nn.Linear) or not isinstance(lstm, nn.LSTM) or type(lin2) is not nn.Linear:
-        return False
-    return (lin1.out_features == HIDDEN and lstm.input_size == HIDDEN and lstm.hidden_size == HIDDEN and lstm.num_layers == 1
-            and not lstm.bidirectional and lstm.batch_first and not getattr(lstm, 'proj_size', 0) and lin2.in_features == HIDDEN)
+def _swap(module, forms):
+    """Critics of one of ``forms`` that are not swapped yet -> the fused subclass of their own class."""
+    return _reclass(module, lambda m: _fused_class(type(m), _MIXIN[critic_form(m)[0]])
+                    if not isinstance(m, _Fused) and critic_form(m)[0] in forms else None)
 
 
-def _is_model_critic(m):
-    """The model-learning critic by structure: the attention critic's trunk and, beside ``dense2``, a plain ``Linear(64, k)`` ``dense3`` of
-    ``dense2``'s width (a ``dense3`` of another width is some other network: left alone)."""
-    lin3 = getattr(m, 'dense3', None)
-    return (type(lin3) is nn.Linear and _has_attention_trunk(m) and lin3.in_features == HIDDEN
-            and lin3.out_features == m.dense2.out_features)
-
-
-def _modules(module):
-    return module.modules() if isinstance(module, nn.Module) else ()
+def _unswap(module, mixin):
+    return _reclass(module, lambda m: type(m)._unfused if isinstance(m, mixin) else None)
 
 
 def fuse_attention(module):
@@ -195,49 +235,28 @@ def fuse_attention(module):
     to a subclass of its own class: parameters and ``state_dict`` keys stay, ``isinstance`` checks keep holding, and ``copy.deepcopy``
     keeps the swap (the deep copy a Trainer takes for its target network).  The subclass is made at run time, so a swapped module is
     saved by ``state_dict`` (as the Trainers do), not pickled whole.  Returns the number of critics swapped."""
-    n = 0
-    for m in _modules(module):
-        if not isinstance(m, FusedAttention) and _is_attention_critic(m):
-            m.__class__ = _fused_class(type(m))
-            n += 1
-    return n
+    return _swap(module, ('attention',))
 
 
 def unfuse_attention(module):
     """The reverse of ``fuse_attention``: every swapped critic gets the exact class it had.  Returns the number swapped back."""
-    n = 0
-    for m in _modules(module):
-        if isinstance(m, FusedAttention):
-            m.__class__ = type(m)._unfused
-            n += 1
-    return n
+    return _unswap(module, FusedAttention)
 
 
 def fuse_model_attention(module):
     """``fuse_attention`` for the model-learning variant: every model critic inside ``module`` (``module`` itself included) gets
     ``FusedModelAttention.forward`` by the same swap of ``__class__``.  ``fuse_attention`` leaves such a critic alone and this function
     leaves an attention critic alone, so both may run over one container.  Returns the number of critics swapped."""
-    n = 0
-    for m in _modules(module):
-        if not isinstance(m, (FusedAttention, FusedModelAttention)) and _is_model_critic(m):
-            m.__class__ = _fused_class(type(m), FusedModelAttention)
-            n += 1
-    return n
+    return _swap(module, ('model',))
 
 
 def unfuse_model_attention(module):
     """The reverse of ``fuse_model_attention``.  Returns the number swapped back."""
-    n = 0
-    for m in _modules(module):
-        if isinstance(m, FusedModelAttention):
-            m.__class__ = type(m)._unfused
-            n += 1
-    return n
+    return _unswap(module, FusedModelAttention)
 
 
 def fuse_trainer(trainer):
     """``fuse_attention`` and ``fuse_model_attention`` on ``trainer.critic``, and on ``trainer.target_critic`` while it is still a module
     (``accelerate_trainer(targets=True)`` replaces it by a wrapper on the no-gradient kernel, which has its own attention).  Returns the
     number swapped."""
-    return sum(fuse_attention(getattr(trainer, name, None)) + fuse_model_attention(getattr(trainer, name, None))
-               for name in ('critic', 'target_critic'))
+    return sum(_swap(getattr(trainer, name, None), _MIXIN) for name in ('critic', 'target_critic'))

@@ -24,70 +24,64 @@ two critics it wraps is read off the structure: ``dense2`` is a ``TimeDistribute
 """
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
+from .attention import attend, critic_form, lstm_trunk
 from .policy import FusedActor, TimeDistributed
 from .policy import accelerate_trainer  # noqa: F401  (the one entry point; ``targets=True`` uses the classes below)
 
 
-class CriticNetwork(nn.Module):
-    """Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis -> attention of every step's output against the final
-    hidden state (dot product, softmax over the agents, weighted sum) -> ReLU -> Linear(64, out_dim).
+class _LstmCritic(nn.Module):
+    """The trunk of the three critics: Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis (``attention.lstm_trunk`` runs
+    it).  Subclasses add ``dense2`` (then ``dense3``) after it, so submodules register in the reference's order."""
+
+    def __init__(self, input_dim):
+        super().__init__()
+        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
+        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+
+    def context(self, obs, action, relu):
+        """The attention of every step's output against the final hidden state (dot product, softmax over the agents, weighted sum)."""
+        steps, h_n = lstm_trunk(self, obs, action)                        # [b,N,64], [1,b,64]
+        return attend(steps, h_n[-1], relu)
+
+
+class CriticNetwork(_LstmCritic):
+    """The trunk -> attention -> ReLU -> Linear(64, out_dim).
     ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``[b, out_dim]``."""
 
     def __init__(self, input_dim, out_dim=1):
-        super().__init__()
-        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
-        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+        super().__init__(input_dim)
         self.dense2 = nn.Linear(64, out_dim)
 
     def forward(self, obs, action):
-        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
-        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
-        steps, (h_n, _) = self.lstm(hid, None)                            # [b,N,64], [1,b,64]
-        score = torch.bmm(steps, h_n[-1].unsqueeze(2)).squeeze(2)         # <out_t, h_N>  [b,N]
-        weight = F.softmax(score, dim=1)
-        ctx = torch.bmm(steps.transpose(1, 2), weight.unsqueeze(2)).squeeze(2)
-        return self.dense2(F.relu(ctx))
+        return self.dense2(self.context(obs, action, relu=True))
 
 
-class BiCNetCritic(nn.Module):
-    """Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis -> TimeDistributed(Linear(64, out_dim)) on the LSTM's
-    output itself (no ReLU, no attention): one Q per agent.  Layer names as the reference's (``dense1.module``, ``lstm``,
-    ``dense2.module``).  ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``[b, N, out_dim]``."""
+class BiCNetCritic(_LstmCritic):
+    """The trunk -> TimeDistributed(Linear(64, out_dim)) on the LSTM's output itself (no ReLU, no attention): one Q per agent.  Layer
+    names as the reference's (``dense1.module``, ``lstm``, ``dense2.module``).
+    ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``[b, N, out_dim]``."""
 
     def __init__(self, input_dim, out_dim=1):
-        super().__init__()
-        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
-        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+        super().__init__(input_dim)
         self.dense2 = TimeDistributed(nn.Linear(64, out_dim))
 
     def forward(self, obs, action):
-        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
-        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
-        steps, _ = self.lstm(hid, None)
-        return self.dense2(steps)
+        return self.dense2(lstm_trunk(self, obs, action)[0])
 
 
-class ModelCriticNetwork(nn.Module):
-    """Linear(D + A, 64) -> ReLU -> LSTM(64 -> 64) over the AGENT axis -> the attention of ``CriticNetwork`` -> two heads on the
-    context itself (no ReLU): ``dense2`` = Q, ``dense3`` = the predicted reward.  Layer names as the reference's (``dense1.module``,
-    ``lstm``, ``dense2``, ``dense3``).  ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``(Q [b, out_dim], r [b, out_dim])``."""
+class ModelCriticNetwork(_LstmCritic):
+    """The trunk -> the attention of ``CriticNetwork`` -> two heads on the context itself (no ReLU): ``dense2`` = Q, ``dense3`` = the
+    predicted reward.  Layer names as the reference's (``dense1.module``, ``lstm``, ``dense2``, ``dense3``).
+    ``forward(obs [b,N,D], action [b,N,A] or a list of such)`` -> ``(Q [b, out_dim], r [b, out_dim])``."""
 
     def __init__(self, input_dim, out_dim=1):
-        super().__init__()
-        self.dense1 = TimeDistributed(nn.Linear(input_dim, 64))
-        self.lstm = nn.LSTM(64, 64, num_layers=1, batch_first=True, bidirectional=False)
+        super().__init__(input_dim)
         self.dense2 = nn.Linear(64, out_dim)
         self.dense3 = nn.Linear(64, out_dim)
 
     def forward(self, obs, action):
-        parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
-        hid = F.relu(self.dense1(torch.cat(parts, dim=-1)))
-        steps, (h_n, _) = self.lstm(hid, None)
-        score = torch.bmm(steps, h_n[-1].unsqueeze(2)).squeeze(2)
-        weight = F.softmax(score, dim=1)
-        ctx = torch.bmm(steps.transpose(1, 2), weight.unsqueeze(2)).squeeze(2)
+        ctx = self.context(obs, action, relu=False)
         return self.dense2(ctx), self.dense3(ctx)
 
 
@@ -109,13 +103,9 @@ class FusedCritic(object):
         self._C, self._lib_mod, self.lib = C, _lib, _lib.load()
         self.critic = critic
         self.heads = None if heads is None else tuple(int(h) for h in heads)
-        self.per_step = not isinstance(critic.dense2, nn.Linear) and hasattr(critic.dense2, 'module')
-        lin1, lstm, lin2 = critic.dense1.module, critic.lstm, self._dense2()
-        lin3 = getattr(critic, 'dense3', None)
-        self.model = lin3 is not None
-        ok3 = not self.model or (not self.per_step and type(lin3) is nn.Linear and lin3.in_features == 64 and lin3.out_features == 1)
-        if not (lin1.out_features == 64 and lstm.input_size == 64 and lstm.hidden_size == 64 and lstm.num_layers == 1
-                and not lstm.bidirectional and lstm.batch_first and lin2.in_features == 64 and lin2.out_features == 1 and ok3):
+        form, widths = critic_form(critic)
+        self.per_step, self.model = form == 'steps', form == 'model'
+        if form is None or any(w != 1 for w in widths):
             raise ValueError('FusedCritic serves Linear(D + A, 64) -> LSTM(64 -> 64) -> attention -> Linear(64, 1), the per-step '
                              'form Linear(D + A, 64) -> LSTM(64 -> 64) -> TimeDistributed(Linear(64, 1)) and the model-learning form '
                              'LSTM(64 -> 64) -> attention -> Linear(64, 1) twice (dense2, dense3); other heads (a dense3 that is '

@@ -8,8 +8,8 @@
 
 #include "pworld.h"
 
-// libpworld.so is seven translation units (pworld.hip: environment; pworld_replay.hip: replay ring, wire blocks; pworld_policy.hip: actor,
-// policy rollouts; pworld_policy_generic.hip: the generic policy rollout; pworld_critic.hip; pworld_optim.hip; pworld_lstm.hip).  The thread-local error text lives in pworld.hip; all reach it through this hook.
+// libpworld.so is eight translation units (pworld.hip: environment; pworld_replay.hip: replay ring, wire blocks; pworld_policy.hip: actor,
+// policy rollouts; pworld_policy_generic.hip: the generic policy rollout; pworld_critic.hip; pworld_optim.hip; pworld_lstm.hip; pworld_attention.hip).  The thread-local error text lives in pworld.hip; all reach it through this hook.
 extern "C" __attribute__((visibility("hidden"))) void pw_internal_set_error(const char *msg);
 // pworld_policy_generic.hip: the launcher of pw_policy_rollout_generic_kernel; pw_policy_rollout (pworld_policy.hip) has checked the
 // handle, the weights, io and num_steps and hands everything else over.

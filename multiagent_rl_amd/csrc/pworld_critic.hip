@@ -10,43 +10,60 @@
 
 namespace {
 
-template <int KO, int KA>
-int critic_launch(const CriticArgs &C, hipStream_t stream)
+// One trait per form: the argument block, the kernel of <KO, KA>, its LDS bytes and the rows per workgroup (R).
+template <class Args> using CriticKernel = void (*)(const Args);
+
+struct AttentionForm {  // pw_critic_forward
+    using Args = CriticArgs;
+    template <int KO, int KA> static CriticKernel<Args> kernel() { return pw_critic_forward_kernel<KO, KA, false>; }
+    static size_t lds(const CriticArgs &C) { return critic_lds(C.N, C.R).bytes; }
+    static int rows(int N) { return N <= 32 ? 16 : 8; }  // all N step outputs of a workgroup's rows stay in LDS for the attention pass
+};
+
+struct StepsForm {  // pw_critic_forward_steps
+    using Args = CriticArgs;
+    template <int KO, int KA> static CriticKernel<Args> kernel() { return pw_critic_forward_kernel<KO, KA, true>; }
+    static size_t lds(const CriticArgs &C) { return critic_steps_lds(C.N, C.R).bytes; }
+    static int rows(int) { return 16; }  // only h_{t-1} and h_t are live: the two-slot ring serves every N with full tiles
+};
+
+struct ModelForm : AttentionForm {  // pw_critic_forward_model: the attention form's LDS layout and R rule
+    using Args = CriticModelArgs;
+    template <int KO, int KA> static CriticKernel<Args> kernel() { return pw_critic_forward_kernel<KO, KA>; }
+};
+
+// The one launcher.  optin_mask is a static of the instantiation, so there is one per kernel: a mask two kernels shared would
+// skip the opt-in of the second, whose launch then fails wherever its LDS exceeds 64 KB.
+template <class Form, int KO, int KA>
+int critic_launch(const typename Form::Args &C, hipStream_t stream)
 {
     static unsigned long long optin_mask = 0;
-    const auto kernel = pw_critic_forward_kernel<KO, KA, false>;
-    const size_t lds = critic_lds(C.N, C.R).bytes;
+    const auto kernel = Form::template kernel<KO, KA>();
     PW_LDS_OPTIN(&optin_mask, kernel);
     const long groups = (C.b + C.R - 1) / C.R;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), Form::lds(C), stream, C);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }
 
-template <int KO, int KA>
-int critic_steps_launch(const CriticArgs &C, hipStream_t stream)
+template <class Form, int KO>
+int critic_ka(const typename Form::Args &C, hipStream_t s)
 {
-    static unsigned long long optin_mask = 0;
-    const auto kernel = pw_critic_forward_kernel<KO, KA, true>;
-    const size_t lds = critic_steps_lds(C.N, C.R).bytes;
-    PW_LDS_OPTIN(&optin_mask, kernel);
-    const long groups = (C.b + C.R - 1) / C.R;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
+    return (C.A + 3) / 4 <= 2 ? critic_launch<Form, KO, 2>(C, s) : critic_launch<Form, KO, 4>(C, s);
 }
 
-template <int KO, int KA>
-int critic_model_launch(const CriticModelArgs &C, hipStream_t stream)
+// The one ladder: R by the form's rule, then the instantiation by the k steps of dense1 (four k each): observation part
+// (so <= 26), action part (<= 4).
+template <class Form>
+int critic_go(typename Form::Args &C, void *stream)
 {
-    static unsigned long long optin_mask = 0;
-    void (*const kernel)(const CriticModelArgs) = pw_critic_forward_kernel<KO, KA>;
-    const size_t lds = critic_lds(C.N, C.R).bytes;
-    PW_LDS_OPTIN(&optin_mask, kernel);
-    const long groups = (C.b + C.R - 1) / C.R;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)groups), dim3(512), lds, stream, C);
-    PW_HIP_CHECK(hipGetLastError());
-    return PW_OK;
+    C.R = Form::rows(C.N);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int so = (C.D + 3) / 4;
+    if (so <= 4) return critic_ka<Form, 4>(C, s);
+    if (so <= 8) return critic_ka<Form, 8>(C, s);
+    if (so <= 16) return critic_ka<Form, 16>(C, s);
+    return critic_ka<Form, 26>(C, s);
 }
 
 // the arguments all entry points share; fills everything of C but R
@@ -84,15 +101,7 @@ int pw_critic_forward(const float *obs, const int32_t *act_idx, const float *act
     if (int rc = critic_args(obs, act_idx, act_vec, n_act0, n_act1, w1, b1, w_ih, w_hh, b_ih, b_hh, w2, b2, b, N, obs_dim, rew, done,
                              gamma, q, y, C))
         return rc;
-    C.R = N <= 32 ? 16 : 8;  // all N step outputs of a workgroup's rows stay in LDS for the attention pass
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;  // k steps of dense1: observation part (<= 26), action part (<= 4)
-#define PW_CRITIC_GO(KO) return sa <= 2 ? critic_launch<KO, 2>(C, s) : critic_launch<KO, 4>(C, s)
-    if (so <= 4) PW_CRITIC_GO(4);
-    if (so <= 8) PW_CRITIC_GO(8);
-    if (so <= 16) PW_CRITIC_GO(16);
-    PW_CRITIC_GO(26);
-#undef PW_CRITIC_GO
+    return critic_go<AttentionForm>(C, stream);
 }
 
 int pw_critic_forward_steps(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
@@ -104,15 +113,7 @@ int pw_critic_forward_steps(const float *obs, const int32_t *act_idx, const floa
     if (int rc = critic_args(obs, act_idx, act_vec, n_act0, n_act1, w1, b1, w_ih, w_hh, b_ih, b_hh, w2, b2, b, N, obs_dim, rew, done,
                              gamma, q, y, C))
         return rc;
-    C.R = 16;  // only h_{t-1} and h_t are live: the two-slot ring serves every N with full tiles
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;
-#define PW_CRITIC_GO(KO) return sa <= 2 ? critic_steps_launch<KO, 2>(C, s) : critic_steps_launch<KO, 4>(C, s)
-    if (so <= 4) PW_CRITIC_GO(4);
-    if (so <= 8) PW_CRITIC_GO(8);
-    if (so <= 16) PW_CRITIC_GO(16);
-    PW_CRITIC_GO(26);
-#undef PW_CRITIC_GO
+    return critic_go<StepsForm>(C, stream);
 }
 
 int pw_critic_forward_model(const float *obs, const int32_t *act_idx, const float *act_vec, int32_t n_act0, int32_t n_act1,
@@ -127,15 +128,7 @@ int pw_critic_forward_model(const float *obs, const int32_t *act_idx, const floa
         return rc;
     if (r_pred && (!w3 || !b3)) return fail(PW_EINVAL, "the reward prediction needs w3 and b3");
     C.w3 = w3; C.b3 = b3; C.r_pred = r_pred;
-    C.R = N <= 32 ? 16 : 8;  // pw_critic_forward's rule: the same LDS layout
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int so = (obs_dim + 3) / 4, sa = (C.A + 3) / 4;
-#define PW_CRITIC_GO(KO) return sa <= 2 ? critic_model_launch<KO, 2>(C, s) : critic_model_launch<KO, 4>(C, s)
-    if (so <= 4) PW_CRITIC_GO(4);
-    if (so <= 8) PW_CRITIC_GO(8);
-    if (so <= 16) PW_CRITIC_GO(16);
-    PW_CRITIC_GO(26);
-#undef PW_CRITIC_GO
+    return critic_go<ModelForm>(C, stream);
 }
 
 }  // extern "C"

@@ -200,6 +200,35 @@ def test_td_target_is_the_expression_on_the_launchs_own_q(N, D, heads, b):
     assert torch.equal(fc.td_target(obs, idx, r, d, GAMMA), y)
 
 
+def test_every_instantiation_opts_in_to_its_own_lds():
+    """The host side launches all three forms through one launcher template; the opt-in to more than 64 KiB of LDS is remembered per
+    kernel.  N = 32 needs 146.5 KiB, so in ONE process every instantiation of the attention form (KO in {4, 8, 16, 26} x KA in {2, 4})
+    and then every one of the model form is launched at b = 17 (a full workgroup and one row): a kernel whose opt-in another
+    kernel's had masked would fail its launch.  q (and r_pred) against float64 as everywhere in this file."""
+    from multiagent_rl_amd.critic import CriticNetwork, FusedCritic, ModelCriticNetwork
+    from tests import model_ref as mr
+    N, b = 32, 17
+    rng = np.random.RandomState(32)
+    for cls in (CriticNetwork, ModelCriticNetwork):
+        for D in (4, 20, 40, 100):
+            for A in (5, 15):
+                torch.manual_seed(D + A)
+                net = cls(D + A, 1).eval().cuda()
+                obs = (rng.randn(b, N, D) * 2).astype(np.float32)
+                idx = rng.randint(0, A, (b, N, 1)).astype(np.int32)
+                act = cr.one_hot(idx, (A,))
+                got = FusedCritic(net)(torch.from_numpy(obs).cuda(), torch.from_numpy(idx[..., 0]).cuda())
+                if cls is ModelCriticNetwork:
+                    assert got[0].shape == (b, 1) and got[1].shape == (b, 1)
+                    got, want = np.stack([g[:, 0].cpu().numpy() for g in got]), np.stack(mr.critic_f64(net, obs, act))
+                else:
+                    assert got.shape == (b, 1)
+                    got, want = got[:, 0].cpu().numpy(), cr.forward_f64(net, obs, act)
+                worst = float(np.abs(got - want).max())
+                _report('%-52s |d| %.2e' % ('%s N=32 D=%d A=%d b=17' % (cls.__name__, D, A), worst))
+                assert worst <= ATOL, (cls.__name__, D, A, worst)
+
+
 def _soft_update(target, source, tau):
     for tp, sp in zip(target.parameters(), source.parameters()):        # ddpg_gumbel_fix.py:37-48
         tp.data.copy_(tp.data * (1.0 - tau) + sp.data * tau)
