@@ -23,16 +23,22 @@ namespace {
 //   wave OB       8 envs, one step behind: observation rows, stored as one contiguous block per step
 //                 (stream_write_obs_block), and the pre-reset rows at episode ends; done / terminal stores; the collision
 //                 tests (counts handed to OA through LDS one step later, masks stored) -- the two output waves issue
-//                 about the same number of vector instructions per step (profiles/r7_quad_loop_census.txt).
+//                 about the same number of vector instructions per step (profiles/r7_quad_loop_census.txt); and the
+//                 physics waves' action force: OB fetches the action indices (LDS-direct loads, four iterations ahead),
+//                 looks the force up in a six-entry table and leaves it in a two-slot LDS ring TWO steps ahead of the
+//                 physics waves, which read it with one LDS load at the top of a step (steps 0 and 1 of a launch they
+//                 fetch and decode themselves, before the loop).  No meeting of its own: the entry of step t + 2 is
+//                 written between barriers t and t + 1 and read behind barrier t + 1; its slot's previous entry was
+//                 consumed before barrier t (profiles/r8_quad_actions.txt, r8_quad_loop_census.txt).
 // One s_barrier per step.  The ring slot sequence is WORKGROUP-uniform: in a step in which ANY of the 8 envs resets,
 // every env publishes a pre-reset and a post-reset slot (identical for the envs that do not reset), so no wave needs
 // another env's slot index; each wave follows all 8 episode clocks itself.  Envs out of step with each other can make
 // that happen in consecutive steps, so the ring has 4 slots: the two the output waves are reading (one step behind)
 // and the two the physics waves may be writing.
 // Per-step overheads are kept off the physics waves' instruction stream: the episode clocks are offsets behind ONE scalar
-// compare per step (the vector work runs in reset steps only), the action force is a six-entry table lookup, the action
-// indices arrive four steps ahead by LDS-direct loads (pw_common.hpp act_fetch_issue), the pair operands of the next step
-// are read back before the barrier.  Measured state (profiles/r2_action_prefetch.txt, r2_c2_b4096_quad_summary.json):
+// compare per step (the vector work runs in reset steps only), the action force arrives ready-made from wave OB (the
+// physics waves' step loop holds no vector memory operation, no vmcnt wait and no M0 statement), the pair operands of the
+// next step are read back before the barrier.  Measured state (profiles/r2_action_prefetch.txt, r2_c2_b4096_quad_summary.json):
 // 0.62 us per step at B = 4096, the three kinds of waves within 10 % of each other, 0.53 us for a lone workgroup.
 // Arithmetic and results are identical to the other simple_spread kernels (same bit-exact tests, `quad` path).
 // ------------------------------------------------------------------------------------------
@@ -43,17 +49,28 @@ __device__ __forceinline__ void quad_pair_of(const int q, int &i, int &j)
     j = q - (i == 0 ? 0 : i == 1 ? 5 : i == 2 ? 9 : i == 3 ? 12 : 14) + i + 1;
 }
 
-// The physics waves' action fetch (pw_common.hpp act_fetch_issue, which the duo / tag kernels keep): the same LDS-direct load in
-// its scalar-base form -- `row` is the workgroup-uniform pointer to the step's action plane, a running pointer of the caller's,
-// `lane_off` the lane's constant byte offset in it -- so a step pays one scalar add for the address instead of a 64-bit product
-// and a vector add.  The wait for the slot's previous content is the compiler's own: `slot_read`, the value the caller has just read
-// from that slot, is an operand.  M0 is still saved and restored inside the statement: the compiler takes "m0" in a clobber list
-// only with the remark that a reserved register "may not be preserved across the asm statement".
+// Wave OB's action fetch (pw_common.hpp act_fetch_issue, which the duo / tag kernels keep in their physics waves): the same
+// LDS-direct load in its scalar-base form -- `row` is the workgroup-uniform pointer to the step's action plane, a running pointer
+// of the caller's, `lane_off` the lane's constant byte offset in it -- so a step pays one scalar add for the address instead of a
+// 64-bit product and a vector add.  The wait for the slot's previous content is the compiler's own: `slot_read`, the value the
+// caller has just read from that slot, is an operand.  M0 is still saved and restored inside the statement: the compiler takes
+// "m0" in a clobber list only with the remark that a reserved register "may not be preserved across the asm statement".
 __device__ __forceinline__ void quad_act_fetch(const int32_t *row, const uint32_t lane_off, const uint32_t lds_slot, const uint32_t slot_read)
 {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(lane_off), "s"(row), "s"(lds_slot), "v"(slot_read) : "memory");
+}
+
+// U2 + U4: the action force of index `ai`, one of five constants, with the step's own expressions (so the bits are the step's);
+// any index outside 0..4 gives no force.  {u_x + 0, u_y + 0}: the accumulators' starting values.
+__device__ __forceinline__ float2 quad_action_force(const int ai, const float sens, const float fscale)
+{
+    float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
+    float uy = 0.0f + ((ai == 3 ? 1.0f : 0.0f) - (ai == 4 ? 1.0f : 0.0f));
+    ux *= sens; uy *= sens;
+    if (fscale != 1.0f) { ux = fscale * ux; uy = fscale * uy; }
+    return make_float2(ux + 0.0f, uy + 0.0f);
 }
 
 // The pair force of a physics lane: pw_common.hpp collision_force_pair<true, K1> behind the near test, with the two tests folded
@@ -127,7 +144,7 @@ __device__ __forceinline__ void quad_coll_tests(const float2 mine, const float2 
 #define PW_QUAD_BARRIER(t) duo_barrier()   // one workgroup meeting per step
 #endif
 #ifndef PW_QUAD_ACT_AHEAD
-#define PW_QUAD_ACT_AHEAD 4   // steps the physics waves' action indices are fetched ahead (a power of two; LDS ring slots per wave)
+#define PW_QUAD_ACT_AHEAD 4   // iterations wave OB fetches the action indices ahead of their use (a power of two; slots of its LDS ring)
 #endif
 #ifndef PW_QUAD_PAD_P   // timing experiments only (tools/experiments/pw_experiments.hpp): padding of a wave's step loop
 #define PW_QUAD_PAD_P()
@@ -137,15 +154,16 @@ __device__ __forceinline__ void quad_coll_tests(const float2 mine, const float2 
 #endif
 constexpr int kQuadActAhead = PW_QUAD_ACT_AHEAD;
 constexpr int kQuadN = 6, kQuadL = 6, kQuadEPP = 4, kQuadEPW = 8;   // agents, landmarks, envs per physics wave / per workgroup
-struct SpreadQuadLds { float4 *s_ring; float2 *s_ftab, *s_lmB, *s_utab; float *s_min, *s_rew; int32_t *s_act; uint32_t bytes; };
+struct SpreadQuadLds { float4 *s_ring; float2 *s_ftab, *s_lmB, *s_utab, *s_u; float *s_min, *s_rew; int32_t *s_act; uint32_t bytes; };
 __host__ __device__ inline SpreadQuadLds spread_quad_lds(unsigned char *raw = nullptr)
 {
     LdsCursor c{reinterpret_cast<float *>(raw)}; SpreadQuadLds o;
     o.s_ring = c.take<float4>(4 * kWave);                        // [4][64] {px, py, vx, vy}, index e_local * 6 + a
     o.s_ftab = c.take<float2>(2 * kQuadEPP * kQuadN * kQuadN);   // [2 P waves][24 agents][6 partners]
     o.s_min = c.take<float>(kWave); o.s_rew = c.take<float>(kWave);   // [64] each: OB -> OA, a lane's collision count of even / odd steps (int32)
-    o.s_lmB = c.take<float2>(kQuadEPW * kQuadL); o.s_act = c.take<int32_t>(2 * kQuadActAhead * kWave);   // [8 * 6] OB; [2 P waves][4 steps][64] action indices
-    o.s_utab = c.take<float2>(2 * 8);                            // [2 P waves][8] action force per index
+    o.s_lmB = c.take<float2>(kQuadEPW * kQuadL); o.s_act = c.take<int32_t>(2 * kQuadActAhead * kWave);   // [8 * 6] OB; first half: [4 steps][64] action indices (OB)
+    o.s_u = reinterpret_cast<float2 *>(o.s_act + kQuadActAhead * kWave);   // alias, inside s_act's second half: [2 steps][48] action force, OB -> P (768 of its 1024 bytes)
+    o.s_utab = c.take<float2>(2 * 8);                            // [8] action force per index (OB; the second eight are unused)
     o.bytes = 4 * c.at; return o;
 }
 template <bool UNIT_MASS, bool COLL = false, bool K1 = false>
@@ -231,37 +249,19 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         int ep_off = A.ep_step[env];  // clock before step t = t + ep_off
         uint32_t ep_count = A.ep_count[env];
         Y.s_ring[me] = make_float4(px, py, vx, vy);
-        // U2 + U4 as a table: the action force of an index is one of five constants, computed here once with the step's
-        // own expressions (so the bits are the step's), entry 5 = any other index (no force); a step reads ONE entry
-        float2 *utab = Y.s_utab + wave * 8;
-        if (lane < 6) {
-            const int ai = lane;
-            float ux = 0.0f + ((ai == 1 ? 1.0f : 0.0f) - (ai == 2 ? 1.0f : 0.0f));
-            float uy = 0.0f + ((ai == 3 ? 1.0f : 0.0f) - (ai == 4 ? 1.0f : 0.0f));
-            ux *= A.sens; uy *= A.sens;
-            if (A.fscale != 1.0f) { ux = A.fscale * ux; uy = A.fscale * uy; }
-            utab[lane] = make_float2(ux + 0.0f, uy + 0.0f);
+        // The action force {u_x + 0, u_y + 0} of step t arrives from wave OB through Y.s_u[t & 1][me], written two steps ahead (see
+        // there: who waits for what); the step loop holds no vector memory operation at all.  Steps 0 and 1 have no iteration of OB's
+        // in front of them: this wave fetches and decodes those two itself, here, into the same two slots (its own lanes' entries;
+        // a launch of one step reads step 0's index twice).
+        float2 *u_w = Y.s_u + me;
+        {
+            const int32_t a0 = A.act[g], a1 = A.act[(T > 1 ? BN : (size_t)0) + g];
+            u_w[0] = quad_action_force(a0, A.sens, A.fscale);
+            u_w[kQuadEPW * N] = quad_action_force(a1, A.sens, A.fscale);
         }
-        wave_lds_sync();
+        int u_at = 0;                 // the entry of the coming step: 0 <-> 48, toggled (a lane's constant offset, nothing selected)
         const float k = A.contact_margin, cf = A.contact_force, dt = A.dt, damp = A.damp, mass = A.mass;
         const uint32_t near_lo = __float_as_uint(A.near_thr2), near_span = 0x7F800000u - near_lo;
-        // Action indices: fetched four steps ahead by LDS-direct loads (pw_common.hpp, act_fetch_issue: under a full chip
-        // a load issued one step ahead cost 385 cycles of every step)
-        const unsigned char *act_row = reinterpret_cast<const unsigned char *>(A.act);   // the action plane of the next step to fetch: workgroup-uniform, a running pointer
-        const size_t act_stride = BN * sizeof(int32_t);
-        const uint32_t act_off = g * (uint32_t)sizeof(int32_t);
-        int32_t *act_ring = Y.s_act + wave * (kQuadActAhead * kWave);
-        const uint32_t act_lds = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(act_ring));
-        // indices of step t -> slot t & 3; called for t = 0, 1, 2, ... in turn.  The tail re-fetches the last step: the pointer's
-        // stride turns 0 there (also from the start, if T is below the fetch depth)
-        auto fetch_act = [&](int t, uint32_t slot_read) {
-            quad_act_fetch(reinterpret_cast<const int32_t *>(act_row), act_off, act_lds + (uint32_t)(t & (kQuadActAhead - 1)) * (kWave * 4), slot_read);
-            act_row += t + 1 < T ? act_stride : (size_t)0;
-        };
-        // every load the compiler counts is consumed before the first uncounted one is issued: a counted wait inside the
-        // loop (for a value first used there) would be short by the fetches in flight, i.e. drain them
-        asm volatile("" :: "v"(ep_off), "v"(ep_count), "v"(offs_all), "v"(px), "v"(py), "v"(vx), "v"(vy), "s"(t_reset));
-        for (int t0 = 0; t0 < kQuadActAhead; ++t0) fetch_act(t0, 0u);
         // the pair lanes' operands of the coming step are fetched right after the publish, before the barrier (this
         // wave only reads its own envs' entries, and a wave's LDS operations execute in issue order): the read's latency
         // hides behind the barrier
@@ -270,11 +270,8 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         PW_STAMP_DECL;
         for (int t = 0; t < T; ++t) {
             PW_STAMP_START;
-            asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kQuadActAhead - 1) : "memory");  // step t's indices are in LDS (the later fetches stay in flight)
-            PW_STAMP(3);
-            const uint32_t ai = (uint32_t)act_ring[(t & (kQuadActAhead - 1)) * kWave + lane];
-            fetch_act(t + kQuadActAhead, ai);  // into the slot just read (its wait for the read above is the one the table lookup needs anyway)
-            const float2 u0 = utab[ai < 5u ? ai : 5u];  // {u_x + 0, u_y + 0}: the accumulators' starting values
+            const float2 u0 = u_w[u_at];                // consumed behind the pair phase
+            u_at = kQuadEPW * N - u_at;
             const bool two_slots = t == t_reset;        // workgroup-uniform: some env of the workgroup resets in this step
             // ---- pair phase: every unordered pair of the wave's envs at once
             float Fx, Fy;
@@ -319,7 +316,6 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             PW_QUAD_BARRIER(t);
             PW_STAMP(2);
         }
-        act_fetch_drain();  // the tail's fetches have landed before the wave ends
 #ifdef PW_STAMPS
         if (blockIdx.x == 0 && wave == 0 && lane == 0)
             for (int i_ = 0; i_ < 4; ++i_) g_pw_stamps[i_] = st_acc[i_];
@@ -514,8 +510,45 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             lm_u[u] = *reinterpret_cast<const float4 *>(Y.s_lmB + (row_u[u] / N) * L + (cgrp > 0 ? 2 * cgrp - 2 : 0));
     };
     Y.s_lmB[me] = make_float2(olx, oly);
+    // The physics waves' action force is this wave's work too (it has the issue slots, profiles/r6_quad_issue_budget.txt; nothing of it
+    // depends on the state): lane l < 48 is ring index `me` = l, the workgroup's 48 indices of a step are contiguous in A.act.  The
+    // indices arrive by LDS-direct loads (pw_common.hpp act_fetch_issue: registers rotated through a loop get copied at the back edge, and
+    // a copy of a pending load waits for it), step s into slot s & 3 of Y.s_act's first half, fetched kQuadActAhead iterations before
+    // they are used; iteration t looks step t + 2's force up in the six-entry table below (entry 5: any index outside 0..4) and writes
+    // it to Y.s_u[t & 1][me].  Who waits for what: the write lies between barriers t and t + 1 -- this wave's barrier waits for its LDS
+    // operations -- and a physics lane reads the entry at the top of step t + 2, behind barrier t + 1; it has consumed slot t & 1's
+    // previous entry (step t's) before it arrives at barrier t, and this wave writes the slot again only behind that barrier.  No
+    // meeting of its own.  Steps 0 and 1 are the physics waves' own (see there).  The compiler does not count these loads, but it counts
+    // this wave's stores into the same counter, so the wait is written out with the number of vector memory operations a step issues
+    // at least: kStepStores stores (a reset step issues more: the wait only gets stricter) and one fetch.  The fetch of step t + 2 was
+    // issued kQuadActAhead iterations ago at this place, so kQuadActAhead * kStepStores stores and kQuadActAhead - 1 fetches lie behind
+    // it; the fetches issued before the loop, which have fewer behind them, are waited for before the loop (one load's latency at the
+    // start of a launch, in the shadow of the physics waves' own start-of-launch loads and first step).  The tail re-fetches the last step: the pointer's stride turns 0 there.
+    constexpr int kStepStores = 5 + (COLL ? 1 : 0);   // done, terminal, three observation chunks, the collision mask
+    constexpr int kActBehind = kQuadActAhead * kStepStores + kQuadActAhead - 1;
+    constexpr int kActWait = kActBehind < 63 ? kActBehind : 63;   // vmcnt is a six-bit field (a smaller count only waits for more)
+    const unsigned char *act_row = reinterpret_cast<const unsigned char *>(A.act) + (size_t)(T > 2 ? 2 : T > 0 ? T - 1 : 0) * (BN * sizeof(int32_t));
+    const size_t act_stride = BN * sizeof(int32_t);
+    const uint32_t act_off = g * (uint32_t)sizeof(int32_t);
+    const unsigned char *act_ring = reinterpret_cast<const unsigned char *>(Y.s_act + lane);
+    uint32_t act_lds = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(Y.s_act));
+    asm volatile("" : "+s"(act_lds));   // (the address as a value of the loop's: otherwise the pointer's null test is repeated in every step)
+    constexpr uint32_t kSlotBytes = kWave * sizeof(int32_t), kRingMask = kQuadActAhead * kSlotBytes - 1;
+    auto fetch_act = [&](int s, uint32_t slot_at, uint32_t slot_read) {   // indices of step s -> slot s & 3, at byte slot_at of the ring; called for s = 2, 3, 4, ... in turn
+        quad_act_fetch(reinterpret_cast<const int32_t *>(act_row), act_off, act_lds + slot_at, slot_read);
+        act_row += s + 1 < T ? act_stride : (size_t)0;
+    };
+    // every load the compiler counts is consumed before the first uncounted one is issued: a counted wait inside the loop (for a
+    // value first used there, as ep_count in a reset step) would be short by the fetches in flight, i.e. drain them
+    asm volatile("" :: "v"(ep_off), "v"(ep_count), "v"(offs_all), "v"(olx), "v"(oly), "s"(t_reset));
+    for (int s0 = 2; s0 < 2 + kQuadActAhead; ++s0) fetch_act(s0, ((uint32_t)s0 * kSlotBytes) & kRingMask, 0u);
+    if (lane < 6) Y.s_utab[lane] = quad_action_force(lane, A.sens, A.fscale);
+    float2 *u_w = Y.s_u + me;
+    int u_at = 0;             // the entry iteration t writes: 0 <-> 48, toggled
+    uint32_t act_slot = (2 * kSlotBytes) & kRingMask;   // byte offset of slot (t + 2) & 3
     wave_lds_sync();
     load_landmarks();
+    act_fetch_drain();
     // workgroup-uniform plane pointers of step t (the compiler keeps them in scalar registers: every term is uniform)
     unsigned char *obs_t = reinterpret_cast<unsigned char *>(A.obs + ((size_t)env0 * N) * D);
     uint8_t *done_t = A.done, *term_t = A.terminal;
@@ -537,6 +570,8 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         nt_store(done_t + g, (uint8_t)0);
         PW_QUAD_BARRIER(t);
         PW_STAMP(0);
+        asm volatile("s_waitcnt vmcnt(%0)" :: "n"(kActWait) : "memory");  // step t + 2's indices are in LDS (the later fetches and this wave's recent stores stay in flight)
+        const uint32_t ai = *reinterpret_cast<const uint32_t *>(act_ring + act_slot);
         int nxt = (cur + 1) & 3;
         float2 cmine, cq6[N];
         {
@@ -545,6 +580,9 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
 #pragma unroll
             for (int j = 0; j < N; ++j) cq6[j] = *reinterpret_cast<const float2 *>(pre + j);
         }
+        fetch_act(t + 2 + kQuadActAhead, act_slot, ai);  // into the slot just read (its wait for the read above is the one the table lookup needs anyway)
+        act_slot = (act_slot + kSlotBytes) & kRingMask;
+        const float2 u2 = Y.s_utab[ai < 5u ? ai : 5u];
         nt_store(term_t + env, (uint8_t)(t >= t_term ? 1 : 0));
         if (t == t_reset) {  // workgroup-uniform, once per episode
             const bool rst = t >= t_term;
@@ -576,6 +614,8 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             quad_coll_tests<COLL>(cmine, cq6, A.coll_thr2, cnt, cmask);
             cnt_w[cnt_at] = cnt;   // complete before this wave arrives at the next barrier (its s_waitcnt)
             cnt_at = cnt_span - cnt_at;
+            u_w[u_at] = u2;        // step t + 2's action force, likewise complete before the next barrier
+            u_at = kQuadEPW * N - u_at;
             if (COLL) {
                 nt_store(coll_t + g, (uint64_t)cmask);   // is_collision bits of the state step t produced (pre-reset)
                 coll_t += BN;
@@ -601,6 +641,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
 #endif
     A.lm_x[(size_t)env * L + a] = olx;
     A.lm_y[(size_t)env * L + a] = oly;
+    act_fetch_drain();  // the tail's fetches have landed before the wave ends
 }
 
 }  // namespace

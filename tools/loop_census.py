@@ -14,7 +14,8 @@ Two counts per loop:
           over a region only when no lane wants it; the path a step takes when some lane does) -- scalar branches (an episode reset,
           a cold block behind a wave-uniform test) take whichever side is shorter
 Loops that hold an s_barrier are a workgroup's step loops; `role` names the quad kernel's by what only that wave does: the physics
-waves load action indices into LDS, wave OA shuffles (ds_bpermute), wave OB stores 16-byte chunks, an idle physics wave only meets."""
+waves publish the state ring (ds_write_b128) and store nothing to global memory, wave OA shuffles (ds_bpermute), wave OB stores
+16-byte chunks, an idle physics wave only meets."""
 import heapq
 import os
 import re
@@ -162,8 +163,8 @@ def loops(ins):
         cc, cops, ctext = _count(ins, blocks, path[::-1])
         role = ''
         if 's_barrier' in bops:
-            role = ('P' if any(o.startswith('global_load_lds') for o in bops) else 'OA' if 'ds_bpermute_b32' in bops else
-                    'OB' if 'global_store_dwordx4' in bops else 'idle')
+            role = ('P' if 'ds_write_b128' in bops and not any(o.startswith('global_store') for o in bops) else
+                    'OA' if 'ds_bpermute_b32' in bops else 'OB' if 'global_store_dwordx4' in bops else 'idle')
         res.append(dict(header=ins[blocks[h][0]][0], latch=ins[blocks[max(latches)][1]][0], body=bc, common=cc, body_ops=bops,
                         common_ops=cops, common_text=ctext, role=role))
     return res
