@@ -152,13 +152,86 @@ __device__ __forceinline__ void quad_coll_tests(const float2 mine, const float2 
 #ifndef PW_QUAD_PAD_OB
 #define PW_QUAD_PAD_OB()
 #endif
+#ifndef PW_QUAD_RESET_XY   // timing experiments only (PW_EXP_NO_RESET_DRAWS): a wave kind's reset draws; kind 1 physics, 2 OA, 4 OB
+#define PW_QUAD_RESET_XY(kind, seed, env_id, episode, entity, x, y) pw_reset_xy(seed, env_id, episode, entity, -1.0f, 1.0f, x, y)
+#endif
+#ifndef PW_QUAD_DRAW_ROUNDS
+#define PW_QUAD_DRAW_ROUNDS 10  // Philox rounds (of each of its two draws) wave OB runs per iteration while it draws ahead: 1, 2, 5 or 10 (measured: 10)
+#endif
+#ifndef PW_QUAD_DRAW_DELAY
+#define PW_QUAD_DRAW_DELAY 1    // iterations behind a reset step at which the first slice runs (>= 1: the reset iteration itself is OB's longest)
+#endif
 constexpr int kQuadActAhead = PW_QUAD_ACT_AHEAD;
 constexpr int kQuadN = 6, kQuadL = 6, kQuadEPP = 4, kQuadEPW = 8;   // agents, landmarks, envs per physics wave / per workgroup
-struct SpreadQuadLds { float4 *s_ring; float2 *s_ftab, *s_lmB, *s_utab, *s_u; float *s_min, *s_rew; int32_t *s_act; uint32_t bytes; };
+// ------------------------------------------------------------------------------------------
+// Reset draws ahead (round 9, profiles/r9_quad_reset_bound.txt, r9_quad_reset_ahead.txt).  A reset position is
+// pw_reset_xy(seed, env_id, ep_count + 1, entity): every operand is known when the CURRENT episode begins.  With a fixed episode length all
+// envs of a workgroup (of the whole batch) reset in the same step, and in that step each physics lane ran Philox4x32-10 (twenty 64-bit
+// products, quarter rate) on the step's critical path, and OA and OB each ran it again for the same 48 landmarks one iteration later.
+// Now wave OB, lane (env e, index a), draws BOTH entities a (the agent) and N + a (the landmark it owns) of episode ep_count + 1 ahead, in
+// kQuadDrawSlices slices of kQuadDrawRounds Philox rounds of each draw, one slice per iteration, the state in registers (the two chains
+// are independent and interleave); the last slice converts and publishes: the agent's position to s_drawA[me], where physics lane `me`
+// finds it with one ds_read_b64, the landmark's to s_drawL[me] for OA lane `me`, and OB keeps its own copy in registers.  Same Philox, same
+// counters and keys, same float conversion (quad_draw_xy is pw_reset_xy's, tests/quad_draw_rule_dump.hip compares them on the host): the
+// bits do not change, only where and when they are made.
+// Slice size and start are a MEASURED choice (profiles/r9_quad_reset_ahead.txt, us per step at B = 4096, parent 0.522): 1 round per
+// iteration 0.505, 2 rounds 0.495, 5 rounds 0.494, all 10 in ONE iteration 0.488; that one slice 2, 3, 6 iterations behind the reset step
+// instead of 1: 0.497, 0.495, 0.496; 5 rounds starting 3 behind: 0.488.  Spreading the quarter-rate products thin does not pay: every
+// iteration with a slice in it is a longer iteration of OB's, and one long iteration right behind the reset step -- where the physics
+// waves have just waited for OB's longest iteration anyway -- costs least.  So the default is one slice (kQuadDrawSlices = 1, depth 2).
+// The pipeline is WORKGROUP-uniform and every wave derives its state from the clocks it follows anyway: it starts in OB's iteration
+// t_start = 0 of a launch, or t_start = t + 1 behind a reset step t, and only if all clocks of the workgroup are equal (then every env
+// resets in step t_reset) and that reset is at least kQuadDrawDepth steps away (quad_draw_engages); then t_fast = t_reset, else no slice
+// is issued and t_fast = -1.  A reset step with t == t_fast is the fast one: the physics lanes and OA read their entry, OB takes its
+// registers, t_reset advances by the episode length with one scalar add (no lane reads), and the pipeline restarts.  Every other reset
+// step -- clocks apart, episodes shorter than the depth, a launch that begins closer to a reset than the depth, T = 1 -- runs the code
+// that was there before.
+// Who waits for what (no meeting of its own): the slices run in OB's iterations t_start .. t_start + kQuadDrawSlices - 1, the entries are
+// written in the last of them, i.e. between barriers t_start + kQuadDrawSlices - 1 and t_start + kQuadDrawSlices (OB's barrier waits for
+// its LDS operations).  t_fast >= t_start + kQuadDrawDepth = t_start + kQuadDrawSlices + 1: a physics lane reads in step t_fast, behind
+// barrier t_fast - 1 >= t_start + kQuadDrawSlices; OA reads in its iteration t_fast, behind barrier t_fast.  The entries are written
+// again by the NEXT pipeline only (with equal clocks no other reset lies in between), which starts at t_fast + 1 and writes behind barrier
+// t_fast + kQuadDrawSlices: the physics lanes arrived at barrier t_fast, and OA at barrier t_fast + 1, with their reads done.
+// The entries live in LDS nobody used: ring entries 48..63 of the four slots (a slot holds 8 envs x 6 agents = 48 states; every ring
+// access in this file is indexed by a ring index < 48, idle lanes shadowing lane 0).  Entry i of a region: 32 entries in one slot's tail,
+// the other 16 in the next slot's (quad_draw_at).
+// ------------------------------------------------------------------------------------------
+constexpr int kQuadDrawRounds = PW_QUAD_DRAW_ROUNDS, kQuadDrawSlices = 10 / kQuadDrawRounds;
+constexpr int kQuadDrawDelay = PW_QUAD_DRAW_DELAY;
+constexpr int kQuadDrawDepth = kQuadDrawSlices + 1;   // steps from the pipeline's first slice to the first reset step that may use its draws
+static_assert(kQuadDrawRounds * kQuadDrawSlices == 10, "a slice is a whole number of Philox4x32-10's rounds");
+static_assert(kQuadDrawDelay >= 1, "the pipeline restarts behind the reset step");
+constexpr int kQuadNever = 0x7fffffff;
+// THE engage rule (all three wave kinds call it, tests/test_quad_draw_rule.py tabulates it): may a reset step that comes
+// `steps_since_start` steps after the pipeline's first slice take its positions from the pipeline?
+__host__ __device__ inline bool quad_draw_engages(const int auto_reset, const int max_episode_len, const bool clocks_equal, const int steps_since_start)
+{
+    return auto_reset != 0 && max_episode_len > 0 && clocks_equal && steps_since_start >= kQuadDrawDepth;
+}
+__host__ __device__ inline int quad_draw_at(const int i) { return (i >> 5) * (2 * kWave) + (i & 31); }   // float2 index of entry i < 48 in s_drawA / s_drawL
+// one round of pw_philox4x32_10 (include/pworld_math.h) on a state kept by the caller; k0, k1: the round's keys
+__host__ __device__ inline void quad_philox_round(uint32_t (&c)[4], const uint32_t k0, const uint32_t k1)
+{
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[1] = (uint32_t)p1; c[3] = (uint32_t)p0; c[0] = n0; c[2] = n2;
+}
+// pw_reset_xy's conversion of the first two words, lo = -1, hi = 1 (its expressions, so its bits)
+__host__ __device__ inline float2 quad_draw_xy(const uint32_t r0, const uint32_t r1)
+{
+    const float lo = -1.0f, hi = 1.0f;
+    const float span = hi - lo;
+    const float u0 = (float)(r0 >> 8) * 5.9604644775390625e-8f;
+    const float u1 = (float)(r1 >> 8) * 5.9604644775390625e-8f;
+    return make_float2(span * u0 + lo, span * u1 + lo);
+}
+struct SpreadQuadLds { float4 *s_ring; float2 *s_ftab, *s_lmB, *s_utab, *s_u, *s_drawA, *s_drawL; float *s_min, *s_rew; int32_t *s_act; uint32_t bytes; };
 __host__ __device__ inline SpreadQuadLds spread_quad_lds(unsigned char *raw = nullptr)
 {
     LdsCursor c{reinterpret_cast<float *>(raw)}; SpreadQuadLds o;
     o.s_ring = c.take<float4>(4 * kWave);                        // [4][64] {px, py, vx, vy}, index e_local * 6 + a
+    o.s_drawA = reinterpret_cast<float2 *>(o.s_ring + kQuadEPW * kQuadN);               // alias, the tails of ring slots 0 and 1: [48] agent positions of the next episode, OB -> P (quad_draw_at)
+    o.s_drawL = reinterpret_cast<float2 *>(o.s_ring + 2 * kWave + kQuadEPW * kQuadN);   // alias, the tails of ring slots 2 and 3: [48] landmark positions of the next episode, OB -> OA
     o.s_ftab = c.take<float2>(2 * kQuadEPP * kQuadN * kQuadN);   // [2 P waves][24 agents][6 partners]
     o.s_min = c.take<float>(kWave); o.s_rew = c.take<float>(kWave);   // [64] each: OB -> OA, a lane's collision count of even / odd steps (int32)
     o.s_lmB = c.take<float2>(kQuadEPW * kQuadL); o.s_act = c.take<int32_t>(2 * kQuadActAhead * kWave);   // [8 * 6] OB; first half: [4 steps][64] action indices (OB)
@@ -205,9 +278,19 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         return t_from + m;
     };
     int t_reset = next_reset_step(0);
-    auto reset_step_update = [&](int t) {  // call in a step with t == t_reset, once: the clocks that reached the end restart
-        if (t + 1 + offs_all >= A.max_episode_len) offs_all = -(t + 1);
-        t_reset = next_reset_step(t + 1);
+    // The draw pipeline's state (see "Reset draws ahead" above): t_fast, the reset step that takes its positions from the pipeline, or -1.
+    auto clocks_equal = [&]() -> bool { return __builtin_amdgcn_ballot_w64(offs_all != __builtin_amdgcn_readfirstlane(offs_all)) == 0; };  // (idle lanes hold env 0's)
+    int t_fast = quad_draw_engages(A.auto_reset, A.max_episode_len, clocks_equal(), t_reset) ? t_reset : -1;   // first slice in iteration 0
+    auto reset_step_update = [&](int t) {  // call in a step with t == t_reset, once: the clocks that reached the end restart; the pipeline restarts behind the step
+        if (t == t_fast) {  // every clock restarts: no lane reads
+            offs_all = -(t + 1);
+            t_reset = t + A.max_episode_len;
+            t_fast = quad_draw_engages(A.auto_reset, A.max_episode_len, true, A.max_episode_len - kQuadDrawDelay) ? t_reset : -1;
+        } else {
+            if (t + 1 + offs_all >= A.max_episode_len) offs_all = -(t + 1);
+            t_reset = next_reset_step(t + 1);
+            t_fast = quad_draw_engages(A.auto_reset, A.max_episode_len, clocks_equal(), t_reset - (t + kQuadDrawDelay)) ? t_reset : -1;
+        }
     };
     int cur = 0;  // ring slot of the current state: workgroup-uniform
 
@@ -260,6 +343,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             u_w[kQuadEPW * N] = quad_action_force(a1, A.sens, A.fscale);
         }
         int u_at = 0;                 // the entry of the coming step: 0 <-> 48, toggled (a lane's constant offset, nothing selected)
+        const float2 *draw_r = Y.s_drawA + quad_draw_at(me);   // this lane's position of the next episode, once wave OB has drawn it
         const float k = A.contact_margin, cf = A.contact_force, dt = A.dt, damp = A.damp, mass = A.mass;
         const uint32_t near_lo = __float_as_uint(A.near_thr2), near_span = 0x7F800000u - near_lo;
         // the pair lanes' operands of the coming step are fetched right after the publish, before the barrier (this
@@ -297,10 +381,16 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             int nxt = (cur + 1) & 3;
             Y.s_ring[nxt * kWave + me] = make_float4(px, py, vx, vy);
             if (__builtin_expect(two_slots, 0)) {  // rare (once per episode): the envs at their episode's end restart, EVERY env publishes a second slot
-                if (t + 1 + ep_off >= A.max_episode_len) {
+                const bool fast = t == t_fast;  // workgroup-uniform: every env restarts, at the position wave OB drew ahead
+                if (fast || t + 1 + ep_off >= A.max_episode_len) {
                     ep_count += 1;
                     ep_off = -(t + 1);
-                    pw_reset_xy(A.seed, env_id, ep_count, (uint32_t)a, -1.0f, 1.0f, &px, &py);
+                    if (fast) {  // written at least one barrier ago (see "Reset draws ahead"): no Philox here
+                        const float2 d = *draw_r;
+                        px = d.x; py = d.y;
+                    } else {
+                        PW_QUAD_RESET_XY(1, A.seed, env_id, ep_count, (uint32_t)a, &px, &py);
+                    }
                     vx = 0.f; vy = 0.f;
                 }
                 reset_step_update(t);
@@ -362,6 +452,7 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         const int cnt_span = (int)(Y.s_rew - Y.s_min);
         int cnt_at = 0;       // word offset of the buffer B(t - 1) reads: 0 <-> cnt_span, workgroup-uniform
         int pre_last = 0;     // the pre-reset slot of the latest A
+        const float2 *draw_r = Y.s_drawL + quad_draw_at(me);   // the owned landmark's position of the next episode, once wave OB has drawn it
         // the pieces, in the order an iteration interleaves them
         float2 q6[N];
         auto a_reads = [&](const int nxt) __attribute__((always_inline)) {
@@ -391,10 +482,16 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
         };
         auto a_clock = [&](const int t, int nxt) __attribute__((always_inline)) {  // episode clocks; the slot A(t + 1) reads
             if (__builtin_expect(t == t_reset, 0)) {  // workgroup-uniform, once per episode
-                if (t + 1 + ep_off >= A.max_episode_len) {
+                const bool fast = t == t_fast;  // workgroup-uniform: every env restarts, with the landmark wave OB drew ahead
+                if (fast || t + 1 + ep_off >= A.max_episode_len) {
                     ep_count += 1;
                     ep_off = -(t + 1);
-                    pw_reset_xy(A.seed, env_id, ep_count, (uint32_t)(N + a), -1.0f, 1.0f, &olx, &oly);
+                    if (fast) {
+                        const float2 d = *draw_r;
+                        olx = d.x; oly = d.y;
+                    } else {
+                        PW_QUAD_RESET_XY(2, A.seed, env_id, ep_count, (uint32_t)(N + a), &olx, &oly);
+                    }
                 }
                 reset_step_update(t);
                 nxt = (nxt + 1) & 3;
@@ -541,6 +638,21 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
     // every load the compiler counts is consumed before the first uncounted one is issued: a counted wait inside the loop (for a
     // value first used there, as ep_count in a reset step) would be short by the fetches in flight, i.e. drain them
     asm volatile("" :: "v"(ep_off), "v"(ep_count), "v"(offs_all), "v"(olx), "v"(oly), "s"(t_reset));
+    // The draws of the next episode (see "Reset draws ahead" above): the two Philox states of this lane, slice t - t_draw in iteration t.
+    uint32_t ca[4], cl[4];
+    float2 nlm = make_float2(0.0f, 0.0f);   // the finished landmark draw, this wave's own copy
+    const uint32_t seed_lo = (uint32_t)A.seed, seed_hi = (uint32_t)(A.seed >> 32);
+    float2 *draw_wa = Y.s_drawA + quad_draw_at(me), *draw_wl = Y.s_drawL + quad_draw_at(me);
+    int t_draw = kQuadNever;   // the iteration of the pipeline's first slice: workgroup-uniform
+    auto draw_start = [&](int t_first) __attribute__((always_inline)) {   // call with ep_count of the episode that runs in iteration t_first
+        const bool go = t_fast >= 0;
+        t_draw = go ? t_first : kQuadNever;
+        ca[0] = (uint32_t)a; cl[0] = (uint32_t)(N + a);
+        ca[1] = cl[1] = ep_count + 1u;
+        ca[2] = cl[2] = (uint32_t)env_id;
+        ca[3] = cl[3] = (uint32_t)(env_id >> 32);
+    };
+    draw_start(0);
     for (int s0 = 2; s0 < 2 + kQuadActAhead; ++s0) fetch_act(s0, ((uint32_t)s0 * kSlotBytes) & kRingMask, 0u);
     if (lane < 6) Y.s_utab[lane] = quad_action_force(lane, A.sens, A.fscale);
     float2 *u_w = Y.s_u + me;
@@ -594,9 +706,11 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
                 ep_count += 1;
                 ep_off = -(t + 1);
                 t_term = A.max_episode_len - 1 - ep_off;
-                pw_reset_xy(A.seed, env_id, ep_count, (uint32_t)(N + a), -1.0f, 1.0f, &olx, &oly);
+                if (t == t_fast) { olx = nlm.x; oly = nlm.y; }   // workgroup-uniform: every env restarts, with the landmark drawn ahead
+                else PW_QUAD_RESET_XY(4, A.seed, env_id, ep_count, (uint32_t)(N + a), &olx, &oly);
             }
             reset_step_update(t);
+            draw_start(t + kQuadDrawDelay);
             wave_lds_sync();     // the pre-reset rows have read the old landmarks
             if (rst) Y.s_lmB[me] = make_float2(olx, oly);
             wave_lds_sync();
@@ -632,6 +746,21 @@ __global__ void __launch_bounds__(4 * kWave) pw_spread_quad_kernel(const StreamP
             nt_store(reinterpret_cast<float4 *>(obs_t + off_u[u]), o);
         }
         obs_t += obs_stride; done_t += BN; term_t += A.B;
+        const int ph = t - t_draw;   // the pipeline's slice of this iteration; one scalar compare and branch in the steps without
+        if ((unsigned)ph < (unsigned)kQuadDrawSlices) {
+            uint32_t k0 = seed_lo + (uint32_t)(ph * kQuadDrawRounds) * 0x9E3779B9u, k1 = seed_hi + (uint32_t)(ph * kQuadDrawRounds) * 0xBB67AE85u;
+#pragma unroll
+            for (int r = 0; r < kQuadDrawRounds; ++r) {
+                quad_philox_round(ca, k0, k1);
+                quad_philox_round(cl, k0, k1);
+                k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+            }
+            if (ph == kQuadDrawSlices - 1) {  // done: published before this wave arrives at the next barrier (its s_waitcnt)
+                nlm = quad_draw_xy(cl[0], cl[1]);
+                *draw_wa = quad_draw_xy(ca[0], ca[1]);
+                *draw_wl = nlm;
+            }
+        }
         PW_QUAD_PAD_OB();
         PW_STAMP(1);
     }

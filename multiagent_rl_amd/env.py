@@ -18,6 +18,11 @@ import torch
 from . import _lib
 from ._lib import PwConfig, PwStateLayout, PwStepIO, check
 
+# csrc/pw_kernels_spread_quad.hpp kQuadDrawDepth: steps between the start of a launch (or an episode) and the first episode end whose
+# reset positions the quad kernel has drawn ahead.  Nothing here uses it -- results do not depend on it -- it names the launch lengths at
+# which the kernel changes path, for the tests (tests/test_quad_draw_rule.py holds it against the header).
+QUAD_DRAW_DEPTH = 2
+
 
 class Discrete(object):
     """gym.spaces.Discrete stand-in: ``.n`` and deliberately NO ``.high``

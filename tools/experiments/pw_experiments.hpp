@@ -16,6 +16,10 @@
 //   PW_EXP_NO_COLL_TESTS  the quad kernel's six collision tests per output lane and step compiled out, the count fixed at 1 (read by
 //                         pw_kernels_spread_quad.hpp quad_coll_tests): the bound of taking that work off a SIMD altogether.  Measured
 //                         on the kernel whose wave OA still held the tests (profiles/r7_quad_balance.txt); now they are wave OB's
+//   PW_EXP_NO_RESET_DRAWS=<mask>  the quad kernel's reset draws (pw_reset_xy: Philox4x32-10, twenty 64-bit products) replaced by a short
+//                         hash of the same operands, per wave kind: bit 0 the physics waves, bit 1 wave OA, bit 2 wave OB (1: P only,
+//                         6: OA + OB, 7: all).  What the draws cost a reset step, and whose share reaches the step time
+//                         (profiles/r9_quad_reset_bound.txt)
 //   (PW_QUAD_ACT_AHEAD=8|16 is a plain parameter of pw_kernels_spread_quad.hpp, not an experiment: results stay exact)
 #pragma once
 #ifndef PW_EXPERIMENTS
@@ -51,6 +55,23 @@ __device__ __forceinline__ void nt_store(float2 *p, const float2 v) { asm volati
 #define PW_QUAD_BARRIER(t) do { if (!((t) & 1)) duo_barrier(); else wave_lds_sync(); } while (0)
 #elif defined(PW_EXP_BARRIER0)
 #define PW_QUAD_BARRIER(t) wave_lds_sync()
+#endif
+
+#if defined(PW_EXP_NO_RESET_DRAWS) && PW_EXP_NO_RESET_DRAWS > 0
+// kind: 1 physics, 2 OA, 4 OB.  The stand-in must keep the agents' positions independent and uniform on [-1, 1): the physics waves skip
+// the force block when no pair of the wave is near, so the contact rate IS the step time (a first stand-in that lined an env's agents
+// up 0.25 apart made the step 6 % SLOWER).  Hence a full 32-bit mix: five 32-bit products instead of twenty 64-bit ones.
+#define PW_QUAD_RESET_XY(kind, seed, env_id, episode, entity, x, y)                                                              \
+    do {                                                                                                                         \
+        if ((PW_EXP_NO_RESET_DRAWS) & (kind)) {                                                                                  \
+            uint32_t h_ = (uint32_t)(env_id) * 0x9E3779B9u + (episode) * 0x85EBCA6Bu + (entity) * 0xC2B2AE35u + (uint32_t)(seed); \
+            h_ ^= h_ >> 16; h_ *= 0x85EBCA6Bu; h_ ^= h_ >> 13; h_ *= 0xC2B2AE35u; h_ ^= h_ >> 16;                                \
+            *(x) = 2.0f * ((float)(h_ & 0xFFFFu) * 1.52587890625e-05f) + -1.0f;                                                  \
+            *(y) = 2.0f * ((float)(h_ >> 16) * 1.52587890625e-05f) + -1.0f;                                                      \
+        } else {                                                                                                                 \
+            pw_reset_xy(seed, env_id, episode, entity, -1.0f, 1.0f, x, y);                                                       \
+        }                                                                                                                        \
+    } while (0)
 #endif
 
 #define PW_EXP_STR_(x) #x

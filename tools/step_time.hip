@@ -13,6 +13,7 @@ int main(int argc, char **argv)
     const bool tag = getenv("ST_TAG") != nullptr;
     pw_config_default(&cfg, tag ? PW_SIMPLE_TAG : PW_SIMPLE_SPREAD, B, N, tag ? 2 : -1, tag ? 4 : 0);
     cfg.auto_reset = 1;
+    if (argc > 6) cfg.max_episode_len = atoi(argv[6]);   // episode length (default: the config's 25); longer than T * (reps + 3): no reset is ever timed
     pw_handle *h;
     if (pw_create(&cfg, &h)) { printf("create: %s\n", pw_last_error()); return 1; }
     void *state; hipMalloc(&state, pw_state_bytes(h)); hipMemset(state, 0, pw_state_bytes(h));
@@ -39,7 +40,7 @@ int main(int argc, char **argv)
     hipEventRecord(e1, nullptr);
     hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1);
-    printf("%s B=%d N=%d T=%d: %.4f us/step  %.3e env-steps/s  [%s]\n", argv[0], B, N, T, ms * 1e3 / ((double)reps * T),
+    printf("%s B=%d N=%d T=%d len=%d: %.4f us/step  %.3e env-steps/s  [%s]\n", argv[0], B, N, T, (int)cfg.max_episode_len, ms * 1e3 / ((double)reps * T),
            (double)B * reps * T / (ms * 1e-3), pw_rollout_kernel(h));
     return 0;
 }
