@@ -18,6 +18,10 @@ forward and backward, on the HIP kernels (``multiagent_rl_amd.lstm.fuse_lstm``);
 ``Trainer(..., fused_attention=True)``: the attention block of an attention critic (and of the target critic copied from it) runs,
 forward and backward, on the HIP kernels (``multiagent_rl_amd.attention.fuse_attention``); the default is the stock expression, and a
 critic without that block is left as it is.
+``Trainer(..., graph_update=True)``: the whole update is captured once and replayed as one graph launch per ``optimize()``
+(``multiagent_rl_amd.graph.GraphedUpdate``, installed by ``accelerate_trainer(self, targets=True, ..., graph=True)``); it needs the three
+switches above and a ``ReplayBuffer(device_index='counter')``, and says what is missing otherwise.  ``optimize()`` then returns the two
+loss TENSORS of the replay (no read-back per update); ``optimize.losses()`` reads them.
 """
 import copy
 import os
@@ -47,7 +51,7 @@ class Trainer(object):
     per_agent = False   # BiCNetTrainer: per-agent rewards / dones [b,N] and a critic that returns [b,N,1]
 
     def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
-                 fused_lstm=False, fused_attention=False):
+                 fused_lstm=False, fused_attention=False, graph_update=False):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
         if fused_attention:   # before the deep copies, like fused_lstm
@@ -62,10 +66,15 @@ class Trainer(object):
         self.fused_optimizer = bool(fused_optimizer)
         if self.fused_optimizer:   # clip (0.5) + Adam + soft update of the target: one launch per network
             from multiagent_rl_amd.optim import FusedAdam
-            self.actor_optimizer = FusedAdam(self.actor.parameters(), lr, max_norm=0.5, targets=self.target_actor.parameters(), tau=TAU)
-            self.critic_optimizer = FusedAdam(self.critic.parameters(), lr, max_norm=0.5, targets=self.target_critic.parameters(), tau=TAU)
+            self.actor_optimizer = FusedAdam(self.actor.parameters(), lr, max_norm=0.5, targets=self.target_actor.parameters(), tau=TAU,
+                                             graph_steps=bool(graph_update))
+            self.critic_optimizer = FusedAdam(self.critic.parameters(), lr, max_norm=0.5, targets=self.target_critic.parameters(), tau=TAU,
+                                              graph_steps=bool(graph_update))
         self.memory, self.action_type, self.batch_size = memory, action_type, batch_size
         self.iter = 0
+        if graph_update:   # the target networks go to the HIP kernels and optimize() becomes the graphed update (or a ValueError says why not)
+            from multiagent_rl_amd.policy import accelerate_trainer
+            accelerate_trainer(self, targets=True, graph=True)
 
     @staticmethod
     def _fuse_attention(critic):
@@ -101,6 +110,11 @@ class Trainer(object):
         return F.gumbel_softmax(logits, hard=True, dim=-1).cpu().numpy()
 
     def optimize(self):
+        loss_actor, loss_critic = self.optimize_tensors()
+        return float(loss_actor), float(loss_critic)
+
+    def optimize_tensors(self):
+        """One update; -> (loss_actor, loss_critic) as device tensors: no read-back, so the whole of it can be captured in a graph."""
         s0, a0, r, s1, d = (torch.as_tensor(x, dtype=torch.float32, device=self.device)
                             for x in self.memory.sample_index(self.memory.make_index(self.batch_size)))
         if r.dim() != (2 if self.per_agent else 1):
@@ -128,7 +142,7 @@ class Trainer(object):
                     for pt, ps in zip(tgt.parameters(), src.parameters()):
                         pt.mul_(1.0 - TAU).add_(ps, alpha=TAU)
         self.iter += 1
-        return float(loss_actor.detach()), float(loss_critic.detach())
+        return loss_actor.detach(), loss_critic.detach()
 
     def save_models(self, name, out_dir='Models'):
         """Target nets' state_dicts as ``<name>_actor.pt`` / ``<name>_critic.pt`` (ddpg_gumbel_fix.py:221-229)."""

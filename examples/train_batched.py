@@ -76,7 +76,17 @@ def main(argv=None):
                     help="the attention block of the learner's critic runs, forward and backward, on the HIP kernels (madr_learner's "
                          'fused_attention switch; with --reference: accelerate_trainer(.., attention=True)); needs the attention or '
                          'the model critic; off by default: losses differ from the stock expression in the last bits')
+    ap.add_argument('--graph-update', action='store_true',
+                    help="the learner's whole update is captured once and replayed as one graph launch per update "
+                         '(multiagent_rl_amd.graph.GraphedUpdate); needs --fused-targets --fused-optimizer --fused-lstm --fused-attention '
+                         '(--critic bicnet, which has no attention block: the first three); the ring draws its batches from device cells')
     args = ap.parse_args(argv)
+    if args.graph_update:
+        need = ['--fused-targets', '--fused-optimizer', '--fused-lstm'] + ([] if args.critic == 'bicnet' else ['--fused-attention'])
+        lacking = [f for f in need if not getattr(args, f[2:].replace('-', '_'))]
+        if lacking:
+            ap.error('--graph-update needs %s: a captured update holds no vendor RNN call and no stock optimiser (missing: %s)'
+                     % (' '.join(need), ' '.join(lacking)))
     if args.fused_attention and args.critic not in ('attention', 'model') and not args.reference:
         ap.error('--fused-attention needs --critic attention or --critic model (the block exists in the LSTM + attention critics only)')
     if args.fused_targets and args.critic not in ('attention', 'bicnet', 'model') and not args.reference:
@@ -122,10 +132,14 @@ def main(argv=None):
                 k['fused_lstm'] = True
             if args.fused_attention and not args.reference:
                 k['fused_attention'] = True
+            if args.graph_update and not args.reference:
+                k['graph_update'] = True     # madr_learner installs the fused targets and the graphed update itself
+                return plain_trainer(*a, **k)
             learner = plain_trainer(*a, **k)
             if args.fused_targets or args.reference:
                 accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
-                                   lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference)
+                                   lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference,
+                                   graph=args.graph_update)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))
@@ -178,7 +192,8 @@ def main(argv=None):
             hist = train_batched(env, actor, critic, Trainer, scenario_name, action_type, cnt=cnt, out_dir=args.out_dir,
                                  chunk=args.chunk, max_updates_per_chunk=args.max_updates_per_chunk, gather=gather,
                                  ring='state' if (gather is None and state_ok) else 'rows',
-                                 rank=rank, world=world, log=print if rank == 0 else (lambda *a: None), per_agent_transition=bicnet)
+                                 rank=rank, world=world, log=print if rank == 0 else (lambda *a: None), per_agent_transition=bicnet,
+                                 graph_update=args.graph_update)
             results.append((scenario_name, cnt, hist['stats']))
             if rank == 0:
                 s = hist['stats']

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 115 /* 0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 116 /* 0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -299,6 +299,23 @@ size_t pw_replay_add_rollout_scratch_bytes(int32_t B);
 int pw_replay_gather(const pw_replay_store *st, const int64_t *idx, int32_t b,
                      float *out_obs, float *out_act, float *out_rew, float *out_next_obs,
                      float *out_done, void *stream);
+/* make_index() + sample_index() as ONE launch whose every changing input lives in device memory (a captured launch freezes by-value
+ * arguments): draws b ring slots and, where outputs are given, gathers them exactly as pw_replay_gather would (row, two-head,
+ * per-agent and STATE rings; the same arithmetic, so the same bits as pw_replay_gather on out_idx).
+ *   c = *call_dev (which draw this is), len = clamp(*len_dev, 1, st->capacity) (how many transitions the ring holds);
+ *   element e takes word (e & 3) of Philox4x32-10(counter = (e >> 2, c lo, c hi, 0x52504C59), key = (seed lo, seed hi));
+ *   idx = ((u64)word * (u64)len) >> 32.
+ * Uniform with replacement up to a relative bias of len / 2^32 (2.3e-4 at 10^6 transitions; torch.randint's modulo has the same kind).
+ * The clamp makes an out-of-range slot impossible whatever the cell holds; an empty ring is the caller's to refuse.  The counter
+ * domain meets neither the reset draws nor the Gumbel noise (csrc/pw_replay_draw.hpp lists the streams).  The launch does not
+ * advance *call_dev: follow it with pw_counter_add(call_dev, 1, 0, stream).  out_idx [b] (optional) receives the slots; out_idx
+ * alone, every other output NULL, is the draw alone (make_index).  PW_EINVAL, nothing launched: a null st, call_dev or len_dev,
+ * b < 1, all six outputs NULL, a capacity above 2^32 -- and what pw_replay_gather refuses. */
+int pw_replay_sample(const pw_replay_store *st, uint64_t seed, const int64_t *call_dev, const int64_t *len_dev, int32_t b,
+                     int64_t *out_idx /* may be NULL */, float *out_obs, float *out_act, float *out_rew,
+                     float *out_next_obs, float *out_done /* each may be NULL */, void *stream);
+/* The draw of pw_replay_sample on the host: the slot of element e of draw number `call` at length len (clamped to [1, 2^32]). */
+int64_t pw_replay_draw_host(uint64_t seed, int64_t call, int64_t e, int64_t len);
 
 /* ---- multi-GPU exchange (one rank per GPU; the collective itself is RCCL, driven by the host) ----
  * A transition row is f32 [obs N*D | next_obs N*D | act N | rew | done], width 2*N*D + N + 2.
@@ -609,6 +626,18 @@ typedef struct pw_opt_tensor {
 int pw_adam_step(const pw_opt_tensor *tensors, int32_t count, int64_t step, double lr, double beta1, double beta2, double eps,
                  double weight_decay, double max_norm /* <= 0: no clipping */, double tau /* used where target != NULL */,
                  float *total_norm /* device, or NULL */, void *stream);
+/* pw_adam_step with the step count in device memory (a captured launch freezes by-value arguments): *step_dev (8-byte aligned) is
+ * the step this call takes, a value below 1 counts as 1; advance it with pw_counter_add(step_dev, 1, 0, stream).  Same table,
+ * hyper-parameters, limits and arithmetic; the kernel forms the two step-dependent scalars itself, in float64:
+ *   bc2_sqrt = (float)sqrt(1 - beta2^t), step_size = (float)(lr / (1 - beta1^t)), beta^t by square-and-multiply, least significant
+ *   bit first (r = 1; x = beta; while t: if t & 1: r *= x; x *= x; t >>= 1) -- multiplications only, so host and device agree bit
+ * for bit (csrc/pw_optim_bias.hpp).  pw_adam_step uses std::pow; after rounding to float32 the two forms agree at every t <= 20000
+ * for (beta1, beta2, lr) in {(0.9, 0.999, 1e-2), (0.9, 0.999, 1e-3), (0.8, 0.99, 3e-4)}.  PW_EINVAL as pw_adam_step, and a null or
+ * misaligned step_dev. */
+int pw_adam_step_dev(const pw_opt_tensor *tensors, int32_t count, const int64_t *step_dev, double lr, double beta1, double beta2,
+                     double eps, double weight_decay, double max_norm, double tau, float *total_norm, void *stream);
+/* out[0] = bc2_sqrt, out[1] = step_size of pw_adam_step_dev at `step`, formed on the host by the same function. */
+void pw_adam_bias_scalars(int64_t step, double lr, double beta1, double beta2, float out[2]);
 /* target[k] = target[k] * (1 - tau) + source[k] * tau for count tensor pairs of numel[k] elements, one launch: both products
  * rounded to float32 before the sum, bit for bit torch's `t * (1.0 - tau) + s * tau`.  tau == 1 copies (an infinity in the old
  * target does not become NaN).  The three arrays are HOST arrays of device pointers / sizes; limits as pw_adam_step. */

@@ -163,6 +163,8 @@ SIGNATURES = {
     'pw_debug_math': (C.c_int, [C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_int64, C.c_void_p]),
     'pw_margin_one_correction': (C.c_int, [C.c_float]),
     'pw_replay_gather': (C.c_int, [C.POINTER(PwReplayStore), C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_void_p]),
+    'pw_replay_sample': (C.c_int, [C.POINTER(PwReplayStore), C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 6 + [C.c_void_p]),
+    'pw_replay_draw_host': (C.c_int64, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64]),
     'pw_critic_forward': (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 8 + [C.c_int64, C.c_int32, C.c_int32,
                                                                                           C.c_void_p, C.c_void_p, C.c_float,
                                                                                           C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -174,6 +176,8 @@ SIGNATURES = {
                                                                                                  C.c_void_p, C.c_void_p, C.c_void_p,
                                                                                                  C.c_void_p]),
     'pw_adam_step': (C.c_int, [C.POINTER(PwOptTensor), C.c_int32, C.c_int64] + [C.c_double] * 7 + [C.c_void_p, C.c_void_p]),
+    'pw_adam_step_dev': (C.c_int, [C.POINTER(PwOptTensor), C.c_int32, C.c_void_p] + [C.c_double] * 7 + [C.c_void_p, C.c_void_p]),
+    'pw_adam_bias_scalars': (None, [C.c_int64, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_float)]),
     'pw_soft_update': (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int32, C.c_double,
                                  C.c_void_p]),
     'pw_lstm_train_forward': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),

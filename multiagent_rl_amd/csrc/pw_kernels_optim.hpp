@@ -25,7 +25,8 @@
 //   g  = fma(wd, p, g)                            (weight_decay != 0: the L2 form, after the clip)
 //   m  = fma(m, beta1, g * (1 - beta1))           (1 - beta1, 1 - beta2: float64 on the host, then rounded)
 //   v  = fma(v, beta2, (g * g) * (1 - beta2))
-//   d  = sqrt(v) / sqrt(1 - beta2^step) + eps     (IEEE sqrt and division; the bias corrections: float64 on the host)
+//   d  = sqrt(v) / sqrt(1 - beta2^step) + eps     (IEEE sqrt and division; the bias corrections: float64 on the host --
+//                                                   pw_adam_step_dev: float64 in the kernel, pw_optim_bias.hpp)
 //   p  = fma(-(lr / (1 - beta1^step)), m / d, p)
 // torch.optim.Adam(foreach=False) forms m with lerp and v with mul + addcmul: a different, equally long rounding chain.
 //
@@ -37,110 +38,19 @@
 #include <hip/hip_runtime.h>
 
 #include "pworld.h"
+#include "pw_optim_args.hpp"
 
 namespace {
 
-constexpr int kOptThreads = 512;
-constexpr int kOptTile = 2048;   // elements per workgroup: 4 per lane
-
-struct OptTensor {
-    float *param;
-    const float *grad;
-    float *exp_avg, *exp_avg_sq;
-    float *target;
-    long numel;
-};
-
-struct OptArgs {
-    OptTensor t[PW_OPT_MAX_TENSORS];
-    int tile_begin[PW_OPT_MAX_TENSORS + 1];
-    int count;
-    int need_norm;        // max_norm > 0 or total_norm wanted
-    double max_norm;      // <= 0: no clipping
-    float wd, beta1, beta2, omb1, omb2, eps, bc2_sqrt, step_size;
-    float tau, omt;       // (float)tau, (float)(1 - tau)
-    int hard;             // tau == 1
-    float *total_norm;
-};
-
-struct SoftTensor {
-    float *target;
-    const float *source;
-    long numel;
-};
-
-struct SoftArgs {
-    SoftTensor t[PW_OPT_MAX_TENSORS];
-    int tile_begin[PW_OPT_MAX_TENSORS + 1];
-    int count;
-    float tau, omt;
-    int hard;
-};
-
-// The tensor that owns tile w: tile_begin[k] <= w < tile_begin[k + 1] (a uniform scan of at most 32 entries).
-template <typename Args>
-__device__ __forceinline__ int opt_tile_owner(const Args &A, const int w)
-{
-    int k = 0;
-    while (k + 1 < A.count && A.tile_begin[k + 1] <= w) ++k;
-    return k;
-}
-
-__device__ __forceinline__ float opt_polyak(const float t, const float p, const float omt, const float tau)
-{
-    const float a = t * omt, b = p * tau;
-    return a + b;
-}
-
+// The body is text shared with pw_adam_step_dev_kernel (pw_kernels_optim_dev.hpp); the two scalars that kernel forms itself are macros here.
 __global__ void __launch_bounds__(kOptThreads) pw_adam_step_kernel(const OptArgs A)
 {
     __shared__ double s_part[kOptThreads];
-    const int lane = threadIdx.x;
-    float coef = 1.0f;
-    if (A.need_norm) {
-        double acc = 0.0;
-        for (int k = 0; k < A.count; ++k) {
-            const float *__restrict__ g = A.t[k].grad;
-            const long n = A.t[k].numel;
-            for (long i = lane; i < n; i += kOptThreads) {
-                const double x = (double)g[i];
-                acc += x * x;
-            }
-        }
-        s_part[lane] = acc;
-        __syncthreads();
-        for (int s = kOptThreads / 2; s > 0; s >>= 1) {
-            if (lane < s) s_part[lane] += s_part[lane + s];
-            __syncthreads();
-        }
-        const double norm = sqrt(s_part[0]);
-        if (A.max_norm > 0.0) {
-            const double c = A.max_norm / (norm + 1e-6);
-            coef = (float)(c >= 1.0 ? 1.0 : c);   // NaN passes, as torch's clamp(max=1) lets it
-        }
-        if (A.total_norm != nullptr && blockIdx.x == 0 && lane == 0) *A.total_norm = (float)norm;
-    }
-    const int k = opt_tile_owner(A, (int)blockIdx.x);
-    const OptTensor T = A.t[k];
-    const long base = (long)((int)blockIdx.x - A.tile_begin[k]) * kOptTile;
-    const bool clip = A.max_norm > 0.0;
-#pragma unroll
-    for (int j = 0; j < kOptTile / kOptThreads; ++j) {
-        const long i = base + j * kOptThreads + lane;
-        if (i >= T.numel) break;
-        float g = T.grad[i];
-        float p = T.param[i];
-        if (clip) g = g * coef;
-        if (A.wd != 0.0f) g = __builtin_fmaf(A.wd, p, g);
-        const float m = __builtin_fmaf(T.exp_avg[i], A.beta1, g * A.omb1);
-        const float v = __builtin_fmaf(T.exp_avg_sq[i], A.beta2, (g * g) * A.omb2);
-        const float d = sqrtf(v) / A.bc2_sqrt + A.eps;
-        p = __builtin_fmaf(-A.step_size, m / d, p);
-        T.exp_avg[i] = m;
-        T.exp_avg_sq[i] = v;
-        T.param[i] = p;
-        if (T.target != nullptr) T.target[i] = A.hard ? p : opt_polyak(T.target[i], p, A.omt, A.tau);
-    }
+#define PW_ADAM_BC2_SQRT A.bc2_sqrt
+#define PW_ADAM_STEP_SIZE A.step_size
+#include "pw_kernels_optim_adam_body.inc"
+#undef PW_ADAM_BC2_SQRT
+#undef PW_ADAM_STEP_SIZE
 }
 
 __global__ void __launch_bounds__(kOptThreads) pw_soft_update_kernel(const SoftArgs A)

@@ -1,8 +1,9 @@
 // pw_kernels_replay.hpp -- part of libpworld.so (translation unit csrc/pworld_replay.hip includes it).
-// Device replay ring, transition packing and the fused multi-GPU exchange launch.
+// Device replay ring, transition packing and the fused multi-GPU exchange launch.  The batch draw of pw_replay_sample: pw_replay_draw.hpp.
 #pragma once
 
 #include "pw_common.hpp"
+#include "pw_replay_draw.hpp"
 
 namespace {
 
@@ -224,35 +225,51 @@ __global__ void __launch_bounds__(256) pw_replay_add_rollout_kernel(const pw_rep
     }
 }
 
+// Where a gathered batch element comes from.  pw_replay_gather: the caller's index list.  pw_replay_sample: the draw of
+// pw_replay_draw.hpp, which every thread of an element evaluates for itself (stateless per element); the element's first thread
+// also stores it where out_idx is given.  The gather bodies are shared as text (pw_kernels_replay_gather_body.inc,
+// pw_kernels_replay_gather_state_body.inc): as __forceinline__ function templates over the slot source they compile the two existing
+// kernels to other instructions than the bodies in the kernels do (other scalar loads of the argument block, two more VGPRs), and
+// tools/code_object.py --compare holds every existing kernel to its parent's disassembly.
+struct ReplayDraw {
+    uint64_t seed;
+    int64_t call, len;
+    __device__ __forceinline__ ReplayDraw(const pw_replay_store &st, const uint64_t seed_, const int64_t *call_dev, const int64_t *len_dev)
+        : seed(seed_), call(*call_dev), len(pw_replay_clamp_len(*len_dev, st.capacity)) {}
+    __device__ __forceinline__ size_t operator()(const size_t e) const { return (size_t)pw_replay_draw(seed, call, (int64_t)e, len); }
+};
+
 __global__ void pw_replay_gather_kernel(const pw_replay_store st, const int64_t *idx, const int b,
                                         float *out_obs, float *out_act, float *out_rew, float *out_next_obs,
                                         float *out_done)
 {
-    const int ND = st.num_agents * st.obs_dim, N = st.num_agents, H = store_heads(st);
-    const int W0 = st.head_width[0] > 0 ? st.head_width[0] : 5, W1 = H == 2 ? st.head_width[1] : 0, W = W0 + W1;
-    const size_t total = (size_t)b * ND;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t e = i / ND, c = i - e * ND;
-        const size_t slot = (size_t)idx[e];
-        if (out_obs) out_obs[i] = st.obs[slot * ND + c];
-        if (out_next_obs) out_next_obs[i] = st.next_obs[slot * ND + c];
-        if (c < (size_t)N) {
-            if (out_act) {  // the one-hot rows the reference stored: [head 0 | head 1] per agent (run.py:38-41)
-                const int a0 = st.act[(slot * N + c) * H], a1 = H == 2 ? st.act[(slot * N + c) * H + 1] : -1;
-                float *row = out_act + (e * N + c) * W;
-                for (int k = 0; k < W0; ++k) row[k] = a0 == k ? 1.0f : 0.0f;
-                for (int k = 0; k < W1; ++k) row[W0 + k] = a1 == k ? 1.0f : 0.0f;
-            }
-            if (st.per_agent) {
-                if (out_rew) out_rew[e * N + c] = st.rew[slot * N + c];
-                if (out_done) out_done[e * N + c] = st.done[slot * N + c];
-            }
-        }
-        if (c == 0 && !st.per_agent) {
-            if (out_rew) out_rew[e] = st.rew[slot];
-            if (out_done) out_done[e] = st.done[slot];
-        }
-    }
+#define PW_GATHER_SLOT(e) ((size_t)idx[e])
+#define PW_GATHER_NOTE(first, e, slot)
+#include "pw_kernels_replay_gather_body.inc"
+#undef PW_GATHER_SLOT
+#undef PW_GATHER_NOTE
+}
+
+// pw_replay_sample on a row ring: the gather above with slot = draw(e) in place of idx[e]; out_idx (optional) receives the draw.
+__global__ void pw_replay_sample_kernel(const pw_replay_store st, const uint64_t seed, const int64_t *call_dev, const int64_t *len_dev,
+                                        const int b, int64_t *out_idx, float *out_obs, float *out_act, float *out_rew,
+                                        float *out_next_obs, float *out_done)
+{
+    const ReplayDraw draw(st, seed, call_dev, len_dev);
+#define PW_GATHER_SLOT(e) draw(e)
+#define PW_GATHER_NOTE(first, e, slot) if ((first) && out_idx) out_idx[e] = (int64_t)(slot);
+#include "pw_kernels_replay_gather_body.inc"
+#undef PW_GATHER_SLOT
+#undef PW_GATHER_NOTE
+}
+
+// The draw alone (ReplayBuffer.make_index): thread = batch element.
+__global__ void pw_replay_draw_kernel(const pw_replay_store st, const uint64_t seed, const int64_t *call_dev, const int64_t *len_dev,
+                                      const int b, int64_t *out_idx)
+{
+    const ReplayDraw draw(st, seed, call_dev, len_dev);
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < (size_t)b; e += (size_t)gridDim.x * blockDim.x)
+        out_idx[e] = (int64_t)draw(e);
 }
 
 // Transition rows for the multi-GPU exchange: [obs ND | next_obs ND | act N | rew | done], f32.
@@ -686,30 +703,24 @@ __global__ void __launch_bounds__(256) pw_replay_gather_state_kernel(const pw_re
                                                                      float *out_obs, float *out_act, float *out_rew,
                                                                      float *out_next_obs, float *out_done)
 {
-    const RowGeom G = {st.scenario, st.num_agents, st.num_landmarks, st.num_adversaries};
-    const int N = st.num_agents, U = st.obs_dim / 2, W0 = st.head_width[0] > 0 ? st.head_width[0] : 5;
-    const size_t total = (size_t)b * N * U;
-    const float4 *r_s = reinterpret_cast<const float4 *>(st.obs), *r_n = reinterpret_cast<const float4 *>(st.next_obs);
-    const float2 *r_lm = reinterpret_cast<const float2 *>(st.lm);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t ea = i / U, e = ea / N;
-        const int k = (int)(i - ea * U), a = (int)(ea - e * N);
-        const size_t slot = (size_t)idx[e];
-        const float2 *lm = r_lm + slot * G.L;
-        if (out_obs) reinterpret_cast<float2 *>(out_obs)[i] = state_row_unit(G, a, k, r_s + slot * N, lm);
-        if (out_next_obs) reinterpret_cast<float2 *>(out_next_obs)[i] = state_row_unit(G, a, k, r_n + slot * N, lm);
-        if (k == 0) {
-            if (out_act) {
-                const int a0 = st.act[slot * N + a];
-                float *row = out_act + ea * W0;
-                for (int q = 0; q < W0; ++q) row[q] = a0 == q ? 1.0f : 0.0f;
-            }
-            if (a == 0) {
-                if (out_rew) out_rew[e] = st.rew[slot];
-                if (out_done) out_done[e] = st.done[slot];
-            }
-        }
-    }
+#define PW_GATHER_SLOT(e) ((size_t)idx[e])
+#define PW_GATHER_NOTE(first, e, slot)
+#include "pw_kernels_replay_gather_state_body.inc"
+#undef PW_GATHER_SLOT
+#undef PW_GATHER_NOTE
+}
+
+// pw_replay_sample on a STATE ring.
+__global__ void __launch_bounds__(256) pw_replay_sample_state_kernel(const pw_replay_store st, const uint64_t seed, const int64_t *call_dev,
+                                                                     const int64_t *len_dev, const int b, int64_t *out_idx, float *out_obs,
+                                                                     float *out_act, float *out_rew, float *out_next_obs, float *out_done)
+{
+    const ReplayDraw draw(st, seed, call_dev, len_dev);
+#define PW_GATHER_SLOT(e) draw(e)
+#define PW_GATHER_NOTE(first, e, slot) if ((first) && out_idx) out_idx[e] = (int64_t)(slot);
+#include "pw_kernels_replay_gather_state_body.inc"
+#undef PW_GATHER_SLOT
+#undef PW_GATHER_NOTE
 }
 
 // ------------------------------------------------------------------------------------------

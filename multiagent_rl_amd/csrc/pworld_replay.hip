@@ -1,4 +1,4 @@
-// libpworld.so, fifth translation unit -- the replay ring (pw_replay_add*, pw_replay_gather), transition packing (pw_pack_transitions,
+// libpworld.so, fifth translation unit -- the replay ring (pw_replay_add*, pw_replay_gather, pw_replay_sample), transition packing (pw_pack_transitions,
 // pw_exchange) and the three wire formats (pw_chunk_wire_*, pw_state_wire_*, pw_ref_wire_*).  The kernels are csrc/pw_kernels_replay.hpp; of the
 // environment only the handle is used (pw_state_wire_begin / _finalize).  Declared in include/pworld.h; the error text is shared with pworld.hip.
 #include "pw_host.hpp"
@@ -212,6 +212,52 @@ int pw_replay_gather(const pw_replay_store *st, const int64_t *idx, int32_t b, f
     const size_t total = (size_t)b * st->num_agents * st->obs_dim;
     hipLaunchKernelGGL(pw_replay_gather_kernel, dim3(grid_blocks(total, 8192)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        *st, idx, b, out_obs, out_act, out_rew, out_next_obs, out_done);
+    PW_HIP_CHECK(hipGetLastError());
+    return PW_OK;
+}
+
+int64_t pw_replay_draw_host(uint64_t seed, int64_t call, int64_t e, int64_t len)
+{
+    return pw_replay_draw(seed, call, e, pw_replay_clamp_len(len, (int64_t)1 << 32));
+}
+
+int pw_replay_sample(const pw_replay_store *st, uint64_t seed, const int64_t *call_dev, const int64_t *len_dev, int32_t b,
+                     int64_t *out_idx, float *out_obs, float *out_act, float *out_rew, float *out_next_obs, float *out_done,
+                     void *stream)
+{
+    if (!st) return fail(PW_EINVAL, "pw_replay_sample: st is null");
+    if (!call_dev) return fail(PW_EINVAL, "pw_replay_sample: call_dev is null (the device cell that numbers the draw)");
+    if (!len_dev) return fail(PW_EINVAL, "pw_replay_sample: len_dev is null (the device cell that holds the ring's length)");
+    if (b < 1) return fail(PW_EINVAL, "pw_replay_sample: b must be >= 1");
+    const bool gather = out_obs || out_act || out_rew || out_next_obs || out_done;
+    if (!out_idx && !gather)
+        return fail(PW_EINVAL, "pw_replay_sample: out_idx, out_obs, out_act, out_rew, out_next_obs and out_done are all null (nothing to write)");
+    if (st->capacity < 1 || st->capacity > ((int64_t)1 << 32))
+        return fail(PW_EINVAL, "pw_replay_sample: st->capacity must be in [1, 2^32] (the draw scales one 32-bit word)");
+    if ((reinterpret_cast<uintptr_t>(call_dev) | reinterpret_cast<uintptr_t>(len_dev) | reinterpret_cast<uintptr_t>(out_idx)) & 7)
+        return fail(PW_EINVAL, "pw_replay_sample: call_dev, len_dev and out_idx must be 8-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!gather) {  // the draw alone: ReplayBuffer.make_index
+        hipLaunchKernelGGL(pw_replay_draw_kernel, dim3(grid_blocks((size_t)b, 1024)), dim3(256), 0, s, *st, seed, call_dev, len_dev, b, out_idx);
+        PW_HIP_CHECK(hipGetLastError());
+        return PW_OK;
+    }
+    if (st->obs_dim < 2) return fail(PW_EINVAL, "pw_replay_sample: st->obs_dim must be >= 2");
+    if (st->act_heads < 0 || st->act_heads > 2 || (st->act_heads == 2 && (st->head_width[0] < 0 || st->head_width[1] < 1)))
+        return fail(PW_EINVAL, "pw_replay_sample: bad st->act_heads / st->head_width");
+    if (st->state_rows) {  // STATE ring: the rows are rebuilt from the drawn slot's states and landmarks
+        if (int rc = state_ring_ok(st, "pw_replay_sample")) return rc;
+        if ((reinterpret_cast<uintptr_t>(out_obs) | reinterpret_cast<uintptr_t>(out_next_obs)) & 7)
+            return fail(PW_EINVAL, "pw_replay_sample (STATE ring): out_obs / out_next_obs must be 8-byte aligned");
+        const size_t units = (size_t)b * st->num_agents * (st->obs_dim / 2);
+        hipLaunchKernelGGL(pw_replay_sample_state_kernel, dim3(grid_blocks(units, 8192)), dim3(256), 0, s, *st, seed, call_dev, len_dev, b,
+                           out_idx, out_obs, out_act, out_rew, out_next_obs, out_done);
+        PW_HIP_CHECK(hipGetLastError());
+        return PW_OK;
+    }
+    const size_t total = (size_t)b * st->num_agents * st->obs_dim;
+    hipLaunchKernelGGL(pw_replay_sample_kernel, dim3(grid_blocks(total, 8192)), dim3(256), 0, s, *st, seed, call_dev, len_dev, b, out_idx,
+                       out_obs, out_act, out_rew, out_next_obs, out_done);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }

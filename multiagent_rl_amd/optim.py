@@ -54,10 +54,18 @@ class FusedAdam(torch.optim.Optimizer):
     ``t = t * (1 - tau) + p * tau`` rides in the same launch, on the new ``p``.  Parameters whose ``.grad`` is ``None`` take no
     part in the norm or the Adam step and get no state, as in torch; their targets still move, as the stock ``soft_update``
     moves every target: one ``pw_soft_update`` launch for them, before the group's own.  ``last_total_norm``: the gradient norm of the most
-    recent launch as a device scalar (never read back here)."""
+    recent launch as a device scalar (never read back here).
+
+    ``graph_steps=True`` (what a captured update needs, ``multiagent_rl_amd.graph``): the step count of every group also lives in an
+    int64 device cell; ``step()`` launches ``pw_adam_step_dev``, which forms the bias corrections from that cell in the kernel, and then
+    advances the cell with ``pw_counter_add`` -- so a replayed ``step()`` takes step t + 1, not step t again.  The host-side
+    ``state[p]['step']`` advances in ``step()`` as always (also while a graph is being captured, when nothing runs on the device);
+    ``note_graph_steps(n)`` advances it for ``n`` replays.  ``state_dict()`` is unchanged: it still loads into ``torch.optim.Adam``.  The
+    other hyper-parameters travel as kernel arguments: a captured ``step()`` keeps the ``lr`` / ``betas`` / ``eps`` / ``weight_decay`` it
+    was captured with."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_norm=None, targets=None, tau=None,
-                 amsgrad=False, maximize=False):
+                 amsgrad=False, maximize=False, graph_steps=False):
         if amsgrad or maximize:
             raise ValueError('FusedAdam serves neither amsgrad nor maximize')
         # the defaults of the installed torch's Adam, key for key: a state_dict of either loads into the other
@@ -87,6 +95,28 @@ class FusedAdam(torch.optim.Optimizer):
         self._norms = {}
         self.last_total_norm = None
         self._lib = None
+        self.graph_steps = bool(graph_steps)
+        self._step_cells = {}    # group index -> int64 device cell: the step the group's NEXT launch takes
+
+    def sync_step_cells(self):
+        """Rewrite the device step cells from the host-side ``step`` (after ``load_state_dict``, or after ``step`` was set by hand)."""
+        for gi, group in enumerate(self.param_groups):
+            cell = self._step_cells.get(gi)
+            steps = [float(self.state[p]['step']) for p in group['params'] if len(self.state.get(p, {}))]
+            if cell is not None and steps:
+                cell.fill_(int(steps[0]) + 1)
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self.sync_step_cells()
+
+    def note_graph_steps(self, n=1):
+        """Host bookkeeping for ``n`` ``step()`` calls that ran inside a replayed graph (the device cells have advanced there)."""
+        for group in self.param_groups:
+            for p in group['params']:
+                st = self.state.get(p)
+                if st is not None and len(st):
+                    st['step'] = st['step'] + n
 
     def __setstate__(self, state):
         super().__setstate__(state)
@@ -157,11 +187,20 @@ class FusedAdam(torch.optim.Optimizer):
             if norm is None or norm.device != device:
                 norm = self._norms[gi] = torch.zeros((), dtype=torch.float32, device=device)
             beta1, beta2 = group['betas']
-            _lib.check(self._lib.pw_adam_step(table, len(rows), step, float(group['lr']), float(beta1), float(beta2),
-                                              float(group['eps']), float(group['weight_decay']),
-                                              self.max_norm if self.max_norm is not None else 0.0,
-                                              self.tau if self.tau is not None else 0.0,
-                                              C.c_void_p(norm.data_ptr()), _stream(device)))
+            hyper = (float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay']),
+                     self.max_norm if self.max_norm is not None else 0.0, self.tau if self.tau is not None else 0.0,
+                     C.c_void_p(norm.data_ptr()), _stream(device))
+            if self.graph_steps:
+                cell = self._step_cells.get(gi)
+                if cell is None or cell.device != device:
+                    if torch.cuda.is_current_stream_capturing():   # a captured fill would reset the cell at every replay
+                        raise RuntimeError('FusedAdam(graph_steps=True): take one step() eagerly before capturing (it creates the '
+                                           'Adam state and the device step cell; created inside a capture they would be reset by every replay)')
+                    cell = self._step_cells[gi] = torch.full((1,), step, dtype=torch.int64, device=device)
+                _lib.check(self._lib.pw_adam_step_dev(table, len(rows), C.c_void_p(cell.data_ptr()), *hyper))
+                _lib.check(self._lib.pw_counter_add(C.c_void_p(cell.data_ptr()), 1, 0, _stream(device)))
+            else:
+                _lib.check(self._lib.pw_adam_step(table, len(rows), step, *hyper))
             for st in steps:
                 if isinstance(st['step'], torch.Tensor):
                     st['step'] += 1
@@ -215,17 +254,21 @@ def soft_update(target, source, tau):
         launch(batch)
 
 
-def fuse_optimizers(trainer):
+def fuse_optimizers(trainer, graph_steps=False):
     """``trainer.actor_optimizer`` / ``trainer.critic_optimizer`` -> ``FusedAdam`` with the hyper-parameters and state of the
     optimisers they replace; ``trainer.soft_update`` -> the one-launch ``soft_update``.  The Trainer's own ``clip_grad_norm_``
-    calls stay torch's (the Trainer is not modified), so the kernels' clip is off here (``max_norm=None``).  Returns the two
-    optimisers."""
+    calls stay torch's (the Trainer is not modified), so the kernels' clip is off here (``max_norm=None``).  ``graph_steps``:
+    ``FusedAdam``'s switch of that name.  Returns the two optimisers."""
     out = []
     for name in ('actor_optimizer', 'critic_optimizer'):
         old = getattr(trainer, name)
+        if isinstance(old, FusedAdam):   # the Trainer took the switch itself (the example learner's fused_optimizer)
+            old.graph_steps = old.graph_steps or bool(graph_steps)
+            out.append(old)
+            continue
         if not isinstance(old, torch.optim.Adam):
             raise ValueError('%s is %s: accelerate_trainer(optimizer=True) replaces torch.optim.Adam' % (name, type(old).__name__))
-        new = FusedAdam.from_adam(old)
+        new = FusedAdam.from_adam(old, graph_steps=graph_steps)
         setattr(trainer, name, new)
         out.append(new)
     trainer.soft_update = soft_update

@@ -133,11 +133,17 @@ class FusedActor(object):
         self.defer_step_advance = False  # graph mode: the caller advances _step_dev (pw_rollout_tail)
 
     @torch.no_grad()
-    def refresh(self):
+    def refresh(self, in_place=False):
+        """Re-snapshot the actor's weights.  Default: new tensors (``cat`` / ``contiguous`` / a new packed image).  ``in_place=True``:
+        the same values written INTO the existing buffers (``copy_`` / ``torch.cat(out=...)`` / the pack launch onto the existing
+        image), so every address a captured launch holds stays valid and a captured ``refresh(in_place=True)`` feeds the captured
+        forward; shapes are fixed after construction, and a changed one raises."""
         a = self.actor
         lin1, lstm = a.dense1.module, a.bilstm
         two = type(a.out_dim) is list  # MultiDiscrete actor: two heads on the same BiLSTM output
         heads = [a.dense2_1.module, a.dense2_2.module] if two else [a.dense2.module]
+        if in_place:
+            return self._refresh_in_place(lin1, lstm, heads)
         self.heads = tuple(int(h.out_features) for h in heads)
         assert lstm.hidden_size == 32 and lstm.bidirectional and lstm.num_layers == 1 and sum(self.heads) <= 16
         dev = lin1.weight.device
@@ -157,6 +163,27 @@ class FusedActor(object):
         cp = lambda t: self._C.c_void_p(t.data_ptr())  # noqa: E731
         self._lib_mod.check(self.lib.pw_actor_front_pack(cp(self.w1), cp(self.wih), D, cp(self.frag),
                                                          self._C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+    def _refresh_in_place(self, lin1, lstm, heads):
+        srcs = dict(w1=lin1.weight, b1=lin1.bias, whh_f=lstm.weight_hh_l0, whh_r=lstm.weight_hh_l0_reverse)
+        cats = dict(wih=[lstm.weight_ih_l0, lstm.weight_ih_l0_reverse], w2=[h.weight for h in heads], b2=[h.bias for h in heads])
+        want = dict((k, tuple(v.shape)) for k, v in srcs.items())
+        want.update((k, (sum(t.shape[0] for t in v),) + tuple(v[0].shape[1:])) for k, v in cats.items())
+        for k, shape in want.items():
+            have = getattr(self, k)
+            if tuple(have.shape) != shape or have.device != lin1.weight.device or tuple(int(h.out_features) for h in heads) != self.heads:
+                raise ValueError('FusedActor.refresh(in_place=True): %s is %r on %s, the actor now has %r on %s -- shapes are fixed after '
+                                 'construction (build a new FusedActor)' % (k, tuple(have.shape), have.device, shape, lin1.weight.device))
+        for k, v in srcs.items():
+            getattr(self, k).copy_(v.detach())
+        for k, v in cats.items():
+            torch.cat([t.detach() for t in v], 0, out=getattr(self, k))
+        self.wih_t.copy_(self.wih.t())
+        H4 = 4 * lstm.hidden_size   # bih = [b_ih + b_hh | the reverse direction's]: each half summed into its place
+        torch.add(lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), out=self.bih[:H4])
+        torch.add(lstm.bias_ih_l0_reverse.detach(), lstm.bias_hh_l0_reverse.detach(), out=self.bih[H4:])
+        cp = lambda t: self._C.c_void_p(t.data_ptr())  # noqa: E731
+        self._lib_mod.check(self.lib.pw_actor_front_pack(cp(self.w1), cp(self.wih), self.w1.shape[1], cp(self.frag), self._stream()))
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -345,7 +372,7 @@ class FusedExploration(object):
         return [eye[0][idx[..., 0]], eye[1][idx[..., 1]]]
 
 
-def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False):
+def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False, graph=False, graph_warmup=3):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -376,9 +403,23 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     rocBLAS's.
 
     The model-learning variant's Trainer (``model_ddpg_gumbel_fix.py``) is served by every switch: with ``targets=True`` the target
-    actor's wrapper returns ``(logits, None)`` and the target critic's ``(q, r)``, as that Trainer unpacks them."""
+    actor's wrapper returns ``(logits, None)`` and the target critic's ``(q, r)``, as that Trainer unpacks them.
+
+    ``graph=True`` (with all four switches; a critic without an attention block needs the first three) replaces ``trainer.optimize`` by a
+    ``multiagent_rl_amd.graph.GraphedUpdate``: ``graph_warmup`` eager updates, then one captured update replayed as one graph launch per
+    call.  The optimisers switch to ``graph_steps`` mode, the target actor's snapshot is refreshed in place inside the captured region,
+    the exploration actor's eagerly after each replay; ``trainer.memory`` must be a ``ReplayBuffer(device_index='counter')``.  What is
+    missing from that configuration is a ``ValueError`` that names it.  Switches a Trainer has already taken itself (the example
+    learner's ``fused_optimizer`` / ``fused_lstm`` / ``fused_attention``) count."""
+    if graph:   # what this call will not put right is refused before anything is patched (and before the GPU is needed)
+        from .graph import missing_for_graph
+        mended = [name for name, on in (('targets', targets), ('optimizer', optimizer), ('lstm', lstm), ('attention', attention)) if on]
+        miss = [m for m in missing_for_graph(trainer) if m.split(':')[0] not in mended]
+        if miss:
+            raise ValueError('accelerate_trainer(graph=True): a captured update needs -- ' + '; '.join(miss))
     fx = FusedExploration(trainer.actor, getattr(trainer, 'action_type', 'Discrete'), seed=seed)
     trainer.get_exploration_action = fx.get_exploration_action
+    trainer._pw_accel = fx
     target_actor = None
     if targets:
         from .critic import fuse_targets
@@ -386,7 +427,7 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
         fx.target_actor = target_actor
     if optimizer:
         from .optim import fuse_optimizers
-        fx.optimizers = fuse_optimizers(trainer)
+        fx.optimizers = fuse_optimizers(trainer, graph_steps=graph)
     if lstm:
         from .lstm import fuse_trainer
         fx.fused_lstms = fuse_trainer(trainer)
@@ -403,10 +444,16 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
             out = inner(*a, **k)
             fx.refresh()
             if target_actor is not None:
-                target_actor.refresh()
+                target_actor.refresh(in_place=graph)   # a captured update holds the snapshot's addresses
             return out
         setattr(trainer, name, wrapped)
-    _wrap('optimize')
+    fx.inner_optimize = getattr(trainer, 'optimize', None)
+    if graph:
+        from .graph import GraphedUpdate
+        fx.graphed = GraphedUpdate(trainer, warmup=graph_warmup)   # ValueError naming what is missing
+        trainer.optimize = fx.graphed
+    else:
+        _wrap('optimize')
     _wrap('load_models')
     return fx
 

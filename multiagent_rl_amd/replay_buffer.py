@@ -49,7 +49,7 @@ def _ptr(t):
 
 class ReplayBuffer(object):
     def __init__(self, size, num_agents=None, obs_dim=None, device=None, act_heads=None, per_agent=None, state_ring=None,
-                 device_index=False):
+                 device_index=False, index_seed=0):
         """size: max number of transitions (``ReplayBuffer(size=1e+6)``, experiments/run.py:20).
         Storage is allocated on the first add (when N and D are known) unless given here.
         ``act_heads``: sizes of the action heads, ``(5,)`` (default) or ``(5, dim_c)``; ``per_agent``: per-agent
@@ -57,11 +57,25 @@ class ReplayBuffer(object):
         ``device_index=True``: ``make_index`` draws the batch's indices ON the device (one ``torch.randint``; uniform with replacement
         like the reference's ``batch_size`` calls of Python's never-seeded ``random.randint``, rls/replay_buffer.py:51-52) and returns
         the int64 tensor ``sample_index`` takes as it is -- 1024 host-side draws, a list and an upload cost a learner ~0.7 ms of every
-        update."""
+        update.
+        ``device_index='counter'`` (what a captured update needs, ``multiagent_rl_amd.graph``): the draw itself is a HIP launch
+        (``pw_replay_sample``) whose two changing inputs live in int64 device cells -- the number of the draw, advanced on the device
+        after every draw, and the ring's length, rewritten (``fill_`` on the current stream) whenever an append, ``clear`` or
+        unpickling changes ``len(self)`` -- so a replayed ``make_index`` / ``sample`` draws afresh from the ring as it is then.  Element
+        e of draw c is a function of (``index_seed``, c, e, length) alone (``include/pworld.h``).  ``make_index(b)`` returns the index
+        tensor (one launch), ``sample(b)`` draws and gathers in one launch.  An empty ring is refused on the host."""
         self._maxsize = int(size)
-        self.device_index = bool(device_index)
+        if device_index == 'counter':
+            if self._maxsize > 1 << 32:
+                raise ValueError("device_index='counter' serves rings of at most 2^32 transitions")
+        elif not isinstance(device_index, (bool, int)):
+            raise ValueError("device_index must be False, True or 'counter', got %r" % (device_index,))
+        self.device_index = 'counter' if device_index == 'counter' else bool(device_index)
+        self.index_seed = int(index_seed) & 0xFFFFFFFFFFFFFFFF
+        self._cells = None       # 'counter' mode: int64 device cells [draw number, length]
+        self._draws0 = 0         # the draw number an unpickled buffer resumes from
         self._next_idx = 0
-        self._len = 0
+        self._len_host = 0
         self._device = None if device is None else torch.device(device)
         self._store = None
         self._lib = None
@@ -84,6 +98,19 @@ class ReplayBuffer(object):
         self.num_agents, self.obs_dim = num_agents, obs_dim
         if num_agents is not None and obs_dim is not None:
             self._allocate(num_agents, obs_dim)
+
+    # every writer of the length (the appends here, the rollout's ring sink, the multi-GPU gather) goes through this setter, so the
+    # device cell of 'counter' mode follows each of them, on the stream the append itself was issued on
+    @property
+    def _len(self):
+        return self._len_host
+
+    @_len.setter
+    def _len(self, value):
+        value = int(value)
+        changed, self._len_host = value != self._len_host, value
+        if changed and self._cells is not None:
+            self._cells[1:].fill_(value)
 
     # -- storage
     def _allocate(self, N, D):
@@ -122,6 +149,42 @@ class ReplayBuffer(object):
         # device copies of _next_idx (hipGraph mode): cell [0] for add_batch(device_cursor=True); add_batch_tail
         # ping-pongs between [0] and [1] (it reads one cell in every workgroup and writes the other)
         self._cursor = torch.zeros(2, dtype=torch.int64, device=dev)
+        if self.device_index == 'counter':
+            self._cells = torch.tensor([self._draws0, self._len_host], dtype=torch.int64).to(dev)
+
+    def use_counter_index(self, index_seed=None):
+        """Switch an existing ring to ``device_index='counter'`` (e.g. the ring a multi-GPU gather made for itself)."""
+        if self._maxsize > 1 << 32:
+            raise ValueError("device_index='counter' serves rings of at most 2^32 transitions")
+        self.device_index = 'counter'
+        if index_seed is not None:
+            self.index_seed = int(index_seed) & 0xFFFFFFFFFFFFFFFF
+        if self._store is not None and self._cells is None:
+            self._cells = torch.tensor([self._draws0, self._len_host], dtype=torch.int64).to(self._device)
+
+    def reset_draws(self, call=0):
+        """'counter' mode: the next draw is number ``call`` (draws repeat from there: they are a function of the number)."""
+        self._draws0 = int(call)
+        if self._cells is not None:
+            self._cells[:1].fill_(self._draws0)
+
+    def _draw(self, batch_size, gather):
+        """One ``pw_replay_sample`` launch + the counter's advance -> (idx [b] int64, the five batch tensors or None)."""
+        self._ensure_device()
+        if self._store is None or self._len_host < 1:
+            raise ValueError("ReplayBuffer: the ring is empty -- nothing to draw from")
+        b, N, D, dev = int(batch_size), self.num_agents, self.obs_dim, self._device
+        idx = torch.empty(b, dtype=torch.int64, device=dev)
+        out = None
+        if gather:
+            rd = (b, N) if self.per_agent else (b,)
+            out = (torch.empty(b, N, D, device=dev), torch.empty(b, N, sum(self.act_heads), device=dev),
+                   torch.empty(rd, device=dev), torch.empty(b, N, D, device=dev), torch.empty(rd, device=dev))
+        outs = [_ptr(t) for t in out] if gather else [None] * 5
+        check(self._lib.pw_replay_sample(C.byref(self._store), self.index_seed, _ptr(self._cells), _ptr(self._cells[1:]), b,
+                                         _ptr(idx), *outs, self._stream()))
+        check(self._lib.pw_counter_add(_ptr(self._cells), 1, 0, self._stream()))
+        return idx, out
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
@@ -146,14 +209,17 @@ class ReplayBuffer(object):
             host = {k: getattr(self, k)[sl].cpu().numpy() for k in ('obs', 'next_obs', 'act', 'rew', 'done') + (('lm',) if self.state_ring else ())}
         return dict(maxsize=self._maxsize, next_idx=self._next_idx, len=self._len, num_agents=self.num_agents,
                     obs_dim=self.obs_dim, act_heads=self.act_heads, per_agent=self.per_agent, planes=host, state_ring=self.state_ring,
-                    device_index=self.device_index)
+                    device_index=self.device_index, index_seed=self.index_seed,
+                    draws=int(self._cells[0].item()) if self._cells is not None else self._draws0)
 
     def __setstate__(self, st):
         self.__init__(st['maxsize'], act_heads=st['act_heads'], per_agent=st['per_agent'])
         self._next_idx, self._len = st['next_idx'], st['len']
         self.num_agents, self.obs_dim = st['num_agents'], st['obs_dim']
         self.state_ring = st.get('state_ring')
-        self.device_index = bool(st.get('device_index', False))
+        di = st.get('device_index', False)
+        self.device_index = 'counter' if di == 'counter' else bool(di)
+        self.index_seed, self._draws0 = int(st.get('index_seed', 0)), int(st.get('draws', 0))
         self._host_state = st['planes']   # uploaded by _ensure_device() on first use (unpickling needs no GPU)
 
     def _ensure_device(self):
@@ -341,6 +407,8 @@ class ReplayBuffer(object):
 
     # -- rls/replay_buffer.py:51-57
     def make_index(self, batch_size):
+        if self.device_index == 'counter':
+            return self._draw(batch_size, gather=False)[0]
         if self.device_index and self._store is not None:
             return torch.randint(0, self._len, (int(batch_size),), dtype=torch.int64, device=self._device)
         return [random.randint(0, self._len - 1) for _ in range(batch_size)]
@@ -367,6 +435,8 @@ class ReplayBuffer(object):
         return self._encode_sample(idxes)
 
     def sample(self, batch_size):
+        if batch_size > 0 and self.device_index == 'counter':
+            return self._draw(batch_size, gather=True)[1]     # draw and gather: one launch
         if batch_size > 0:
             idxes = self.make_index(batch_size)
         else:

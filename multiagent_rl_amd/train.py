@@ -111,7 +111,7 @@ def merge_histories(parts):
 def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discrete', cnt=0, arglist=None, memory=None,
                   out_dir='Models', log=print, chunk=100, max_updates_per_chunk=None, policy_seed=None,
                   per_episode_history=True, gather=None, rank=0, world=1, make_rollout=None, ring='rows',
-                  per_agent_transition=False):
+                  per_agent_transition=False, graph_update=False):
     """``experiments/run.py:run`` for a ``BatchedParticleEnv`` (auto_reset=True).  Runs until ``arglist.num_episodes`` episodes
     have finished (over all envs of this rank), then pickles the history with the reference's keys and saves the models.
     ``gather`` (a ``dist.FullTransitionGather``) switches to the multi-GPU form: every rank rolls out into the gather's wire
@@ -122,8 +122,13 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     one-launch rollout serves (the full observation, L > N, landmark contact on simple_spread, ``policy_form=5``) take ``ring='rows'``:
     their rollout refuses a STATE ring.  ``per_agent_transition=True`` (the BiCNet baseline, ``experiments/run_BIC.py:46,50``): the ring
     holds per-agent ``rew`` / ``done`` planes ([cap, N]) and every chunk is the policy rollout followed by ``memory.add_rollout`` (two
-    launches); single-rank row rings only -- with ``gather`` or ``ring='state'`` it raises.  Returns the history
-    dict (with ``stats``: env-steps, updates, wall time)."""
+    launches); single-rank row rings only -- with ``gather`` or ``ring='state'`` it raises.  ``graph_update=True``: the ring this
+    function creates draws its batches from device cells (``ReplayBuffer(device_index='counter')``) and the learner's ``optimize`` is
+    replaced, after construction, by a ``graph.GraphedUpdate`` (a learner that has installed one itself keeps it): a few eager updates,
+    then one graph launch per update; the learner must be in the configuration that serves (``accelerate_trainer``'s four switches), or
+    the ``ValueError`` says what is missing.  A gather's ring is switched to ``'counter'`` mode here, a ring passed in through ``memory=`` must be in it already; the side-stream
+    appends of a gather stay ordered against the replays by ``wait_ingested`` / ``mark_reads_done``.  ``stats`` gains ``graph_replays``.
+    Returns the history dict (with ``stats``: env-steps, updates, wall time)."""
     from .replay_buffer import ReplayBuffer
     cfg = _default_arglist if arglist is None else arglist
     if action_type not in ('Discrete', 'MultiDiscrete'):
@@ -140,6 +145,8 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     if memory is None and learns:
         if gather is not None:
             memory = gather.memory
+            if graph_update and hasattr(memory, 'use_counter_index'):
+                memory.use_counter_index()
         else:
             heads = tuple(int(h) for h in (env.action_space[0].high + 1)) if action_type == 'MultiDiscrete' else None
             kw = dict(act_heads=heads) if heads else {}
@@ -150,8 +157,23 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
                                           num_adversaries=env.cfg.num_adversaries if env.scenario_name == 'simple_tag' else 0))
             if per_agent_transition:
                 kw['per_agent'] = True
-            memory = ReplayBuffer(int(1e6), N, env.obs_dim, device_index=True, **kw)   # the batch's indices drawn on the device
+            # the batch's indices drawn on the device (graph_update: by a launch that reads the draw number and the length from device cells)
+            memory = ReplayBuffer(int(1e6), N, env.obs_dim, device_index='counter' if graph_update else True, **kw)
     learner = Trainer(actor, critic, memory, action_type=action_type)
+    graphed = None
+    if graph_update and learns:
+        from .graph import GraphedUpdate
+        graphed = learner.optimize if isinstance(getattr(learner, 'optimize', None), GraphedUpdate) else None
+        if graphed is None:
+            fx = getattr(learner, '_pw_accel', None)
+            if fx is None:
+                raise ValueError('train_batched(graph_update=True): the learner has not been through accelerate_trainer (targets=True, '
+                                 'optimizer=True, lstm=True, attention=True): there is no fused target actor to keep in step')
+            for opt in (learner.actor_optimizer, learner.critic_optimizer):
+                if hasattr(opt, 'graph_steps'):
+                    opt.graph_steps = True
+            graphed = fx.graphed = GraphedUpdate(learner)
+            learner.optimize = graphed
     seed = (cnt + 12345678 if policy_seed is None else policy_seed) + rank
     if make_rollout is None:
         from .policy import FusedActor
@@ -222,6 +244,7 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     hist['stats'] = dict(env_steps=ro.env_steps, episodes=s['episodes'], mean_episode_reward=s['mean_episode_reward'],
                          updates=updates, updates_run=updates, updates_owed=updates_owed,
                          updates_skipped=updates_owed - updates if learns else None,
+                         graph_replays=graphed.replays if graphed is not None else 0,
                          wall_s=time.time() - t_begin, num_envs=B, chunk=chunk, world=world)
     if learns and updates < updates_owed:
         log('learner: {} of {} owed updates run (max_updates_per_chunk={}, or the ring was still empty)'.format(
