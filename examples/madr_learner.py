@@ -22,6 +22,10 @@ critic without that block is left as it is.
 (``multiagent_rl_amd.graph.GraphedUpdate``, installed by ``accelerate_trainer(self, targets=True, ..., graph=True)``); it needs the three
 switches above and a ``ReplayBuffer(device_index='counter')``, and says what is missing otherwise.  ``optimize()`` then returns the two
 loss TENSORS of the replay (no read-back per update); ``optimize.losses()`` reads them.
+``Trainer(..., fused_sampling=True, sampling_seed=None)``: both Gumbel-softmax samples of an update (four with two heads) run on the HIP
+kernels, one launch forward and one backward each (``multiagent_rl_amd.sampling.GumbelSampler``), with the library's own noise keyed
+(``sampling_seed``; update number, call site, row) instead of torch's generator -- a graphed run then reproduces an eager one bit for bit.
+The default is ``F.gumbel_softmax``; the B = 1 ``get_exploration_action`` keeps it either way.
 """
 import copy
 import os
@@ -51,9 +55,14 @@ class Trainer(object):
     per_agent = False   # BiCNetTrainer: per-agent rewards / dones [b,N] and a critic that returns [b,N,1]
 
     def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
-                 fused_lstm=False, fused_attention=False, graph_update=False):
+                 fused_lstm=False, fused_attention=False, graph_update=False, fused_sampling=False, sampling_seed=None):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
+        self.sampler = None
+        if fused_sampling:   # an INSTANCE attribute: a subclass (or a test) that overrides _sample keeps its own on every other instance
+            from multiagent_rl_amd.sampling import GumbelSampler
+            self.sampler = GumbelSampler(seed=sampling_seed, device=self.device)
+            self._sample = self.sampler.sample
         if fused_attention:   # before the deep copies, like fused_lstm
             self._fuse_attention(self.critic)
         if fused_lstm:   # before the deep copies: a class swap survives them, so the target networks are fused too
@@ -141,6 +150,8 @@ class Trainer(object):
                 for tgt, src in ((self.target_actor, self.actor), (self.target_critic, self.critic)):
                     for pt, ps in zip(tgt.parameters(), src.parameters()):
                         pt.mul_(1.0 - TAU).add_(ps, alpha=TAU)
+        if self.sampler is not None:   # the next update's noise: the cell advances on the device, inside a captured update too
+            self.sampler.end_update()
         self.iter += 1
         return loss_actor.detach(), loss_critic.detach()
 

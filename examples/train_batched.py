@@ -22,7 +22,9 @@ soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch
 ``--reference``), ``--fused-lstm`` runs the recurrence of the learner's LSTMs with gradient on the HIP kernels
 (``multiagent_rl_amd.lstm``: the learner's own ``fused_lstm`` switch, or ``accelerate_trainer(.., lstm=True)`` with ``--reference``),
 ``--fused-attention`` runs the attention critic's attention block with gradient on the HIP kernels (``multiagent_rl_amd.attention``: the
-learner's own ``fused_attention`` switch, or ``accelerate_trainer(.., attention=True)`` with ``--reference``).
+learner's own ``fused_attention`` switch, or ``accelerate_trainer(.., attention=True)`` with ``--reference``),
+``--fused-sampling`` runs the learner's Gumbel-softmax samples with gradient on the HIP kernels, with the library's own noise stream
+(``multiagent_rl_amd.sampling``: the learner's own ``fused_sampling`` switch, or ``accelerate_trainer(.., sampling=True)`` with ``--reference``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -80,6 +82,10 @@ def main(argv=None):
                     help="the learner's whole update is captured once and replayed as one graph launch per update "
                          '(multiagent_rl_amd.graph.GraphedUpdate); needs --fused-targets --fused-optimizer --fused-lstm --fused-attention '
                          '(--critic bicnet, which has no attention block: the first three); the ring draws its batches from device cells')
+    ap.add_argument('--fused-sampling', action='store_true',
+                    help="the learner's Gumbel-softmax samples run, forward and backward, on the HIP kernels (madr_learner's "
+                         'fused_sampling switch; with --reference: accelerate_trainer(.., sampling=True)); off by default: the noise is '
+                         "the library's Philox stream keyed (seed; update, call site, row), not torch's generator")
     args = ap.parse_args(argv)
     if args.graph_update:
         need = ['--fused-targets', '--fused-optimizer', '--fused-lstm'] + ([] if args.critic == 'bicnet' else ['--fused-attention'])
@@ -121,7 +127,7 @@ def main(argv=None):
         from madr_learner import CriticNetwork, Trainer
         if args.critic == 'attention':
             from multiagent_rl_amd.critic import CriticNetwork
-    if args.fused_targets or args.fused_optimizer or args.fused_lstm or args.fused_attention:
+    if args.fused_targets or args.fused_optimizer or args.fused_lstm or args.fused_attention or args.fused_sampling:
         from multiagent_rl_amd.policy import accelerate_trainer
         plain_trainer = Trainer
 
@@ -132,6 +138,8 @@ def main(argv=None):
                 k['fused_lstm'] = True
             if args.fused_attention and not args.reference:
                 k['fused_attention'] = True
+            if args.fused_sampling and not args.reference:
+                k['fused_sampling'] = True
             if args.graph_update and not args.reference:
                 k['graph_update'] = True     # madr_learner installs the fused targets and the graphed update itself
                 return plain_trainer(*a, **k)
@@ -139,7 +147,7 @@ def main(argv=None):
             if args.fused_targets or args.reference:
                 accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
                                    lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference,
-                                   graph=args.graph_update)
+                                   graph=args.graph_update, sampling=args.fused_sampling and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

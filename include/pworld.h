@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 116 /* 0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 117 /* 0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -678,6 +678,24 @@ int pw_attention_pool_forward(const float *Y, int64_t b, int32_t N, int32_t H, i
  *   dY_{N-1} += dq = sum_t ds_t Y_t (t ascending): the last step receives its score's gradient as a step and as the query. */
 int pw_attention_pool_backward(const float *dOut, const float *Y, const float *weight, const float *out, int64_t b, int32_t N,
                                int32_t H, int32_t relu, float *dY, void *stream);
+
+/* The learner's Gumbel-softmax sample WITH gradient (csrc/pw_kernels_sample.hpp), one launch each: F.gumbel_softmax(logits, tau, hard)
+ * on logits [rows,n] float32, 1 <= n <= 16, tau > 0, with the library's own noise instead of torch's generator.
+ *   step_eff = step + (step_dev ? *step_dev : 0)   (step_dev: an int64 device cell, read by the kernel -- a replayed launch of a
+ *     captured graph draws new noise when the cell has been advanced, e.g. by pw_counter_add);
+ *   noise(r, o) = log(-log u), u from word (o & 3) of Philox4x32-10 block (o >> 2), counter (r lo, r hi | tag(blk), step_eff lo,
+ *     step_eff hi), key seed, tag(blk) = ((blk & 1) << 31) | ((blk >> 1) << 30): the draw of the actor heads (pw_actor_head), so a
+ *     learner must use another seed than its exploration actor;
+ *   v = (logit - noise) / tau;  idx = the first maximum of v;  soft = softmax(v), maximum subtracted, summed o ascending;
+ *   y [rows,n] = hard ? (onehot(idx) - soft) + soft : soft   (the VALUE of torch's y_hard - y_soft.detach() + y_soft).
+ * soft [rows,n] (what the backward needs), idx [rows] int32 and noise [rows,n] (the values subtracted) are optional: NULL stores
+ * nothing.  A bad n / tau / rows, a null logits or y, a misaligned pointer: PW_EINVAL naming the argument, nothing launched.
+ * One thread per row, no atomics: the same (inputs, seed, step_eff) give the same bits on any stream. */
+int pw_gumbel_st_forward(const float *logits, int64_t rows, int32_t n, float tau, int32_t hard, uint64_t seed, uint64_t step,
+                         const int64_t *step_dev, float *y, float *soft, int32_t *idx, float *noise, void *stream);
+/* dY [rows,n] contiguous and soft as the forward wrote it -> dLogits [rows,n]:
+ *   dLogits_o = soft_o (dY_o - sum_k dY_k soft_k) / tau, k ascending -- the soft sample's gradient, which the hard sample shares. */
+int pw_gumbel_st_backward(const float *dY, const float *soft, int64_t rows, int32_t n, float tau, float *dLogits, void *stream);
 
 #ifdef __cplusplus
 }

@@ -184,6 +184,8 @@ SIGNATURES = {
     'pw_lstm_train_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
     'pw_attention_pool_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     'pw_attention_pool_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
+    'pw_gumbel_st_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6),
+    'pw_gumbel_st_backward': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -10,7 +10,10 @@ must live in device memory:
 * Adam's bias corrections: ``FusedAdam(graph_steps=True)`` -- ``pw_adam_step_dev`` forms them in the kernel from a device step cell (the host
   form would repeat one step number forever);
 * the target actor's packed weights: ``FusedActor.refresh(in_place=True)`` inside the captured region (the default ``refresh`` allocates new
-  tensors, which a captured forward never reads).
+  tensors, which a captured forward never reads);
+* optionally the sampling noise: ``sampling.GumbelSampler`` -- ``pw_gumbel_st_forward`` adds a device cell to its step, and the cell advances
+  inside the captured region (without it the stock ``F.gumbel_softmax`` is captured: torch's generator serves a replay new noise too, but
+  not the noise an eager run would draw).
 
 Served: the configuration in which no vendor RNN call and no stock optimiser is captured -- ``targets``, ``optimizer``, ``lstm`` and
 ``attention`` on (a critic without an attention block, ``BiCNetCritic``, needs the first three), the optimisers in ``graph_steps`` mode, the
@@ -88,6 +91,7 @@ class GraphedUpdate(object):
         self.trainer, self.warmup = trainer, int(warmup)
         fx = trainer._pw_accel
         self._fx, self._target_actor = fx, fx.target_actor
+        self._sampler = getattr(fx, 'owned_sampler', None)
         self._body = getattr(trainer, 'optimize_tensors', None) or fx.inner_optimize
         self.graph, self._out, self._hyper = None, None, None
         self.eager_calls = self.replays = self.captures = 0
@@ -101,6 +105,8 @@ class GraphedUpdate(object):
     def _update(self):
         """One update: the learner's body, then the target actor's packed weights follow the soft update -- in place, in the same region."""
         out = self._body()
+        if self._sampler is not None:          # accelerate_trainer(sampling=True): the noise cell advances inside the region, replay by replay
+            self._sampler.end_update()
         self._target_actor.refresh(in_place=True)
         return out
 

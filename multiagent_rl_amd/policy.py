@@ -372,7 +372,8 @@ class FusedExploration(object):
         return [eye[0][idx[..., 0]], eye[1][idx[..., 1]]]
 
 
-def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False, graph=False, graph_warmup=3):
+def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False, graph=False, graph_warmup=3,
+                       sampling=False, sampling_seed=None):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -410,7 +411,16 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     call.  The optimisers switch to ``graph_steps`` mode, the target actor's snapshot is refreshed in place inside the captured region,
     the exploration actor's eagerly after each replay; ``trainer.memory`` must be a ``ReplayBuffer(device_index='counter')``.  What is
     missing from that configuration is a ``ValueError`` that names it.  Switches a Trainer has already taken itself (the example
-    learner's ``fused_optimizer`` / ``fused_lstm`` / ``fused_attention``) count."""
+    learner's ``fused_optimizer`` / ``fused_lstm`` / ``fused_attention``) count.
+
+    ``sampling=True`` runs the learner's Gumbel-softmax samples on the HIP kernels with gradient (``multiagent_rl_amd.sampling``): a
+    ``GumbelSampler`` becomes ``trainer.gumbel_softmax`` (the reference Trainer's method) and / or ``trainer._sample`` (the example
+    learner's), whichever the trainer has -- one launch forward and one backward per sample instead of ``F.gumbel_softmax``'s dozen
+    kernels -- and its ``end_update()`` runs behind every ``optimize()``; with ``graph=True`` inside the captured region, so that every
+    replay draws new noise.  The noise is the library's own Philox stream keyed by ``sampling_seed`` (default:
+    ``sampling.default_seed(seed)``, never the exploration actor's key), a function of (seed, update number, call site, row, logit): not
+    torch's generator, which is why this switch is opt-in too, and why a graphed run with it reproduces an eager one bit for bit.  A
+    trainer that carries its own sampler (the example learner's ``fused_sampling``) keeps it."""
     if graph:   # what this call will not put right is refused before anything is patched (and before the GPU is needed)
         from .graph import missing_for_graph
         mended = [name for name, on in (('targets', targets), ('optimizer', optimizer), ('lstm', lstm), ('attention', attention)) if on]
@@ -434,6 +444,12 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     if attention:
         from .attention import fuse_trainer as fuse_attention_trainer
         fx.fused_attentions = fuse_attention_trainer(trainer)
+    sampler = None
+    if sampling:
+        from .sampling import install
+        fx.sampler, owned = install(trainer, seed=sampling_seed, exploration_seed=seed)
+        sampler = fx.sampler if owned else None   # a trainer with its own sampler closes its updates itself
+        fx.owned_sampler = sampler
 
     def _wrap(name):
         inner = getattr(trainer, name, None)
@@ -442,6 +458,8 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
 
         def wrapped(*a, **k):
             out = inner(*a, **k)
+            if sampler is not None and name == 'optimize':
+                sampler.end_update()
             fx.refresh()
             if target_actor is not None:
                 target_actor.refresh(in_place=graph)   # a captured update holds the snapshot's addresses
