@@ -7,6 +7,8 @@ raises, loudly.  Build it with ``python -m multiagent_rl_amd.build_native`` (or
 import ctypes as C
 import os
 
+import torch
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'libpworld.so')
 
@@ -217,3 +219,49 @@ def check(rc):
     if rc != 0:
         raise PworldError('libpworld error %d: %s' % (rc, load().pw_last_error().decode()))
     return rc
+
+
+# ---- launch arguments: the one place where torch objects become what a pw_* entry point takes -----------------------------------
+def ptr(t):
+    """A tensor's address (None stays None: the ABI's optional pointers)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device):
+    """The current stream of ``device``: every launch is queued on it."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def step_io(out, names, lead=None, device=None, **direct):
+    """One ``PwStepIO`` from the tensors ``out`` holds under ``names`` (absent or None: the field stays 0), each contiguous, on
+    ``device`` and of leading shape ``lead`` where those are given; ``direct``: fields the caller holds itself (``act_idx=tensor``).
+    The struct keeps addresses only: the caller keeps the tensors alive."""
+    io = PwStepIO()
+    lead = None if lead is None else tuple(lead)
+    for name in names:
+        t = out.get(name)
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous' % name)
+        if device is not None and t.device != device:
+            raise ValueError('%s is on %s, the launch on %s' % (name, t.device, device))
+        if lead is not None and tuple(t.shape[:len(lead)]) != lead:
+            raise ValueError('%s must be [%s, ...] (got %r)' % (name, ', '.join(str(x) for x in lead), tuple(t.shape)))
+        setattr(io, name, t.data_ptr())
+    for name, t in direct.items():
+        setattr(io, name, None if t is None else t.data_ptr())
+    return io
+
+
+def check_f32(t, what, family, anchor=None, other=None):
+    """What every kernel with gradient asks of a tensor: on the GPU (``family``: who says so, and what to use instead), on ``anchor``
+    (the device of ``other``, the launch's first tensor) where given, float32, contiguous."""
+    if t.device.type != 'cuda':
+        raise RuntimeError('%s is on %s: %s' % (what, t.device, family))
+    if anchor is not None and t.device != anchor:
+        raise RuntimeError('%s is on %s, %s on %s' % (what, t.device, other, anchor))
+    if t.dtype != torch.float32:
+        raise RuntimeError('%s must be float32 (got %s)' % (what, t.dtype))
+    if not t.is_contiguous():
+        raise RuntimeError('%s must be contiguous' % what)

@@ -18,8 +18,6 @@ The critic of the model-learning variant (``critic.ModelCriticNetwork``: the sam
 What every critic of the family shares lives here too, once, and ``critic.py`` imports it (this module imports only ``_lib``): the trunk
 ``lstm_trunk``, the stock attention expression ``attend`` and the structural classifier ``critic_form``.
 """
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -35,16 +33,7 @@ MAX_STEPS = 64    # the longest agent axis served (pw_critic_forward's bound)
 HANDED_BACK = ()
 
 
-def _check(t, what, device=None):
-    if t.device.type != 'cuda':
-        raise RuntimeError('%s is on %s: the attention kernels run on the GPU (no CPU fallback; unfuse_attention restores the stock '
-                           'expression)' % (what, t.device))
-    if device is not None and t.device != device:
-        raise RuntimeError('%s is on %s, Y on %s' % (what, t.device, device))
-    if t.dtype != torch.float32:
-        raise RuntimeError('%s must be float32 (got %s)' % (what, t.dtype))
-    if not t.is_contiguous():
-        raise RuntimeError('%s must be contiguous' % what)
+FAMILY = 'the attention kernels run on the GPU (no CPU fallback; unfuse_attention restores the stock expression)'
 
 
 def _shape(Y):
@@ -56,19 +45,15 @@ def _shape(Y):
     return b, N
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 # ---- the overridable pieces: the two launches.  A CPU test replaces them with torch stand-ins of the same signature. ------------
 def launch_forward(Y, relu, keep):
     """Y [b,N,64] contiguous -> (out [b,64], weight [b,N] or None when not ``keep``): one ``pw_attention_pool_forward``."""
     b, N = _shape(Y)
-    _check(Y, 'Y')
+    _lib.check_f32(Y, 'Y', FAMILY)
+    p = _lib.ptr
     out = torch.empty((b, HIDDEN), dtype=torch.float32, device=Y.device)
     weight = torch.empty((b, N), dtype=torch.float32, device=Y.device) if keep else None
-    _lib.check(_lib.load().pw_attention_pool_forward(_p(Y), b, N, HIDDEN, int(bool(relu)), _p(out), _p(weight),
-                                                     C.c_void_p(torch.cuda.current_stream(Y.device).cuda_stream)))
+    _lib.check(_lib.load().pw_attention_pool_forward(p(Y), b, N, HIDDEN, int(bool(relu)), p(out), p(weight), _lib.stream(Y.device)))
     return out, weight
 
 
@@ -76,14 +61,15 @@ def launch_backward(dOut, Y, weight, out, relu):
     """dOut [b,64] contiguous, Y as given to and weight, out as returned by ``launch_forward`` -> dY [b,N,64]: one
     ``pw_attention_pool_backward``."""
     b, N = _shape(Y)
-    _check(Y, 'Y')
+    _lib.check_f32(Y, 'Y', FAMILY)
+    p = _lib.ptr
     for t, what, shape in ((dOut, 'dOut', (b, HIDDEN)), (weight, 'weight', (b, N)), (out, 'out', (b, HIDDEN))):
-        _check(t, what, Y.device)
+        _lib.check_f32(t, what, FAMILY, Y.device, 'Y')
         if tuple(t.shape) != shape:
             raise ValueError('%s must be %r (got %r)' % (what, shape, tuple(t.shape)))
     dY = torch.empty((b, N, HIDDEN), dtype=torch.float32, device=Y.device)
-    _lib.check(_lib.load().pw_attention_pool_backward(_p(dOut), _p(Y), _p(weight), _p(out), b, N, HIDDEN, int(bool(relu)), _p(dY),
-                                                      C.c_void_p(torch.cuda.current_stream(Y.device).cuda_stream)))
+    _lib.check(_lib.load().pw_attention_pool_backward(p(dOut), p(Y), p(weight), p(out), b, N, HIDDEN, int(bool(relu)), p(dY),
+                                                      _lib.stream(Y.device)))
     return dY
 
 

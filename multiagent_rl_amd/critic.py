@@ -25,6 +25,7 @@ two critics it wraps is read off the structure: ``dense2`` is a ``TimeDistribute
 import torch
 import torch.nn as nn
 
+from . import _lib
 from .attention import attend, critic_form, lstm_trunk
 from .policy import FusedActor, TimeDistributed
 from .policy import accelerate_trainer  # noqa: F401  (the one entry point; ``targets=True`` uses the classes below)
@@ -98,9 +99,7 @@ class FusedCritic(object):
     for index actions of shape ``[b,N,2]``."""
 
     def __init__(self, critic, heads=None):
-        import ctypes as C
-        from . import _lib
-        self._C, self._lib_mod, self.lib = C, _lib, _lib.load()
+        self.lib = _lib.load()
         self.critic = critic
         self.heads = None if heads is None else tuple(int(h) for h in heads)
         form, widths = critic_form(critic)
@@ -171,15 +170,14 @@ class FusedCritic(object):
                 if r.numel() != b or d.numel() != b:
                     raise ValueError('rew and done must hold one number per batch row')
             y = torch.empty(shape, dtype=torch.float32, device=self.device)
-        p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
-        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        p, stream = _lib.ptr, _lib.stream(self.device)
         if self.model:   # the second head only where it is asked for: the target critic's launch stores no reward prediction
             rp = torch.empty(shape, dtype=torch.float32, device=self.device) if want_reward else None
-            self._lib_mod.check(self.lib.pw_critic_forward_model(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d),
-                                                                 float(gamma), p(q), p(rp), p(y), stream))
+            _lib.check(self.lib.pw_critic_forward_model(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d),
+                                                        float(gamma), p(q), p(rp), p(y), stream))
             return q, y, rp
         entry = self.lib.pw_critic_forward_steps if self.per_step else self.lib.pw_critic_forward
-        self._lib_mod.check(entry(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d), float(gamma), p(q), p(y), stream))
+        _lib.check(entry(p(x), p(idx), p(vec), n0, n1, *[p(t) for t in ps], b, N, D, p(r), p(d), float(gamma), p(q), p(y), stream))
         return q, y
 
     def q(self, obs, act):

@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-from ._lib import PwStepIO, check
+from ._lib import check, ptr
 
 
 def shard_env_ids(rank, world, envs_per_rank):
@@ -118,28 +118,23 @@ class SampledTransitionGather(object):
         sel_e = torch.randint(0, self.B, (self.R,), generator=self._gen, dtype=torch.int32, device=self.device)
         return sel_t, sel_e
 
+    def _chunk_io(self, out, actions):
+        """The chunk as the pack kernels read it: [T, B, ...] planes on the actions' device."""
+        if out.get('obs') is None or out.get('rew_shared') is None:
+            raise ValueError('SampledTransitionGather: the chunk outputs need obs and rew_shared')
+        return _lib.step_io(out, ('obs', 'rew_shared', 'final_obs', 'terminal'), lead=(actions.shape[0], self.B), device=actions.device,
+                            act_idx=actions)
+
     def _pack(self, out, actions, sel_t, sel_e, rows):
-        lib = _lib.load()
-        io = PwStepIO()
-        io.act_idx = actions.data_ptr()
-        io.obs = out['obs'].data_ptr()
-        io.rew_shared = out['rew_shared'].data_ptr()
-        if out.get('final_obs') is not None:
-            io.final_obs = out['final_obs'].data_ptr()
-        if out.get('terminal') is not None:
-            io.terminal = out['terminal'].data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        check(lib.pw_pack_transitions(C.byref(io), self.B, self.N, self.D, C.c_void_p(sel_t.data_ptr()),
-                                      C.c_void_p(sel_e.data_ptr()), self.R, C.c_void_p(rows.data_ptr()), stream))
+        io = self._chunk_io(out, actions)
+        check(_lib.load().pw_pack_transitions(C.byref(io), self.B, self.N, self.D, ptr(sel_t), ptr(sel_e), self.R, ptr(rows),
+                                              _lib.stream(self.device)))
 
     def _ingest(self, rows):
-        m = self.memory
-        lib = _lib.load()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        n = rows.shape[0]
-        check(lib.pw_replay_add_packed(C.byref(m._store), m._next_idx, n, C.c_void_p(rows.data_ptr()), stream))
-        m._next_idx = (m._next_idx + n) % m._maxsize
-        m._len = min(m._len + n, m._maxsize)
+        m, n = self.memory, rows.shape[0]
+        start = m.claim(n, self.N, self.D, self.device)
+        check(_lib.load().pw_replay_add_packed(C.byref(m._store), start, n, ptr(rows), _lib.stream(self.device)))
+        m._advance(n)
 
     # -- the exchange
     def _complete(self):
@@ -206,25 +201,13 @@ class SampledTransitionGather(object):
                 self._ingest(rows_in)
             self._pack(out, actions, sel_t, sel_e, rows_out)
             return
-        lib = _lib.load()
-        io = PwStepIO()
-        io.act_idx = actions.data_ptr()
-        io.obs = out['obs'].data_ptr()
-        io.rew_shared = out['rew_shared'].data_ptr()
-        if out.get('final_obs') is not None:
-            io.final_obs = out['final_obs'].data_ptr()
-        if out.get('terminal') is not None:
-            io.terminal = out['terminal'].data_ptr()
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        m = self.memory
-        n_in = 0 if rows_in is None else rows_in.shape[0]
-        check(lib.pw_exchange(C.byref(m._store) if n_in else None, m._next_idx if n_in else 0, n_in,
-                              C.c_void_p(rows_in.data_ptr()) if n_in else None, C.byref(io), self.B, self.N, self.D,
-                              C.c_void_p(sel_t.data_ptr()), C.c_void_p(sel_e.data_ptr()), self.R,
-                              C.c_void_p(rows_out.data_ptr()), stream))
+        io = self._chunk_io(out, actions)
+        m, n_in = self.memory, (0 if rows_in is None else rows_in.shape[0])
+        start = m.claim(n_in, self.N, self.D, self.device) if n_in else 0
+        check(_lib.load().pw_exchange(C.byref(m._store) if n_in else None, start, n_in, ptr(rows_in) if n_in else None, C.byref(io),
+                                      self.B, self.N, self.D, ptr(sel_t), ptr(sel_e), self.R, ptr(rows_out), _lib.stream(self.device)))
         if n_in:
-            m._next_idx = (m._next_idx + n_in) % m._maxsize
-            m._len = min(m._len + n_in, m._maxsize)
+            m._advance(n_in)
 
     def finish(self):
         if self.side is None:
@@ -248,6 +231,89 @@ class _HostStagedRecv(object):
     def wait(self):
         self.work.wait()
         self.dst.copy_(self.host, non_blocking=True)
+
+
+_F32, _I32, _U8 = torch.float32, torch.int32, torch.uint8
+
+
+def _check_obs0(g, obs0):
+    assert obs0.is_contiguous() and obs0.dtype == torch.float32 and tuple(obs0.shape) == (g.B, g.N, g.D)
+
+
+class _Wire(object):
+    """One wire format of ``FullTransitionGather``: its block struct (``Struct``), the entry points that append a block to the ring
+    (``append``) and write a chunk's start into it (``begin``, or None), whether the observation rows stay on the sender (``keeps_obs``:
+    only their first columns travel), the axes ``side['act']`` has behind [T, B, N] (``act_tail``) and its typed ``fields``: name = the
+    layout's offset member -> (shape, dtype), a letter being the gather's attribute of that name and F the layout's F (at least 0).
+    ``layout`` fills a ``Struct``, ``finalize`` condenses a chunk into its block, ``ring`` gives the ReplayBuffer keyword arguments of the
+    learner rank's ring."""
+    begin, keeps_obs, act_tail = None, True, ()
+    ring = staticmethod(lambda g: {})
+
+
+class _RowsWire(_Wire):
+    """``pw_chunk_wire``: the rows travel as the rollout wrote them (any scenario with one action head)."""
+    Struct, append, keeps_obs = _lib.PwChunkWire, 'pw_replay_add_wire', False
+    fields = dict(obs0=(('B', 'N', 'D'), _F32), obs=(('T', 'B', 'N', 'D'), _F32), final_rows=(('F', 'B', 'N', 'D'), _F32),
+                  rew_shared=(('T', 'B'), _F32), act=(('T', 'B', 'N'), _U8), fin_slot=(('T', 'B'), _U8))
+
+    @staticmethod
+    def layout(g, lay):
+        return _lib.load().pw_chunk_wire_layout(g.T, g.B, g.N, g.D, g.max_episode_len, C.byref(lay))
+
+    @staticmethod
+    def finalize(g, block, obs0):
+        _check_obs0(g, obs0)
+        return _lib.load().pw_chunk_wire_finalize(C.byref(g.lay), ptr(block), ptr(obs0), ptr(g.side['final_obs']), ptr(g.side['terminal']),
+                                                  ptr(g.side['act']), _lib.stream(g.device))
+
+
+class _StateWire(_Wire):
+    """``pw_state_wire``: {vel, pos} per agent and step, the landmarks once per episode; the root rebuilds the rows."""
+    Struct, append, begin = _lib.PwStateWire, 'pw_replay_add_state_wire', 'pw_state_wire_begin'
+    fields = dict(state0=(('B', 'N', 4), _F32), state=(('T', 'B', 'N', 4), _F32), final_state=(('F', 'B', 'N', 4), _F32),
+                  lm=(('F+1', 'B', 'L', 2), _F32), ep0=(('B',), _I32), rew_shared=(('T', 'B'), _F32), act=(('T', 'B', 'N'), _U8),
+                  epi=(('T', 'B'), _U8))
+
+    @staticmethod
+    def layout(g, lay):
+        return _lib.load().pw_state_wire_layout_scn(_lib.SCENARIOS[g.scenario], g.T, g.B, g.N, g.L, g.A, g.max_episode_len, C.byref(lay))
+
+    @staticmethod
+    def finalize(g, block, obs0):   # obs0 is already in the block as state0 (pw_state_wire_begin)
+        return _lib.load().pw_state_wire_finalize(g.env._h, C.byref(g.lay), ptr(block), ptr(g.side['obs']), ptr(g.side['final_obs']),
+                                                  ptr(g.side['terminal']), ptr(g.side['act']), _lib.stream(g.device))
+
+    @staticmethod
+    def ring(g):   # a STATE ring: the learner rank writes 32 N + 8 L bytes per transition instead of 8 N D; rows rebuilt when sampled
+        return dict(state_ring=dict(scenario=g.scenario, num_landmarks=g.L, num_adversaries=g.A)) if g.ring_kind == 'state' else {}
+
+
+class _RefWire(_Wire):
+    """``pw_ref_wire``: simple_reference's compact rows (the first 8 numbers, goal bytes per episode, both action heads as bytes)."""
+    Struct, append, act_tail = _lib.PwRefWire, 'pw_replay_add_ref_wire', (2,)
+    fields = dict(head0=(('B', 'N', 8), _F32), head=(('T', 'B', 'N', 8), _F32), final_head=(('F', 'B', 'N', 8), _F32),
+                  goal=(('F+1', 'B', 'N'), _U8), comm0=(('B', 'N'), _U8), rew_shared=(('T', 'B'), _F32), act=(('T', 'B', 'N', 2), _U8),
+                  epi=(('T', 'B'), _U8))
+
+    @staticmethod
+    def layout(g, lay):
+        if (g.N, g.D) != (2, 21):
+            raise ValueError('simple_reference: N = 2, D = 21 expected')
+        return _lib.load().pw_ref_wire_layout(g.T, g.B, g.max_episode_len, C.byref(lay))
+
+    @staticmethod
+    def finalize(g, block, obs0):
+        _check_obs0(g, obs0)
+        return _lib.load().pw_ref_wire_finalize(C.byref(g.lay), ptr(block), ptr(obs0), ptr(g.side['obs']), ptr(g.side['final_obs']),
+                                                ptr(g.side['terminal']), ptr(g.side['act']), _lib.stream(g.device))
+
+    @staticmethod
+    def ring(g):
+        return dict(act_heads=(5, _lib.PW_DIM_C))
+
+
+_FORMAT_OF = {f.Struct: f for f in (_RowsWire, _StateWire, _RefWire)}
 
 
 class FullTransitionGather(object):
@@ -284,7 +350,6 @@ class FullTransitionGather(object):
 
     def __init__(self, env, T, rank, world, device, memory=None, group=None, capacity=int(1e6), wire='auto', overlap_ingest=True,
                  ring='rows', transport='auto'):
-        from ._lib import PwChunkWire, PwStateWire
         self.rank, self.world, self.device, self.group = rank, world, torch.device(device), group
         if transport not in ('auto', 'direct', 'host'):
             raise ValueError("transport must be 'auto', 'direct' or 'host'")
@@ -322,7 +387,7 @@ class FullTransitionGather(object):
         if ring == 'state' and not self.state_wire:
             raise ValueError("ring='state' needs state-only wire blocks (a STATE ring is filled from them only)")
         self.ring_kind = ring
-        self.lay = self._layout(_lib.PwRefWire if self.ref_wire else PwStateWire if self.state_wire else PwChunkWire)
+        self.lay = self._layout(self.format.Struct)
         nbytes = self.lay.total_bytes
         dev = self.device
         # THREE slots: chunk k's blocks travel (and, at the root, are appended) while chunk k + 1 rolls out into the next slot and
@@ -343,10 +408,10 @@ class FullTransitionGather(object):
         # the rollout's outputs that do NOT travel as they are (finalize condenses them into the block)
         self.side = dict(final_obs=torch.empty(self.T, B, N, D, dtype=torch.float32, device=dev) if self.lay.F else None,
                          terminal=torch.zeros(self.T, B, dtype=torch.bool, device=dev),
-                         act=torch.zeros((self.T, B, N, 2) if self.ref_wire else (self.T, B, N), dtype=torch.int32, device=dev),
+                         act=torch.zeros((self.T, B, N) + self.format.act_tail, dtype=torch.int32, device=dev),
                          rew=torch.empty(self.T, B, N, dtype=torch.float32, device=dev),
                          done=torch.zeros(self.T, B, N, dtype=torch.bool, device=dev))
-        if self.state_wire or self.ref_wire:   # the rows stay on the sender: only their first four (eight) columns travel
+        if self.format.keeps_obs:   # the rows stay on the sender: only their first four (eight) columns travel
             self.side['obs'] = torch.empty(self.T, B, N, D, dtype=torch.float32, device=dev)
         self._host = self._host_free = None
         if self.transport == 'host' and world > 1:
@@ -370,17 +435,15 @@ class FullTransitionGather(object):
             return self.D == 4 + 2 * self.L + 2 * (self.N - 1) + 2 * (self.N - self.A)
         return name == 'simple_spread' and local and self.D == 4 + 2 * self.L
 
+    @property
+    def format(self):
+        """The wire format, by the two flags ``__init__`` sets once after its validation (``ref_wire``, ``state_wire``: the public
+        record, and all that a stand-in made without ``__init__`` carries).  Every method asks this object."""
+        return _RefWire if getattr(self, 'ref_wire', False) else _StateWire if self.state_wire else _RowsWire
+
     def _layout(self, Struct):
         lay = Struct()
-        if Struct is _lib.PwRefWire:
-            if (self.N, self.D) != (2, 21):
-                raise ValueError('simple_reference: N = 2, D = 21 expected')
-            check(_lib.load().pw_ref_wire_layout(self.T, self.B, self.max_episode_len, C.byref(lay)))
-        elif Struct is _lib.PwStateWire:
-            check(_lib.load().pw_state_wire_layout_scn(_lib.SCENARIOS[self.scenario], self.T, self.B, self.N, self.L, self.A,
-                                                       self.max_episode_len, C.byref(lay)))
-        else:
-            check(_lib.load().pw_chunk_wire_layout(self.T, self.B, self.N, self.D, self.max_episode_len, C.byref(lay)))
+        check(_FORMAT_OF[Struct].layout(self, lay))
         return lay
 
     def _view(self, block, off, shape, dtype):
@@ -392,33 +455,10 @@ class FullTransitionGather(object):
 
     def views(self, block):
         """Typed views of one wire block (a uint8 tensor of ``lay.total_bytes``)."""
-        lay, T, B, N, D = self.lay, self.T, self.B, self.N, self.D
-        if getattr(self, 'ref_wire', False):
-            F = max(lay.F, 0)
-            return dict(head0=self._view(block, lay.head0, (B, N, 8), torch.float32),
-                        head=self._view(block, lay.head, (T, B, N, 8), torch.float32),
-                        final_head=self._view(block, lay.final_head, (F, B, N, 8), torch.float32),
-                        goal=self._view(block, lay.goal, (F + 1, B, N), torch.uint8),
-                        comm0=self._view(block, lay.comm0, (B, N), torch.uint8),
-                        rew_shared=self._view(block, lay.rew_shared, (T, B), torch.float32),
-                        act=self._view(block, lay.act, (T, B, N, 2), torch.uint8),
-                        epi=self._view(block, lay.epi, (T, B), torch.uint8))
-        if self.state_wire:
-            F, L = max(lay.F, 0), self.L
-            return dict(state0=self._view(block, lay.state0, (B, N, 4), torch.float32),
-                        state=self._view(block, lay.state, (T, B, N, 4), torch.float32),
-                        final_state=self._view(block, lay.final_state, (F, B, N, 4), torch.float32),
-                        lm=self._view(block, lay.lm, (F + 1, B, L, 2), torch.float32),
-                        ep0=self._view(block, lay.ep0, (B,), torch.int32),
-                        rew_shared=self._view(block, lay.rew_shared, (T, B), torch.float32),
-                        act=self._view(block, lay.act, (T, B, N), torch.uint8),
-                        epi=self._view(block, lay.epi, (T, B), torch.uint8))
-        return dict(obs0=self._view(block, lay.obs0, (B, N, D), torch.float32),
-                    obs=self._view(block, lay.obs, (T, B, N, D), torch.float32),
-                    final_rows=self._view(block, lay.final_rows, (max(lay.F, 0), B, N, D), torch.float32),
-                    rew_shared=self._view(block, lay.rew_shared, (T, B), torch.float32),
-                    act=self._view(block, lay.act, (T, B, N), torch.uint8),
-                    fin_slot=self._view(block, lay.fin_slot, (T, B), torch.uint8))
+        lay, F = self.lay, max(self.lay.F, 0)
+        dim = lambda x: x if isinstance(x, int) else F if x == 'F' else F + 1 if x == 'F+1' else getattr(self, x)  # noqa: E731
+        return {name: self._view(block, getattr(lay, name), tuple(dim(x) for x in shape), dtype)
+                for name, (shape, dtype) in self.format.fields.items()}
 
     def outputs(self, slot=None):
         """The [T, ...] output dict for this chunk's rollout launch (``FusedActor.rollout(env, T, out)`` /
@@ -428,9 +468,9 @@ class FullTransitionGather(object):
             torch.cuda.current_stream(self.device).wait_event(self._slot_free[slot])   # nothing overwrites them before they ran
             self._slot_free[slot] = None
         v = self.views(self.wire[slot])
-        if self.state_wire:
+        if self.format.begin:
             self._begin(self.wire[slot])
-        out = dict(obs=self.side['obs'] if (self.state_wire or self.ref_wire) else v['obs'], rew_shared=v['rew_shared'],
+        out = dict(obs=self.side['obs'] if self.format.keeps_obs else v['obs'], rew_shared=v['rew_shared'],
                    terminal=self.side['terminal'], act=self.side['act'], rew=self.side['rew'], done=self.side['done'])
         if self.side['final_obs'] is not None:
             out['final_obs'] = self.side['final_obs']
@@ -448,44 +488,20 @@ class FullTransitionGather(object):
     # -- overridable pieces (the CPU gloo test substitutes torch stand-ins for the two HIP launches)
     def _make_memory(self):
         from .replay_buffer import ReplayBuffer
-        if self.ref_wire:
-            return ReplayBuffer(self.capacity, self.N, self.D, device=self.device, act_heads=(5, _lib.PW_DIM_C), device_index=True)
-        if self.ring_kind == 'state':   # the learner rank writes 32 N + 8 L bytes per transition instead of 8 N D; rows rebuilt when sampled
-            return ReplayBuffer(self.capacity, self.N, self.D, device=self.device, device_index=True,
-                                state_ring=dict(scenario=self.scenario, num_landmarks=self.L, num_adversaries=self.A))
-        return ReplayBuffer(self.capacity, self.N, self.D, device=self.device, device_index=True)
-
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return ReplayBuffer(self.capacity, self.N, self.D, device=self.device, device_index=True, **self.format.ring(self))
 
     def _begin(self, block):
         """State-only wire: the chunk's start (state, landmarks, episode numbers) from the env's bound state planes."""
-        check(_lib.load().pw_state_wire_begin(self.env._h, C.byref(self.lay), C.c_void_p(block.data_ptr()), self._stream()))
+        check(getattr(_lib.load(), self.format.begin)(self.env._h, C.byref(self.lay), ptr(block), _lib.stream(self.device)))
 
     def _finalize(self, block, obs0):
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-        if self.ref_wire:
-            assert obs0.is_contiguous() and obs0.dtype == torch.float32 and tuple(obs0.shape) == (self.B, self.N, self.D)
-            check(_lib.load().pw_ref_wire_finalize(C.byref(self.lay), p(block), p(obs0), p(self.side['obs']), p(self.side['final_obs']),
-                                                   p(self.side['terminal']), p(self.side['act']), self._stream()))
-            return
-        if self.state_wire:   # obs0 is already in the block as state0 (pw_state_wire_begin)
-            check(_lib.load().pw_state_wire_finalize(self.env._h, C.byref(self.lay), p(block), p(self.side['obs']),
-                                                     p(self.side['final_obs']), p(self.side['terminal']), p(self.side['act']),
-                                                     self._stream()))
-            return
-        assert obs0.is_contiguous() and obs0.dtype == torch.float32 and tuple(obs0.shape) == (self.B, self.N, self.D)
-        check(_lib.load().pw_chunk_wire_finalize(C.byref(self.lay), p(block), p(obs0), p(self.side['final_obs']),
-                                                 p(self.side['terminal']), p(self.side['act']), self._stream()))
+        check(self.format.finalize(self, block, obs0))
 
     def _ingest(self, block):
-        m = self.memory
-        lib = _lib.load()
-        add = lib.pw_replay_add_ref_wire if self.ref_wire else lib.pw_replay_add_state_wire if self.state_wire else lib.pw_replay_add_wire
-        check(add(C.byref(m._store), m._next_idx, C.byref(self.lay), C.c_void_p(block.data_ptr()), self._stream()))
-        n = self.T * self.B
-        m._next_idx = (m._next_idx + n) % m._maxsize
-        m._len = min(m._len + n, m._maxsize)
+        m, n = self.memory, self.T * self.B
+        start = m.claim(n, self.N, self.D, self.device)
+        check(getattr(_lib.load(), self.format.append)(C.byref(m._store), start, C.byref(self.lay), ptr(block), _lib.stream(self.device)))
+        m._advance(n)
 
     # -- the exchange
     def _post(self, slot):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PwConfig, PwStateLayout, PwStepIO, check
+from ._lib import PwConfig, PwStateLayout, check, ptr
 
 # csrc/pw_kernels_spread_quad.hpp kQuadDrawDepth: steps between the start of a launch (or an episode) and the first episode end whose
 # reset positions the quad kernel has drawn ahead.  Nothing here uses it -- results do not depend on it -- it names the launch lengths at
@@ -64,10 +64,6 @@ class Box(object):
 
     def __repr__(self):
         return 'Box%s' % (self.shape,)
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def make_config(scenario_name, num_envs, num_agents=None, num_landmarks=None, num_adversaries=None,
@@ -160,7 +156,7 @@ class BatchedParticleEnv(object):
             self.act_width = 5 + self.dim_c
         with torch.cuda.device(self.device):
             self._state = torch.zeros(self.lib.pw_state_bytes(h), dtype=torch.uint8, device=self.device)
-        check(self.lib.pw_bind_state(h, _ptr(self._state)))
+        check(self.lib.pw_bind_state(h, ptr(self._state)))
         lay = PwStateLayout()
         check(self.lib.pw_get_state_layout(h, C.byref(lay)))
         self.layout = lay
@@ -200,7 +196,7 @@ class BatchedParticleEnv(object):
 
     # -- helpers
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
 
     def _f32(self, *shape):
         return torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -219,7 +215,7 @@ class BatchedParticleEnv(object):
         if comm is not None or goal is not None:
             cm, gl = self._dev(comm, torch.float32), self._dev(goal, torch.int32)
             assert (cm is None or cm.shape == (B, N, self.dim_c)) and (gl is None or gl.shape == (B, N))
-            check(self.lib.pw_set_comm_state(self._h, _ptr(cm), _ptr(gl), self._stream()))
+            check(self.lib.pw_set_comm_state(self._h, ptr(cm), ptr(gl), self._stream()))
         pos = self._dev(pos, torch.float32)
         vel = torch.zeros(B, N, 2, device=self.device) if vel is None else self._dev(vel, torch.float32)
         lm = self._dev(landmarks, torch.float32)
@@ -230,19 +226,19 @@ class BatchedParticleEnv(object):
             cur = self.get_state()
             es = cur['ep_step'] if es is None else es
             ec = cur['ep_count'] if ec is None else ec
-        check(self.lib.pw_set_state(self._h, _ptr(pos), _ptr(vel), _ptr(lm), _ptr(es), _ptr(ec), self._stream()))
+        check(self.lib.pw_set_state(self._h, ptr(pos), ptr(vel), ptr(lm), ptr(es), ptr(ec), self._stream()))
 
     def get_state(self):
         B, N, L = self.num_envs, self.n, self.num_landmarks
         out = dict(pos=self._f32(B, N, 2), vel=self._f32(B, N, 2), landmarks=self._f32(B, L, 2),
                    ep_step=torch.empty(B, dtype=torch.int32, device=self.device),
                    ep_count=torch.empty(B, dtype=torch.int32, device=self.device))
-        check(self.lib.pw_get_state(self._h, _ptr(out['pos']), _ptr(out['vel']), _ptr(out['landmarks']),
-                                    _ptr(out['ep_step']), _ptr(out['ep_count']), self._stream()))
+        check(self.lib.pw_get_state(self._h, ptr(out['pos']), ptr(out['vel']), ptr(out['landmarks']),
+                                    ptr(out['ep_step']), ptr(out['ep_count']), self._stream()))
         if self.dim_c:
             out['comm'] = self._f32(B, N, self.dim_c)
             out['goal'] = torch.empty(B, N, dtype=torch.int32, device=self.device)
-            check(self.lib.pw_get_comm_state(self._h, _ptr(out['comm']), _ptr(out['goal']), self._stream()))
+            check(self.lib.pw_get_comm_state(self._h, ptr(out['comm']), ptr(out['goal']), self._stream()))
         return out
 
     # -- MultiAgentEnv.reset
@@ -250,22 +246,22 @@ class BatchedParticleEnv(object):
         """Philox-seeded reset of all (or masked-in) envs -> obs [B,N,D]."""
         obs = self._f32(self.num_envs, self.n, self.obs_dim)
         m = self._dev(mask, torch.uint8)
-        check(self.lib.pw_reset(self._h, _ptr(m), _ptr(obs), self._stream()))
+        check(self.lib.pw_reset(self._h, ptr(m), ptr(obs), self._stream()))
         return obs
 
     def observe(self):
         obs = self._f32(self.num_envs, self.n, self.obs_dim)
-        check(self.lib.pw_observe(self._h, _ptr(obs), self._stream()))
+        check(self.lib.pw_observe(self._h, ptr(obs), self._stream()))
         return obs
 
     def reward(self):
         rew = self._f32(self.num_envs, self.n)
         if self.dim_c:  # the communication scenarios have no collisions
             coll = torch.zeros(self.num_envs, self.n, dtype=torch.int64, device=self.device)
-            check(self.lib.pw_reward(self._h, _ptr(rew), None, self._stream()))
+            check(self.lib.pw_reward(self._h, ptr(rew), None, self._stream()))
             return rew, coll
         coll = torch.empty(self.num_envs, self.n, dtype=torch.int64, device=self.device)
-        check(self.lib.pw_reward(self._h, _ptr(rew), _ptr(coll), self._stream()))
+        check(self.lib.pw_reward(self._h, ptr(rew), ptr(coll), self._stream()))
         return rew, coll
 
     # -- MultiAgentEnv.step
@@ -283,27 +279,22 @@ class BatchedParticleEnv(object):
 
     def _io(self, actions, out, T):
         B, N = self.num_envs, self.n
-        io = PwStepIO()
         lead = (B, N) if T is None else (T, B, N)
         actions = torch.as_tensor(actions)
         if actions.is_floating_point():
             a = actions.to(device=self.device, dtype=torch.float32).contiguous()
             assert a.shape == lead + (self.act_width,), 'float actions must be [..., B, N, %d]' % self.act_width
-            io.act_vec = a.data_ptr()
+            act = dict(act_vec=a)
         elif self.dim_c and not self.speaker_listener:  # simple_reference: [..., B, N, 2] = (movement, symbol)
             assert actions.shape == lead + (2,), 'index actions must be [..., B, N, 2] (move, symbol)'
             a = actions.to(device=self.device, dtype=torch.int32)
             a = (a[..., 0].contiguous(), a[..., 1].contiguous())
-            io.act_idx, io.act_comm = a[0].data_ptr(), a[1].data_ptr()
+            act = dict(act_idx=a[0], act_comm=a[1])
         else:
             a = actions.to(device=self.device, dtype=torch.int32).contiguous()
             assert a.shape == lead, 'index actions must be [..., B, N]'
-            io.act_idx = a.data_ptr()
-        for name in ('obs', 'final_obs', 'rew', 'rew_shared', 'done', 'terminal', 'coll'):
-            t = out.get(name)
-            if t is not None:
-                assert t.is_contiguous() and t.device == self.device
-                setattr(io, name, t.data_ptr())
+            act = dict(act_idx=a)
+        io = _lib.step_io(out, ('obs', 'final_obs', 'rew', 'rew_shared', 'done', 'terminal', 'coll'), device=self.device, **act)
         return io, a
 
     def plan_rollout(self, actions, out):
@@ -313,10 +304,10 @@ class BatchedParticleEnv(object):
         T = int(actions.shape[0])
         io, keep = self._io(actions, out, T)
         fn, h, ref = self.lib.pw_rollout, self._h, C.byref(io)
-        stream_of = self._stream
+        stream_of, dev = _lib.stream, self.device
 
         def launch():
-            rc = fn(h, ref, T, stream_of())
+            rc = fn(h, ref, T, stream_of(dev))
             if rc:
                 check(rc)
         launch.keepalive = (io, keep, out)

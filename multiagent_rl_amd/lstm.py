@@ -13,8 +13,6 @@ float32 on the GPU.  Anything else raises: there is no CPU fallback.  Gate activ
 (``csrc/pw_lstm_math.hpp``), so results differ from MIOpen's in the last bits and a seeded run does not reproduce across the
 switch -- which is why it is opt-in everywhere (``accelerate_trainer(trainer, lstm=True)``).
 """
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -29,15 +27,7 @@ def _served(dirs, H):
     return (int(dirs), int(H)) in SERVED
 
 
-def _check(t, what, device=None):
-    if t.device.type != 'cuda':
-        raise RuntimeError('%s is on %s: the LSTM kernels run on the GPU (no CPU fallback; unfuse_lstm restores nn.LSTM)' % (what, t.device))
-    if device is not None and t.device != device:
-        raise RuntimeError('%s is on %s, G on %s' % (what, t.device, device))
-    if t.dtype != torch.float32:
-        raise RuntimeError('%s must be float32 (got %s)' % (what, t.dtype))
-    if not t.is_contiguous():
-        raise RuntimeError('%s must be contiguous' % what)
+FAMILY = 'the LSTM kernels run on the GPU (no CPU fallback; unfuse_lstm restores nn.LSTM)'
 
 
 def _shape(G, w_hh_fw, w_hh_bw):
@@ -60,29 +50,27 @@ def _shape(G, w_hh_fw, w_hh_bw):
 def launch_forward(G, w_hh_fw, w_hh_bw, keep):
     """G [b,N,dirs,4H] contiguous -> (Y [b,N,dirs*H], saved [b,N,dirs,5,H] or None when not ``keep``): one ``pw_lstm_train_forward``."""
     b, N, dirs, H = _shape(G, w_hh_fw, w_hh_bw)
-    _check(G, 'G')
-    _check(w_hh_fw, 'w_hh_fw', G.device)
+    _lib.check_f32(G, 'G', FAMILY)
+    _lib.check_f32(w_hh_fw, 'w_hh_fw', FAMILY, G.device, 'G')
     if w_hh_bw is not None:
-        _check(w_hh_bw, 'w_hh_bw', G.device)
+        _lib.check_f32(w_hh_bw, 'w_hh_bw', FAMILY, G.device, 'G')
     Y = torch.empty((b, N, dirs * H), dtype=torch.float32, device=G.device)
     saved = torch.empty((b, N, dirs, 5, H), dtype=torch.float32, device=G.device) if keep else None
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(_lib.load().pw_lstm_train_forward(p(G), p(w_hh_fw), p(w_hh_bw), b, N, dirs, H, p(Y), p(saved),
-                                                 C.c_void_p(torch.cuda.current_stream(G.device).cuda_stream)))
+    p = _lib.ptr
+    _lib.check(_lib.load().pw_lstm_train_forward(p(G), p(w_hh_fw), p(w_hh_bw), b, N, dirs, H, p(Y), p(saved), _lib.stream(G.device)))
     return Y, saved
 
 
 def launch_backward(dY, saved, w_hh_fw, w_hh_bw):
     """dY [b,N,dirs*H] contiguous, saved as ``launch_forward`` returned it -> dG [b,N,dirs,4H]: one ``pw_lstm_train_backward``."""
     b, N, dirs, _, H = saved.shape
-    _check(dY, 'dY')
-    _check(saved, 'saved', dY.device)
+    _lib.check_f32(dY, 'dY', FAMILY)
+    _lib.check_f32(saved, 'saved', FAMILY, dY.device, 'G')
     if tuple(dY.shape) != (b, N, dirs * H):
         raise ValueError('dY must be %r (got %r)' % ((b, N, dirs * H), tuple(dY.shape)))
     dG = torch.empty((b, N, dirs, 4 * H), dtype=torch.float32, device=dY.device)
-    p = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-    _lib.check(_lib.load().pw_lstm_train_backward(p(dY), p(saved), p(w_hh_fw), p(w_hh_bw), b, N, dirs, H, p(dG),
-                                                  C.c_void_p(torch.cuda.current_stream(dY.device).cuda_stream)))
+    p = _lib.ptr
+    _lib.check(_lib.load().pw_lstm_train_backward(p(dY), p(saved), p(w_hh_fw), p(w_hh_bw), b, N, dirs, H, p(dG), _lib.stream(dY.device)))
     return dG
 
 

@@ -29,19 +29,13 @@ def _refuse(group):
         raise ValueError('FusedAdam serves none of %s (got %s)' % (', '.join(_REFUSED), ', '.join(on)))
 
 
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+FAMILY = 'the fused optimiser runs on the GPU (no CPU fallback)'
 
 
 def _check_tensor(t, what, device=None):
-    if t.device.type != 'cuda':
-        raise RuntimeError('%s is on %s: the fused optimiser runs on the GPU (no CPU fallback)' % (what, t.device))
-    if device is not None and t.device != device:
-        raise RuntimeError('%s is on %s, the group on %s' % (what, t.device, device))
     if t.is_sparse:
         raise RuntimeError('%s is sparse: not served' % what)
-    if t.dtype != torch.float32 or not t.is_contiguous():
-        raise RuntimeError('%s must be a contiguous float32 tensor (got %s, contiguous=%s)' % (what, t.dtype, t.is_contiguous()))
+    _lib.check_f32(t, what, FAMILY, device, 'the group')
 
 
 class FusedAdam(torch.optim.Optimizer):
@@ -189,7 +183,7 @@ class FusedAdam(torch.optim.Optimizer):
             beta1, beta2 = group['betas']
             hyper = (float(group['lr']), float(beta1), float(beta2), float(group['eps']), float(group['weight_decay']),
                      self.max_norm if self.max_norm is not None else 0.0, self.tau if self.tau is not None else 0.0,
-                     C.c_void_p(norm.data_ptr()), _stream(device))
+                     _lib.ptr(norm), _lib.stream(device))
             if self.graph_steps:
                 cell = self._step_cells.get(gi)
                 if cell is None or cell.device != device:
@@ -197,8 +191,8 @@ class FusedAdam(torch.optim.Optimizer):
                         raise RuntimeError('FusedAdam(graph_steps=True): take one step() eagerly before capturing (it creates the '
                                            'Adam state and the device step cell; created inside a capture they would be reset by every replay)')
                     cell = self._step_cells[gi] = torch.full((1,), step, dtype=torch.int64, device=device)
-                _lib.check(self._lib.pw_adam_step_dev(table, len(rows), C.c_void_p(cell.data_ptr()), *hyper))
-                _lib.check(self._lib.pw_counter_add(C.c_void_p(cell.data_ptr()), 1, 0, _stream(device)))
+                _lib.check(self._lib.pw_adam_step_dev(table, len(rows), _lib.ptr(cell), *hyper))
+                _lib.check(self._lib.pw_counter_add(_lib.ptr(cell), 1, 0, _lib.stream(device)))
             else:
                 _lib.check(self._lib.pw_adam_step(table, len(rows), step, *hyper))
             for st in steps:
@@ -239,7 +233,7 @@ def soft_update(target, source, tau):
         tp = (C.c_void_p * n)(*[t.data_ptr() for t, _ in batch])
         sp = (C.c_void_p * n)(*[s.data_ptr() for _, s in batch])
         ne = (C.c_int64 * n)(*[t.numel() for t, _ in batch])
-        _lib.check(lib.pw_soft_update(tp, sp, ne, n, float(tau), _stream(device)))
+        _lib.check(lib.pw_soft_update(tp, sp, ne, n, float(tau), _lib.stream(device)))
     for t, s in pairs:
         if t.numel() == 0:
             continue

@@ -14,10 +14,15 @@ hand-written HIP work is the environment, not the policy GEMMs.
 the same RNG call, but the result stays an int32 index tensor [B,N] in HBM -- no
 ``.cpu().numpy()`` round trip per env-step.
 """
+import ctypes as C
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from . import _lib
 
 
 class TimeDistributed(nn.Module):
@@ -120,10 +125,7 @@ class FusedActor(object):
     """
 
     def __init__(self, actor, seed=0):
-        import ctypes as C
-        from . import _lib
-        self._C, self._lib_mod, self.lib = C, _lib, _lib.load()
-        import os
+        self.lib = _lib.load()
         self.actor, self.seed, self.calls = actor, int(seed), 0
         self.use_mfma_front = not os.environ.get('PW_ACTOR_NO_MFMA')
         self.use_fused = self.use_mfma_front and not os.environ.get('PW_ACTOR_NO_FUSE')
@@ -160,9 +162,7 @@ class FusedActor(object):
         self.device = dev
         D = self.w1.shape[1]
         self.frag = torch.empty(self.lib.pw_actor_front_pack_floats(D), dtype=torch.float32, device=dev)
-        cp = lambda t: self._C.c_void_p(t.data_ptr())  # noqa: E731
-        self._lib_mod.check(self.lib.pw_actor_front_pack(cp(self.w1), cp(self.wih), D, cp(self.frag),
-                                                         self._C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        self._pack_front()
 
     def _refresh_in_place(self, lin1, lstm, heads):
         srcs = dict(w1=lin1.weight, b1=lin1.bias, whh_f=lstm.weight_hh_l0, whh_r=lstm.weight_hh_l0_reverse)
@@ -182,11 +182,14 @@ class FusedActor(object):
         H4 = 4 * lstm.hidden_size   # bih = [b_ih + b_hh | the reverse direction's]: each half summed into its place
         torch.add(lstm.bias_ih_l0.detach(), lstm.bias_hh_l0.detach(), out=self.bih[:H4])
         torch.add(lstm.bias_ih_l0_reverse.detach(), lstm.bias_hh_l0_reverse.detach(), out=self.bih[H4:])
-        cp = lambda t: self._C.c_void_p(t.data_ptr())  # noqa: E731
-        self._lib_mod.check(self.lib.pw_actor_front_pack(cp(self.w1), cp(self.wih), self.w1.shape[1], cp(self.frag), self._stream()))
+        self._pack_front()
+
+    def _pack_front(self):
+        p = _lib.ptr
+        _lib.check(self.lib.pw_actor_front_pack(p(self.w1), p(self.wih), self.w1.shape[1], p(self.frag), self._stream()))
 
     def _stream(self):
-        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return _lib.stream(self.device)
 
     @torch.no_grad()
     def _fused(self, obs, want_h=False, want_logits=False, want_act=False):
@@ -197,14 +200,14 @@ class FusedActor(object):
         n0, n1 = self.heads[0], (self.heads[1] if len(self.heads) > 1 else 0)
         logits = torch.empty(B, N, n0 + n1, dtype=torch.float32, device=self.device) if want_logits else None
         act = torch.empty((B, N, 2) if n1 else (B, N), dtype=torch.int32, device=self.device) if want_act else None
-        p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _lib.ptr
         step_dev = p(self._step_dev) if (self.graph_mode and want_act) else None
-        self._lib_mod.check(self.lib.pw_actor_fused(p(x), p(self.frag), p(self.b1), p(self.bih), p(self.whh_f),
-                                                    p(self.whh_r), p(self.w2), p(self.b2), n0, n1, B, N, D, 1,
-                                                    self.seed, self.calls, step_dev, p(h), p(logits), p(act),
-                                                    self._stream()))
+        _lib.check(self.lib.pw_actor_fused(p(x), p(self.frag), p(self.b1), p(self.bih), p(self.whh_f),
+                                           p(self.whh_r), p(self.w2), p(self.b2), n0, n1, B, N, D, 1,
+                                           self.seed, self.calls, step_dev, p(h), p(logits), p(act),
+                                           self._stream()))
         if step_dev is not None and not self.defer_step_advance:  # captured: the counter advances on the device
-            self._lib_mod.check(self.lib.pw_counter_add(p(self._step_dev), 1, 0, self._stream()))
+            _lib.check(self.lib.pw_counter_add(p(self._step_dev), 1, 0, self._stream()))
         return h, logits, act
 
     @torch.no_grad()
@@ -218,21 +221,21 @@ class FusedActor(object):
                                       'numbers, got D = %d; unset the switch (PW_ACTOR_NO_FUSE=1 alone keeps the three-launch '
                                       'chain, which serves D <= 104)' % D)
         x = obs.reshape(B * N, D).to(torch.float32).contiguous()
-        p = lambda t: self._C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _lib.ptr
         h = torch.empty(B, N, 64, dtype=torch.float32, device=self.device)
         if self.use_mfma_front:
             # dense1 + ReLU + both input projections in ONE launch on the matrix cores (exact f32 MFMA);
             # the hidden activations never leave registers
             g = torch.empty(B * N, 256, dtype=torch.float32, device=self.device)     # [B,N,2,128]
-            self._lib_mod.check(self.lib.pw_actor_front(p(x), p(self.frag), p(self.b1), p(self.bih), B * N, D, p(g),
-                                                        self._stream()))
+            _lib.check(self.lib.pw_actor_front(p(x), p(self.frag), p(self.b1), p(self.bih), B * N, D, p(g),
+                                               self._stream()))
         else:
             # the same in three launches: weight-stationary dense1 + ReLU, then a rocBLAS GEMM
             x1 = torch.empty(B * N, 64, dtype=torch.float32, device=self.device)
-            self._lib_mod.check(self.lib.pw_dense(p(x), p(self.w1), p(self.b1), B * N, D, 64, 1, p(x1), self._stream()))
+            _lib.check(self.lib.pw_dense(p(x), p(self.w1), p(self.b1), B * N, D, 64, 1, p(x1), self._stream()))
             g = torch.addmm(self.bih, x1, self.wih_t)        # [B*N, 256] = [B,N,2,128]
-        self._lib_mod.check(self.lib.pw_bilstm_forward(p(g), p(self.whh_f), p(self.whh_r), B, N, 1, p(h),
-                                                       self._stream()))
+        _lib.check(self.lib.pw_bilstm_forward(p(g), p(self.whh_f), p(self.whh_r), B, N, 1, p(h),
+                                              self._stream()))
         return h
 
     @torch.no_grad()
@@ -240,12 +243,12 @@ class FusedActor(object):
         B, N, _ = h.shape
         logits = torch.empty(B, N, 5, dtype=torch.float32, device=self.device) if want_logits else None
         act = torch.empty(B, N, dtype=torch.int32, device=self.device) if want_act else None
-        p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _lib.ptr
         step_dev = p(self._step_dev) if (self.graph_mode and want_act) else None
-        self._lib_mod.check(self.lib.pw_actor_head(p(h), p(self.w2), p(self.b2), B * N, self.seed, self.calls,
-                                                   step_dev, p(logits), p(act), self._stream()))
+        _lib.check(self.lib.pw_actor_head(p(h), p(self.w2), p(self.b2), B * N, self.seed, self.calls,
+                                          step_dev, p(logits), p(act), self._stream()))
         if step_dev is not None and not self.defer_step_advance:  # captured: the counter advances on the device
-            self._lib_mod.check(self.lib.pw_counter_add(p(self._step_dev), 1, 0, self._stream()))
+            _lib.check(self.lib.pw_counter_add(p(self._step_dev), 1, 0, self._stream()))
         return logits, act
 
     def _one_launch(self, obs):
@@ -282,7 +285,6 @@ class FusedActor(object):
         ``memory`` (a device ``ReplayBuffer``): the transitions go straight into the ring from the same launch;
         ``stats`` = (episode_return [B], finished_sum, finished_count) tensors: the episode bookkeeping too.  With a
         sink, ``out=False`` skips the step outputs altogether (only the ring / statistics are written)."""
-        from ._lib import PwRolloutSink, PwStepIO
         T, B, N = int(num_steps), env.num_envs, env.n
         two = len(self.heads) == 2   # MultiDiscrete actor: simple_reference, act [T,B,N,2] = (movement, symbol); the sink is a two-head ring
         if two:
@@ -305,23 +307,14 @@ class FusedActor(object):
             if tuple(out['act'].shape) != want or out['act'].dtype != torch.int32 or not out['act'].is_contiguous():
                 raise ValueError('rollout: out["act"] must be a contiguous int32 tensor of shape %r (%s actor), got %r %s'
                                  % (want, 'two-head' if two else 'one-head', tuple(out['act'].shape), out['act'].dtype))
-        io = PwStepIO()
-        for name in ('obs', 'final_obs', 'rew', 'rew_shared', 'done', 'terminal'):
-            t = out.get(name)
-            if t is not None:
-                assert t.is_contiguous() and t.shape[0] == T
-                setattr(io, name, t.data_ptr())
-        p = lambda t: None if t is None else self._C.c_void_p(t.data_ptr())  # noqa: E731
+        io = _lib.step_io(out, ('obs', 'final_obs', 'rew', 'rew_shared', 'done', 'terminal'), lead=(T,))
+        p = _lib.ptr
         sink = None
         if memory is not None or stats is not None:
-            sink = PwRolloutSink()
+            sink = _lib.PwRolloutSink()
             if memory is not None:
-                if memory._store is None:
-                    memory._device = self.device if memory._device is None else memory._device
-                    memory._allocate(N, env.obs_dim)
-                assert T * B <= memory._maxsize
-                sink.ring = self._C.addressof(memory._store)
-                sink.ring_start = memory._next_idx
+                sink.ring_start = memory.claim(T * B, N, env.obs_dim, self.device)   # refuses on the host, before the launch
+                sink.ring = C.addressof(memory._store)
             if stats is not None:
                 if getattr(self, '_sink_scratch_key', None) != (B, N):
                     nbytes = self.lib.pw_policy_rollout_scratch_bytes(env._h)
@@ -330,15 +323,14 @@ class FusedActor(object):
                 sink.episode_return, sink.finished_sum, sink.finished_count = (t.data_ptr() for t in stats)
                 sink.scratch = self._sink_scratch.data_ptr()
         step_dev = p(self._step_dev) if self.graph_mode else None
-        self._lib_mod.check(self.lib.pw_policy_rollout(env._h, p(self.frag), p(self.b1), p(self.bih), p(self.whh_f),
-                                                       p(self.whh_r), p(self.w2), p(self.b2), 1, self.seed, self.calls,
-                                                       step_dev, self._C.byref(io), p(out.get('act')), T,
-                                                       None if sink is None else self._C.byref(sink), self._stream()))
+        _lib.check(self.lib.pw_policy_rollout(env._h, p(self.frag), p(self.b1), p(self.bih), p(self.whh_f),
+                                              p(self.whh_r), p(self.w2), p(self.b2), 1, self.seed, self.calls,
+                                              step_dev, C.byref(io), p(out.get('act')), T,
+                                              None if sink is None else C.byref(sink), self._stream()))
         if memory is not None:
-            memory._next_idx = (memory._next_idx + T * B) % memory._maxsize
-            memory._len = min(memory._len + T * B, memory._maxsize)
+            memory._advance(T * B)
         if step_dev is not None and not self.defer_step_advance:
-            self._lib_mod.check(self.lib.pw_counter_add(p(self._step_dev), T, 0, self._stream()))
+            _lib.check(self.lib.pw_counter_add(p(self._step_dev), T, 0, self._stream()))
         self.calls += T
         return out
 

@@ -40,11 +40,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import PwReplayStore, check
-
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+from ._lib import PwReplayStore, check, ptr
 
 
 class ReplayBuffer(object):
@@ -99,8 +95,8 @@ class ReplayBuffer(object):
         if num_agents is not None and obs_dim is not None:
             self._allocate(num_agents, obs_dim)
 
-    # every writer of the length (the appends here, the rollout's ring sink, the multi-GPU gather) goes through this setter, so the
-    # device cell of 'counter' mode follows each of them, on the stream the append itself was issued on
+    # every change of the length (``_advance``, ``clear``, unpickling, a test that positions the cursor by hand) goes through this setter,
+    # so the device cell of 'counter' mode follows each of them, on the stream the append itself was issued on
     @property
     def _len(self):
         return self._len_host
@@ -180,14 +176,14 @@ class ReplayBuffer(object):
             rd = (b, N) if self.per_agent else (b,)
             out = (torch.empty(b, N, D, device=dev), torch.empty(b, N, sum(self.act_heads), device=dev),
                    torch.empty(rd, device=dev), torch.empty(b, N, D, device=dev), torch.empty(rd, device=dev))
-        outs = [_ptr(t) for t in out] if gather else [None] * 5
-        check(self._lib.pw_replay_sample(C.byref(self._store), self.index_seed, _ptr(self._cells), _ptr(self._cells[1:]), b,
-                                         _ptr(idx), *outs, self._stream()))
-        check(self._lib.pw_counter_add(_ptr(self._cells), 1, 0, self._stream()))
+        outs = [ptr(t) for t in out] if gather else [None] * 5
+        check(self._lib.pw_replay_sample(C.byref(self._store), self.index_seed, ptr(self._cells), ptr(self._cells[1:]), b,
+                                         ptr(idx), *outs, self._stream()))
+        check(self._lib.pw_counter_add(ptr(self._cells), 1, 0, self._stream()))
         return idx, out
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+        return _lib.stream(self._device)
 
     def _rows_only(self, who):
         if self.state_ring is not None:
@@ -286,10 +282,34 @@ class ReplayBuffer(object):
         """Copy the host ring position to the device cursor (call before capturing a graph)."""
         self._cursor.fill_(self._next_idx)
 
+    def _advance(self, n):
+        """The cursor after ``n`` appended transitions: the one place that moves it."""
+        self._next_idx = (self._next_idx + n) % self._maxsize
+        self._len = min(self._len + n, self._maxsize)
+
     def note_graph_adds(self, num_transitions):
         """Host bookkeeping for adds that ran inside a replayed graph (device cursor already advanced)."""
-        self._next_idx = (self._next_idx + num_transitions) % self._maxsize
-        self._len = min(self._len + num_transitions, self._maxsize)
+        self._advance(num_transitions)
+
+    def claim(self, n, num_agents=None, obs_dim=None, device=None):
+        """What an appender does before its launch of ``n`` transitions, here or outside this class (the rollout's ring sink, the
+        multi-GPU gathers): the planes of an unpickled ring are uploaded, a ring without storage is allocated for ``[num_agents,
+        obs_dim]`` rows (on ``device`` unless the constructor named one), the shape is held against an allocated ring and ``n`` against
+        the capacity -- all on the host, before anything is launched.  -> the slot the append starts at; ``_advance(n)`` follows the
+        launch."""
+        self._ensure_device()
+        if self._store is None:
+            if num_agents is None or obs_dim is None:
+                raise ValueError('ReplayBuffer: the ring has no storage yet and the appender does not say its [N, D]')
+            if self._device is None and device is not None:
+                self._device = torch.device(device)
+            self._allocate(num_agents, obs_dim)
+        elif num_agents is not None and (num_agents, obs_dim) != (self.num_agents, self.obs_dim):
+            raise _lib.PworldError('ReplayBuffer: shape mismatch -- the ring holds [N, D] = %r rows, the append brings %r'
+                                   % ((self.num_agents, self.obs_dim), (num_agents, obs_dim)))
+        if n > self._maxsize:
+            raise _lib.PworldError('ReplayBuffer: one append of %d transitions into a ring of %d' % (n, self._maxsize))
+        return self._next_idx
 
     def add_batch(self, obs, act_idx, rew_shared, next_obs, final_obs=None, terminal=None, done=None,
                   device_cursor=False, advance_cursor=True):
@@ -300,14 +320,10 @@ class ReplayBuffer(object):
         device memory by the captured launches; the caller accounts for it with ``note_graph_adds``
         (``advance_cursor=False``: the caller advances ``_cursor`` itself, e.g. in pw_rollout_tail)."""
         B, N, D = obs.shape
-        self._ensure_device()
         self._rows_only('add / add_batch')
-        if self._store is None:
-            self._device = obs.device if obs.is_cuda and self._device is None else self._device
-            if self.act_heads is None and act_idx.dim() == 3:
-                raise ValueError('ReplayBuffer: [B,N,2] action indices need act_heads=(5, dim_c) at construction')
-            self._allocate(N, D)
-        assert (N, D) == (self.num_agents, self.obs_dim) and B <= self._maxsize
+        if self.act_heads is None and act_idx.dim() == 3:
+            raise ValueError('ReplayBuffer: [B,N,2] action indices need act_heads=(5, dim_c) at construction')
+        start = self.claim(B, N, D, obs.device if obs.is_cuda else None)
         H = len(self.act_heads)
         assert tuple(act_idx.shape) == ((B, N) if H == 1 else (B, N, H)), 'action indices must be [B,N] or [B,N,2] (two heads)'
         assert tuple(rew_shared.shape) == ((B, N) if self.per_agent else (B,)), 'reward must be [B] ([B,N] per-agent ring)'
@@ -319,17 +335,16 @@ class ReplayBuffer(object):
         act_idx = act_idx.to(device=dev, dtype=torch.int32).contiguous()
         term = None if terminal is None else terminal.to(device=dev).contiguous().view(torch.uint8)
         if device_cursor:
-            check(self._lib.pw_replay_add(C.byref(self._store), 0, _ptr(self._cursor), B, _ptr(obs), _ptr(act_idx),
-                                          _ptr(rew_shared), _ptr(next_obs), _ptr(final_obs), _ptr(term), _ptr(done),
+            check(self._lib.pw_replay_add(C.byref(self._store), 0, ptr(self._cursor), B, ptr(obs), ptr(act_idx),
+                                          ptr(rew_shared), ptr(next_obs), ptr(final_obs), ptr(term), ptr(done),
                                           self._stream()))
             if advance_cursor:
-                check(self._lib.pw_counter_add(_ptr(self._cursor), B, self._maxsize, self._stream()))
+                check(self._lib.pw_counter_add(ptr(self._cursor), B, self._maxsize, self._stream()))
             return
-        check(self._lib.pw_replay_add(C.byref(self._store), self._next_idx, None, B, _ptr(obs), _ptr(act_idx),
-                                      _ptr(rew_shared), _ptr(next_obs), _ptr(final_obs), _ptr(term), _ptr(done),
+        check(self._lib.pw_replay_add(C.byref(self._store), start, None, B, ptr(obs), ptr(act_idx),
+                                      ptr(rew_shared), ptr(next_obs), ptr(final_obs), ptr(term), ptr(done),
                                       self._stream()))
-        self._next_idx = (self._next_idx + B) % self._maxsize
-        self._len = min(self._len + B, self._maxsize)
+        self._advance(B)
 
     def add_batch_tail(self, obs, act_idx, rew_shared, next_obs, final_obs, terminal, episode_return, finished_sum,
                        finished_count, step_counter=None, parity=None):
@@ -339,27 +354,21 @@ class ReplayBuffer(object):
         int64, e.g. the policy's Philox step) is incremented by the same launch; the caller accounts for the
         adds with ``note_graph_adds``.  All tensors must already be float32 / int32 / uint8 device tensors."""
         B, N, D = obs.shape
-        self._ensure_device()
         self._rows_only('add_batch_tail')
-        if self._store is None:
-            self._device = obs.device if self._device is None else self._device
-            self._allocate(N, D)
-        assert (N, D) == (self.num_agents, self.obs_dim) and B <= self._maxsize
+        start = self.claim(B, N, D, obs.device)
         term = terminal.view(torch.uint8)
         for t, dt in ((obs, torch.float32), (next_obs, torch.float32), (rew_shared, torch.float32),
                       (act_idx, torch.int32), (term, torch.uint8), (episode_return, torch.float32)):
             assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+        cur = nxt = None
+        if parity is not None:
+            start, cur, nxt = 0, ptr(self._cursor[parity:]), ptr(self._cursor[1 - parity:])
+        check(self._lib.pw_replay_add_tail(C.byref(self._store), start, cur, nxt, B, ptr(obs), ptr(act_idx),
+                                           ptr(rew_shared), ptr(next_obs), ptr(final_obs), ptr(term), None,
+                                           ptr(episode_return), ptr(finished_sum), ptr(finished_count),
+                                           ptr(step_counter), self._stream()))
         if parity is None:
-            start, cur, nxt = self._next_idx, None, None
-        else:
-            start, cur, nxt = 0, _ptr(self._cursor[parity:]), _ptr(self._cursor[1 - parity:])
-        check(self._lib.pw_replay_add_tail(C.byref(self._store), start, cur, nxt, B, _ptr(obs), _ptr(act_idx),
-                                           _ptr(rew_shared), _ptr(next_obs), _ptr(final_obs), _ptr(term), None,
-                                           _ptr(episode_return), _ptr(finished_sum), _ptr(finished_count),
-                                           _ptr(step_counter), self._stream()))
-        if parity is None:
-            self._next_idx = (self._next_idx + B) % self._maxsize
-            self._len = min(self._len + B, self._maxsize)
+            self._advance(B)
 
     def add_rollout(self, obs0, out, episode_return=None, finished_sum=None, finished_count=None):
         """A whole rollout chunk in ONE launch: ``out`` = the [T, ...] outputs of ``FusedActor.rollout`` /
@@ -367,15 +376,9 @@ class ReplayBuffer(object):
         observation before its first step.  Stored in the order T ``add_batch`` calls would have used; optionally
         does the chunk's episode-return bookkeeping in the same launch.  A ``per_agent`` ring also takes ``out['rew']`` [T,B,N]
         (required) and ``out['done']`` [T,B,N] (bool / uint8; absent = 0) into its per-agent planes."""
-        from ._lib import PwStepIO
         T, B, N, D = out['obs'].shape
-        self._ensure_device()
         self._rows_only('add_rollout')
-        if self._store is None:
-            self._device = obs0.device if self._device is None else self._device
-            self._allocate(N, D)
-        assert (N, D) == (self.num_agents, self.obs_dim) and T * B <= self._maxsize
-        io = PwStepIO()
+        start = self.claim(T * B, N, D, obs0.device)
         names = ('obs', 'final_obs', 'rew_shared', 'terminal')
         if self.per_agent:   # the BiCNet tuple: the chunk's per-agent planes fill rew / done [cap,N]
             if out.get('rew') is None:
@@ -384,11 +387,7 @@ class ReplayBuffer(object):
             done = out.get('done')
             assert done is None or (tuple(done.shape) == (T, B, N) and done.element_size() == 1), "out['done'] must be [T,B,N] bool / uint8"
             names += ('rew', 'done')
-        for name in names:
-            t = out.get(name)
-            if t is not None:
-                assert t.is_cuda and t.is_contiguous()
-                setattr(io, name, t.data_ptr())
+        io = _lib.step_io(out, names, lead=(T, B), device=self.obs.device)   # the planes' own device: it carries its index
         act = out['act']
         assert act.dtype == torch.int32 and act.is_contiguous() and obs0.is_contiguous() and obs0.dtype == torch.float32
         assert tuple(act.shape) == ((T, B, N, 2) if len(self.act_heads) == 2 else (T, B, N)), \
@@ -399,11 +398,10 @@ class ReplayBuffer(object):
                 n = self._lib.pw_replay_add_rollout_scratch_bytes(B)
                 self._roll_scratch, self._roll_scratch_B = torch.zeros(n, dtype=torch.uint8, device=self._device), B
             scratch = self._roll_scratch
-        check(self._lib.pw_replay_add_rollout(C.byref(self._store), self._next_idx, B, T, _ptr(obs0), C.byref(io),
-                                              _ptr(act), _ptr(episode_return), _ptr(finished_sum),
-                                              _ptr(finished_count), _ptr(scratch), self._stream()))
-        self._next_idx = (self._next_idx + T * B) % self._maxsize
-        self._len = min(self._len + T * B, self._maxsize)
+        check(self._lib.pw_replay_add_rollout(C.byref(self._store), start, B, T, ptr(obs0), C.byref(io),
+                                              ptr(act), ptr(episode_return), ptr(finished_sum),
+                                              ptr(finished_count), ptr(scratch), self._stream()))
+        self._advance(T * B)
 
     # -- rls/replay_buffer.py:51-57
     def make_index(self, batch_size):
@@ -427,8 +425,8 @@ class ReplayBuffer(object):
         rd = (b, N) if self.per_agent else (b,)
         out = (torch.empty(b, N, D, device=dev), torch.empty(b, N, sum(self.act_heads), device=dev),
                torch.empty(rd, device=dev), torch.empty(b, N, D, device=dev), torch.empty(rd, device=dev))
-        check(self._lib.pw_replay_gather(C.byref(self._store), _ptr(idx), b, _ptr(out[0]), _ptr(out[1]),
-                                         _ptr(out[2]), _ptr(out[3]), _ptr(out[4]), self._stream()))
+        check(self._lib.pw_replay_gather(C.byref(self._store), ptr(idx), b, ptr(out[0]), ptr(out[1]),
+                                         ptr(out[2]), ptr(out[3]), ptr(out[4]), self._stream()))
         return out
 
     def sample_index(self, idxes):

@@ -20,6 +20,7 @@ import time
 import numpy as np
 import torch
 
+from . import _lib
 from . import arglist as _default_arglist
 
 
@@ -227,16 +228,14 @@ class BatchedRollout(object):
     def _bookkeeping(self, rew_shared, terminal, counters=()):
         """Episode returns on the device; ``counters`` = up to two (tensor, delta, modulo) device counters that the
         same launch advances (captured steps: replay cursor, Philox step)."""
-        import ctypes as C
-        from ._lib import check
-        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        p = _lib.ptr
         cs = list(counters) + [(None, 0, 0)] * (2 - len(counters))
         args = []
         for t, d, m in cs:
-            args += [None if t is None else p(t), int(d), int(m)]
-        check(self.env.lib.pw_rollout_tail(p(rew_shared), p(terminal), self.env.num_envs, p(self.episode_return),
-                                           p(self.finished_return_sum), p(self.finished_episodes), *args,
-                                           self.env._stream()))
+            args += [p(t), int(d), int(m)]
+        _lib.check(self.env.lib.pw_rollout_tail(p(rew_shared), p(terminal), self.env.num_envs, p(self.episode_return),
+                                                p(self.finished_return_sum), p(self.finished_episodes), *args,
+                                                _lib.stream(self.env.device)))
 
     def _per_agent_memory(self):
         return self.memory is not None and bool(getattr(self.memory, 'per_agent', False))
@@ -285,8 +284,7 @@ class BatchedRollout(object):
         if defer:
             self.policy.defer_step_advance = True
         if self.memory is not None:
-            if self.memory._store is None:
-                self.memory._allocate(env.n, env.obs_dim)
+            self.memory.claim(0, env.n, env.obs_dim, dev)
             self.memory.sync_cursor()
 
         def one(i):
@@ -305,8 +303,6 @@ class BatchedRollout(object):
         torch.cuda.current_stream(dev).wait_stream(side)
         if self.memory is not None:
             self.memory.note_graph_adds(2 * env.num_envs)
-        if hasattr(self.policy, 'calls'):
-            pass  # begin_graph() moved the step counter to the device
         self.env_steps += 2 * env.num_envs
         self._graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph):

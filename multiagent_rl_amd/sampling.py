@@ -17,8 +17,6 @@ What the launch computes, per row: ``v = (logits - noise) / tau``, ``idx`` = the
 ``y = (onehot(idx) - soft) + soft`` (``hard``; the value of torch's ``y_hard - y_soft.detach() + y_soft``) or ``y = soft``.  The
 gradient is the soft sample's for both: ``dLogits_o = soft_o (dY_o - sum_k dY_k soft_k) / tau``.
 """
-import ctypes as C
-
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -39,16 +37,7 @@ def default_seed(exploration_seed=0):
     return (int(exploration_seed) + LEARNER_STREAM) & _MASK64
 
 
-def _check(t, what, device=None):
-    if t.device.type != 'cuda':
-        raise RuntimeError('%s is on %s: the sampling kernels run on the GPU (no CPU fallback; F.gumbel_softmax is the stock '
-                           'expression)' % (what, t.device))
-    if device is not None and t.device != device:
-        raise RuntimeError('%s is on %s, the logits on %s' % (what, t.device, device))
-    if t.dtype != torch.float32:
-        raise RuntimeError('%s must be float32 (got %s)' % (what, t.dtype))
-    if not t.is_contiguous():
-        raise RuntimeError('%s must be contiguous' % what)
+FAMILY = 'the sampling kernels run on the GPU (no CPU fallback; F.gumbel_softmax is the stock expression)'
 
 
 def _shape(logits):
@@ -69,20 +58,12 @@ def _tau(tau):
     return tau
 
 
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 # ---- the overridable pieces: the launches.  A CPU test replaces them with torch stand-ins of the same signature. ----------------
 def launch_forward(logits, tau, hard, seed, step, cell, keep, want_idx=False, want_noise=False):
     """logits [rows,n] contiguous -> ``(y, soft or None, idx or None, noise or None)``: one ``pw_gumbel_st_forward``.  The noise's step is
     ``step`` plus the content of ``cell`` (an int64 device tensor, or None).  ``soft`` is stored only when ``keep``."""
     _shape(logits)
-    _check(logits, 'logits')
+    _lib.check_f32(logits, 'logits', FAMILY)
     tau = _tau(tau)
     if cell is not None and (cell.dtype != torch.int64 or cell.device != logits.device or cell.numel() < 1):
         raise RuntimeError('the step cell must be an int64 tensor on %s' % logits.device)
@@ -92,26 +73,28 @@ def launch_forward(logits, tau, hard, seed, step, cell, keep, want_idx=False, wa
     soft = new((rows, n), torch.float32) if keep else None
     idx = new((rows,), torch.int32) if want_idx else None
     noise = new((rows, n), torch.float32) if want_noise else None
-    _lib.check(_lib.load().pw_gumbel_st_forward(_p(logits), rows, n, tau, int(bool(hard)), int(seed) & _MASK64, int(step) & _MASK64, _p(cell),
-                                                _p(y), _p(soft), _p(idx), _p(noise), _stream(logits.device)))
+    p = _lib.ptr
+    _lib.check(_lib.load().pw_gumbel_st_forward(p(logits), rows, n, tau, int(bool(hard)), int(seed) & _MASK64, int(step) & _MASK64, p(cell),
+                                                p(y), p(soft), p(idx), p(noise), _lib.stream(logits.device)))
     return y, soft, idx, noise
 
 
 def launch_backward(dY, soft, tau):
     """dY [rows,n] contiguous, soft as returned by ``launch_forward`` -> dLogits [rows,n]: one ``pw_gumbel_st_backward``."""
     rows, n = _shape(soft)
-    _check(soft, 'soft')
-    _check(dY, 'dY', soft.device)
+    _lib.check_f32(soft, 'soft', FAMILY)
+    _lib.check_f32(dY, 'dY', FAMILY, soft.device, 'the logits')
     if dY.shape != soft.shape:
         raise ValueError('dY must be %r (got %r)' % (tuple(soft.shape), tuple(dY.shape)))
     dLogits = torch.empty_like(soft)
-    _lib.check(_lib.load().pw_gumbel_st_backward(_p(dY), _p(soft), rows, n, _tau(tau), _p(dLogits), _stream(soft.device)))
+    p = _lib.ptr
+    _lib.check(_lib.load().pw_gumbel_st_backward(p(dY), p(soft), rows, n, _tau(tau), p(dLogits), _lib.stream(soft.device)))
     return dLogits
 
 
 def launch_advance(cell, delta):
     """``cell += delta`` on the device, in stream order (``pw_counter_add``): inside a captured region every replay advances it."""
-    _lib.check(_lib.load().pw_counter_add(_p(cell), int(delta), 0, _stream(cell.device)))
+    _lib.check(_lib.load().pw_counter_add(_lib.ptr(cell), int(delta), 0, _lib.stream(cell.device)))
 
 
 class _Sample(torch.autograd.Function):

@@ -232,32 +232,29 @@ def ref_wire_transitions_reference(g, block):
                 act=v['act'].reshape(T * B, 2, 2).clone(), rew=v['rew_shared'].reshape(T * B).clone(), done=torch.zeros(T * B))
 
 
+# wire format -> (finalize, transitions): the torch restatement of its two launches
+STANDINS = {'PwChunkWire': (wire_finalize_reference, wire_transitions_reference),
+            'PwStateWire': (lambda g, block, obs0: state_wire_finalize_reference(g, block, g.env.landmarks_of_episode),
+                            state_wire_transitions_reference),
+            'PwRefWire': (ref_wire_finalize_reference, ref_wire_transitions_reference)}
+
+
 class CpuFullGather(FullTransitionGather):
     def _layout(self, PwChunkWire):
         # the layout arithmetic is host code of libpworld (no GPU needed)
         return super()._layout(PwChunkWire)
 
     def _make_memory(self):
-        if self.ref_wire:
-            return HostRing()
-        if getattr(self, 'ring_kind', 'rows') == 'state':
-            return HostStateRing(self.scenario, self.A)
-        return HostRing()
+        return HostStateRing(self.scenario, self.A) if self.ring_kind == 'state' else HostRing()
 
     def _begin(self, block):
         state_wire_begin_reference(self, block, *self.env.wire_start())     # the stub env's (state0, landmarks, episode numbers)
 
     def _finalize(self, block, obs0):
-        if self.ref_wire:
-            ref_wire_finalize_reference(self, block, obs0)
-        elif self.state_wire:
-            state_wire_finalize_reference(self, block, self.env.landmarks_of_episode)
-        else:
-            wire_finalize_reference(self, block, obs0)
+        STANDINS[self.format.Struct.__name__][0](self, block, obs0)
 
     def _ingest(self, block):
-        tr = ref_wire_transitions_reference(self, block) if self.ref_wire else \
-            state_wire_transitions_reference(self, block) if self.state_wire else wire_transitions_reference(self, block)
+        tr = STANDINS[self.format.Struct.__name__][1](self, block)
         if isinstance(self.memory, HostStateRing):
             self.memory.append(tr)
         else:

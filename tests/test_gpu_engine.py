@@ -1121,6 +1121,91 @@ def test_policy_rollout_sink_into_a_state_ring_samples_the_row_rings_batch(scena
             FusedActor(net, seed=5).rollout(env_a, 5, False, memory=other)
 
 
+RING_PLANES = ('obs', 'next_obs', 'act', 'rew', 'done')
+
+
+def _sink_case():
+    """simple_spread, local observation, N = L = 3, B = 4, episodes of 2 steps (a reset falls inside a 3-step chunk), a ring of 64 that
+    holds five known transitions -> (env, its state after the reset, actor network, the ring, clones of its slots [0, 5))."""
+    from multiagent_rl_amd import make_batched_env
+    from multiagent_rl_amd.policy import ActorNetwork
+    from multiagent_rl_amd.replay_buffer import ReplayBuffer
+    torch.manual_seed(11)
+    env = make_batched_env('simple_spread', 4, n=3, auto_reset=True, max_episode_len=2, seed=7)
+    env.reset()
+    N, D = env.n, env.obs_dim
+    ring = ReplayBuffer(64, N, D)
+    obs, nxt = torch.randn(5, N, D, device='cuda'), torch.randn(5, N, D, device='cuda')
+    ring.add_batch(obs, torch.randint(0, 5, (5, N), device='cuda', dtype=torch.int32), torch.randn(5, device='cuda'), nxt)
+    assert ring._next_idx == len(ring) == 5 and torch.equal(ring.obs[:5], obs) and torch.equal(ring.next_obs[:5], nxt)
+    five = {name: getattr(ring, name)[:5].clone() for name in RING_PLANES}
+    return env, env.get_state(), ActorNetwork(D, 5).cuda().eval(), ring, five
+
+
+def _restart(env, st):
+    env.set_state(st['pos'], st['vel'], st['landmarks'], ep_step=st['ep_step'], ep_count=st['ep_count'])
+
+
+def _assert_sink_kept_the_five(copy, ring, five, n):
+    torch.cuda.synchronize()
+    assert copy._next_idx == ring._next_idx == 5 + n and len(copy) == len(ring) == 5 + n
+    for name in RING_PLANES:
+        assert torch.equal(getattr(copy, name)[:5], five[name]), name
+        assert torch.equal(getattr(copy, name)[5:5 + n], getattr(ring, name)[5:5 + n]), name
+
+
+def test_unpickled_ring_as_rollout_sink_keeps_its_transitions():
+    """A ring that was pickled with five transitions and is FIRST used as the sink of ``FusedActor.rollout``: its planes are uploaded
+    before the launch appends behind them (``ReplayBuffer.claim``), so it ends as the ring that was never pickled does."""
+    import pickle
+    from multiagent_rl_amd.policy import FusedActor
+    env, st, net, ring, five = _sink_case()
+    copy = pickle.loads(pickle.dumps(ring))
+    assert copy._store is None and len(copy) == 5
+    T = 3
+    for mem in (ring, copy):
+        _restart(env, st)
+        FusedActor(net, seed=5).rollout(env, T, False, memory=mem)
+    _assert_sink_kept_the_five(copy, ring, five, T * env.num_envs)
+
+
+def test_unpickled_ring_as_full_gather_memory_keeps_its_transitions():
+    """The same through ``FullTransitionGather(world=1, wire='rows', memory=...)``: the root's append claims the ring first."""
+    import pickle
+    from multiagent_rl_amd.dist import FullTransitionGather
+    from multiagent_rl_amd.policy import FusedActor
+    env, st, net, ring, five = _sink_case()
+    copy = pickle.loads(pickle.dumps(ring))
+    assert copy._store is None and len(copy) == 5
+    T = 3
+    for mem in (ring, copy):
+        _restart(env, st)
+        full = FullTransitionGather(env, T, 0, 1, torch.device('cuda', 0), memory=mem, wire='rows')
+        obs0 = env.observe()
+        FusedActor(net, seed=5).rollout(env, T, full.outputs())
+        full(obs0)
+        full.finish()
+        assert full.rows_ingested == T * env.num_envs
+    _assert_sink_kept_the_five(copy, ring, five, T * env.num_envs)
+
+
+def test_rollout_into_a_ring_that_is_too_small_is_refused_before_the_launch():
+    """T B = 12 transitions into a ring of 8: ``claim`` raises on the host; the env, the actor's call count and the cursor stay."""
+    from multiagent_rl_amd.policy import FusedActor
+    from multiagent_rl_amd.replay_buffer import ReplayBuffer
+    env, st, net, _, _ = _sink_case()
+    N, D = env.n, env.obs_dim
+    small = ReplayBuffer(8, N, D)
+    small.add_batch(torch.zeros(3, N, D, device='cuda'), torch.zeros(3, N, device='cuda', dtype=torch.int32),
+                    torch.zeros(3, device='cuda'), torch.zeros(3, N, D, device='cuda'))
+    actor = FusedActor(net, seed=5)
+    with pytest.raises(RuntimeError, match='12 transitions into a ring of 8'):
+        actor.rollout(env, 3, False, memory=small)
+    after = env.get_state()
+    assert all(torch.equal(after[k], st[k]) for k in st)
+    assert actor.calls == 0 and small._next_idx == 3 and len(small) == 3
+
+
 def test_state_wire_carries_the_policy_rollout_and_stays_under_130_bytes_per_env_step():
     """C2 (B = 4096, N = 6, 100-step chunks) with the policy in the loop, as bench.py --gpus N drives it: FusedActor.rollout
     writes into FullTransitionGather.outputs(); the root ring equals the ring the same launch's own sink fills

@@ -11,7 +11,6 @@ def run(mode):
     env.reset()
     actor = FusedActor(ActorNetwork(env.obs_dim, [5, 10]).cuda().eval(), seed=7)
     mem = ReplayBuffer(int(8e6), 2, env.obs_dim, act_heads=(5, 10))
-    mem._allocate(2, env.obs_dim) if mem._store is None else None
     ret = torch.zeros(B, device='cuda'); fs = torch.zeros((), dtype=torch.float64, device='cuda'); fc = torch.zeros((), dtype=torch.int64, device='cuda')
     out = None
     def one():

@@ -45,9 +45,9 @@ def run(mode):
 
     def ingest(block, stream):
         for _ in range(a.blocks):
-            _lib.check(add(C.byref(m._store), m._next_idx, C.byref(full.lay), C.c_void_p(block.data_ptr()),
-                           C.c_void_p(stream.cuda_stream)))
-            m._next_idx = (m._next_idx + T * B) % m._maxsize
+            start = m.claim(T * B)
+            _lib.check(add(C.byref(m._store), start, C.byref(full.lay), _lib.ptr(block), C.c_void_p(stream.cuda_stream)))
+            m._advance(T * B)
 
     for k in range(a.chunks + 2):
         if k == 2:
