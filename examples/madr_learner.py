@@ -26,6 +26,9 @@ loss TENSORS of the replay (no read-back per update); ``optimize.losses()`` read
 kernels, one launch forward and one backward each (``multiagent_rl_amd.sampling.GumbelSampler``), with the library's own noise keyed
 (``sampling_seed``; update number, call site, row) instead of torch's generator -- a graphed run then reproduces an eager one bit for bit.
 The default is ``F.gumbel_softmax``; the B = 1 ``get_exploration_action`` keeps it either way.
+``Trainer(..., fused_front=True)``: dense1, the ReLU and the LSTM's input projection of actor and critic (and of the target networks
+copied from them) run, forward and backward, on the HIP kernels (``multiagent_rl_amd.dense.fuse_front``); it needs ``fused_lstm``, and
+the default is the stock expression.
 """
 import copy
 import os
@@ -55,7 +58,8 @@ class Trainer(object):
     per_agent = False   # BiCNetTrainer: per-agent rewards / dones [b,N] and a critic that returns [b,N,1]
 
     def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
-                 fused_lstm=False, fused_attention=False, graph_update=False, fused_sampling=False, sampling_seed=None):
+                 fused_lstm=False, fused_attention=False, graph_update=False, fused_sampling=False, sampling_seed=None,
+                 fused_front=False):
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
         self.sampler = None
@@ -69,6 +73,10 @@ class Trainer(object):
             from multiagent_rl_amd.lstm import fuse_lstm
             fuse_lstm(self.actor)
             fuse_lstm(self.critic)
+        if fused_front:   # before the deep copies too; a ValueError says so where an LSTM is still nn.LSTM
+            from multiagent_rl_amd.dense import fuse_front
+            fuse_front(self.actor)
+            fuse_front(self.critic)
         self.target_actor, self.target_critic = copy.deepcopy(self.actor).eval(), copy.deepcopy(self.critic).eval()
         self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr)
         self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr)

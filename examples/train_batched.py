@@ -24,7 +24,9 @@ soft update as one launch (``multiagent_rl_amd.optim``: the learner's own switch
 ``--fused-attention`` runs the attention critic's attention block with gradient on the HIP kernels (``multiagent_rl_amd.attention``: the
 learner's own ``fused_attention`` switch, or ``accelerate_trainer(.., attention=True)`` with ``--reference``),
 ``--fused-sampling`` runs the learner's Gumbel-softmax samples with gradient on the HIP kernels, with the library's own noise stream
-(``multiagent_rl_amd.sampling``: the learner's own ``fused_sampling`` switch, or ``accelerate_trainer(.., sampling=True)`` with ``--reference``).
+(``multiagent_rl_amd.sampling``: the learner's own ``fused_sampling`` switch, or ``accelerate_trainer(.., sampling=True)`` with ``--reference``),
+``--fused-front`` runs dense1, the ReLU and the LSTM's input projection of the learner's networks with gradient on the HIP kernels
+(``multiagent_rl_amd.dense``: the learner's own ``fused_front`` switch, or ``accelerate_trainer(.., front=True)`` with ``--reference``; needs ``--fused-lstm``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -86,7 +88,13 @@ def main(argv=None):
                     help="the learner's Gumbel-softmax samples run, forward and backward, on the HIP kernels (madr_learner's "
                          'fused_sampling switch; with --reference: accelerate_trainer(.., sampling=True)); off by default: the noise is '
                          "the library's Philox stream keyed (seed; update, call site, row), not torch's generator")
+    ap.add_argument('--fused-front', action='store_true',
+                    help="dense1, the ReLU and the LSTM's input projection of the learner's networks run, forward and backward, on the HIP "
+                         "kernels (madr_learner's fused_front switch; with --reference: accelerate_trainer(.., front=True)); needs "
+                         '--fused-lstm; off by default: the sums run in another order than the stock GEMMs')
     args = ap.parse_args(argv)
+    if args.fused_front and not args.fused_lstm:
+        ap.error('--fused-front needs --fused-lstm: the fused front feeds the fused recurrence')
     if args.graph_update:
         need = ['--fused-targets', '--fused-optimizer', '--fused-lstm'] + ([] if args.critic == 'bicnet' else ['--fused-attention'])
         lacking = [f for f in need if not getattr(args, f[2:].replace('-', '_'))]
@@ -127,7 +135,7 @@ def main(argv=None):
         from madr_learner import CriticNetwork, Trainer
         if args.critic == 'attention':
             from multiagent_rl_amd.critic import CriticNetwork
-    if args.fused_targets or args.fused_optimizer or args.fused_lstm or args.fused_attention or args.fused_sampling:
+    if args.fused_targets or args.fused_optimizer or args.fused_lstm or args.fused_attention or args.fused_sampling or args.fused_front:
         from multiagent_rl_amd.policy import accelerate_trainer
         plain_trainer = Trainer
 
@@ -140,6 +148,8 @@ def main(argv=None):
                 k['fused_attention'] = True
             if args.fused_sampling and not args.reference:
                 k['fused_sampling'] = True
+            if args.fused_front and not args.reference:
+                k['fused_front'] = True
             if args.graph_update and not args.reference:
                 k['graph_update'] = True     # madr_learner installs the fused targets and the graphed update itself
                 return plain_trainer(*a, **k)
@@ -147,7 +157,8 @@ def main(argv=None):
             if args.fused_targets or args.reference:
                 accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
                                    lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference,
-                                   graph=args.graph_update, sampling=args.fused_sampling and args.reference)
+                                   graph=args.graph_update, sampling=args.fused_sampling and args.reference,
+                                   front=args.fused_front and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

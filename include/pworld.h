@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 117 /* 0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 118 /* 0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -696,6 +696,29 @@ int pw_gumbel_st_forward(const float *logits, int64_t rows, int32_t n, float tau
 /* dY [rows,n] contiguous and soft as the forward wrote it -> dLogits [rows,n]:
  *   dLogits_o = soft_o (dY_o - sum_k dY_k soft_k) / tau, k ascending -- the soft sample's gradient, which the hard sample shares. */
 int pw_gumbel_st_backward(const float *dY, const float *soft, int64_t rows, int32_t n, float tau, float *dLogits, void *stream);
+
+/* ---- the dense front of the learner's networks with gradient (translation unit pworld_front.hip) -----------------------------------
+ * [x0 | x1] -> dense1 (w1 [64, d0 + d1], b1 [64]) -> ReLU -> G = hid W_ih^T + (b_ih + b_hh), exact float32:
+ *   x0 [rows,d0], x1 [rows,d1] or NULL with d1 = 0: the two parts of the input row, read side by side (no concatenated copy);
+ *   per direction d < dirs: w_ih[d] [4H,64], b_ih[d], b_hh[d] [4H] as nn.LSTM keeps them, read in place (with dirs = 1 entry 1 is unread);
+ *   hid [rows,64] after the ReLU, or NULL when no gradient will need it; G [rows, dirs*4H] as pw_lstm_train_forward reads it.
+ * Served: (dirs, H) = (1, 64) or (2, 32), 1 <= d0 <= 104, 0 <= d1 <= 16, rows >= 1; anything else, a null argument, an input that is not
+ * 4-byte aligned or a hid / G that is not 16-byte aligned: PW_EINVAL naming it, nothing launched.  One launch. */
+int pw_front_train_forward(const float *x0, int32_t d0, const float *x1, int32_t d1, const float *w1, const float *b1,
+                           const float *const w_ih[2], const float *const b_ih[2], const float *const b_hh[2], int64_t rows,
+                           int32_t dirs, int32_t H, float *hid, float *G, void *stream);
+/* dG [rows, dirs*4H] contiguous, the forward's inputs and its hid ->
+ *   dHid = (dG W_ih) o (hid > 0);  dW_ih[d] = dG_d^T hid;  db_gate[d] = sum over rows of dG_d (one vector serves b_ih and b_hh);
+ *   dW1 = dHid^T [x0 | x1];  db1 = sum over rows of dHid;  dx0 / dx1 = dHid W1 split by column, each only when its pointer is given.
+ * Two launches: the main kernel leaves one partial sum per workgroup and element in `scratch` (at least
+ * pw_front_train_scratch_bytes(rows, d0, d1) bytes), the second adds them in workgroup order.  The number of workgroups and the rows of
+ * each follow from `rows` alone and no floating-point atomic exists: the same inputs give the same bits on every launch. */
+int pw_front_train_backward(const float *dG, const float *x0, int32_t d0, const float *x1, int32_t d1, const float *hid,
+                            const float *w1, const float *const w_ih[2], int64_t rows, int32_t dirs, int32_t H, float *dW1, float *db1,
+                            float *const dW_ih[2], float *const db_gate[2], float *dx0, float *dx1, void *scratch,
+                            size_t scratch_bytes, void *stream);
+/* The bytes of scratch one pw_front_train_backward of this shape needs (0 for a shape that is not served). */
+size_t pw_front_train_scratch_bytes(int64_t rows, int32_t d0, int32_t d1);
 
 #ifdef __cplusplus
 }

@@ -116,13 +116,21 @@ def stock_attention(steps, relu=True):
 
 
 # ---- what every critic of the family shares: the trunk and the question which form a module is ----------------------------------
-def lstm_trunk(m, obs, action):
-    """``m.dense1`` on ``[obs, action...]`` (``action`` a tensor or a list of them), ReLU, ``m.lstm`` over the agent axis
-    -> ``(steps [b,N,64], h_n [1,b,64])``.  ``m``: any module with the family's ``dense1`` and ``lstm``, this project's or not."""
+def stock_trunk(m, obs, action):
+    """The trunk as torch runs it: the cat, ``m.dense1``, the ReLU, ``m.lstm``."""
     parts = [obs] + (list(action) if isinstance(action, (list, tuple)) else [action])
     hid = F.relu(m.dense1(torch.cat(parts, dim=-1)))
     steps, (h_n, _) = m.lstm(hid, None)
     return steps, h_n
+
+
+def lstm_trunk(m, obs, action):
+    """``m.dense1`` on ``[obs, action...]`` (``action`` a tensor or a list of them), ReLU, ``m.lstm`` over the agent axis
+    -> ``(steps [b,N,64], h_n [1,b,64])``.  ``m``: any module with the family's ``dense1`` and ``lstm``, this project's or not.  A
+    module that ``dense.fuse_front`` has swapped carries its own trunk (``_front_trunk``: the same numbers from the dense-front
+    kernels), whichever forward asks for it."""
+    trunk = getattr(m, '_front_trunk', None)
+    return stock_trunk(m, obs, action) if trunk is None else trunk(obs, action)
 
 
 def _linear(m, wrapped=False):
@@ -195,6 +203,16 @@ def _fused_class(cls, mixin):
     return _classes[mixin, cls]
 
 
+def _without(cls, mixin):
+    """``cls`` without the layer ``mixin`` put on it, wherever in a stack of swaps that layer sits: the class the module would have
+    had if that swap had never run (the other swaps' layers are put back over what remains)."""
+    made = [k for k, v in _classes.items() if v is cls]
+    if not made:
+        return cls
+    mx, base = made[0]
+    return base if issubclass(mx, mixin) else _fused_class(_without(base, mixin), mx)
+
+
 def _reclass(module, new_class):
     """Every module inside ``module`` (itself included; nothing if it is no module) for which ``new_class(m)`` names a class gets it."""
     n = 0
@@ -213,7 +231,7 @@ def _swap(module, forms):
 
 
 def _unswap(module, mixin):
-    return _reclass(module, lambda m: type(m)._unfused if isinstance(m, mixin) else None)
+    return _reclass(module, lambda m: _without(type(m), mixin) if isinstance(m, mixin) else None)
 
 
 def fuse_attention(module):

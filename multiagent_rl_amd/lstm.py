@@ -174,7 +174,21 @@ class FusedLSTM(nn.LSTM):
             w_bw = self.weight_hh_l0_reverse
         else:
             w_ih, bias, w_bw = self.weight_ih_l0, self.bias_ih_l0 + self.bias_hh_l0, None
-        G = F.linear(x, w_ih, bias).view(b, N, dirs, 4 * H)
+        return self._from_gates(F.linear(x, w_ih, bias).view(b, N, dirs, 4 * H), w_bw)
+
+    def forward_gates(self, G):
+        """The recurrence alone, on gates formed elsewhere (``dense.front_projection``): ``G [b, N, dirs, 4 H] = x W_ih^T + b_ih + b_hh``
+        -> what ``forward(x)`` returns, ``(Y, (h_n, c_n))``.  ``W_ih`` and the biases are not read here."""
+        why = self._refuse()
+        if why:
+            raise ValueError('FusedLSTM serves one layer, batch_first, with bias, 1 x 64 or 2 x 32 hidden units: not %s' % why)
+        dirs, H = (2 if self.bidirectional else 1), self.hidden_size
+        if not isinstance(G, torch.Tensor) or G.dim() != 4 or tuple(G.shape[2:]) != (dirs, 4 * H):
+            raise ValueError('FusedLSTM.forward_gates takes G [b, N, %d, %d]' % (dirs, 4 * H))
+        return self._from_gates(G, self.weight_hh_l0_reverse if dirs == 2 else None)
+
+    def _from_gates(self, G, w_bw):
+        dirs, H = G.shape[2], self.hidden_size
         Y, saved = _recurrence(G, self.weight_hh_l0, w_bw, True)
         if dirs == 2:
             h_n = torch.stack([Y[:, -1, :H], Y[:, 0, H:]], dim=0)

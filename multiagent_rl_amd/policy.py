@@ -365,7 +365,7 @@ class FusedExploration(object):
 
 
 def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False, graph=False, graph_warmup=3,
-                       sampling=False, sampling_seed=None):
+                       sampling=False, sampling_seed=None, front=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -412,7 +412,13 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     replay draws new noise.  The noise is the library's own Philox stream keyed by ``sampling_seed`` (default:
     ``sampling.default_seed(seed)``, never the exploration actor's key), a function of (seed, update number, call site, row, logit): not
     torch's generator, which is why this switch is opt-in too, and why a graphed run with it reproduces an eager one bit for bit.  A
-    trainer that carries its own sampler (the example learner's ``fused_sampling``) keeps it."""
+    trainer that carries its own sampler (the example learner's ``fused_sampling``) keeps it.
+
+    ``front=True`` runs what every pass with gradient begins with -- dense1, the ReLU and the LSTM's input projection -- on the HIP
+    kernels with gradient (``multiagent_rl_amd.dense.fuse_front``: a class swap to a subclass of the network's own class, one launch
+    forward and two backward instead of a dozen) for ``trainer.actor``, ``trainer.critic`` and the target networks that are still
+    modules.  It needs ``lstm=True`` or LSTMs that are fused already (``ValueError`` otherwise) and composes with ``attention`` in
+    either order.  Opt-in because the sums run in another order than rocBLAS's; it is not a precondition of ``graph=True``."""
     if graph:   # what this call will not put right is refused before anything is patched (and before the GPU is needed)
         from .graph import missing_for_graph
         mended = [name for name, on in (('targets', targets), ('optimizer', optimizer), ('lstm', lstm), ('attention', attention)) if on]
@@ -436,6 +442,9 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     if attention:
         from .attention import fuse_trainer as fuse_attention_trainer
         fx.fused_attentions = fuse_attention_trainer(trainer)
+    if front:
+        from .dense import fuse_trainer as fuse_front_trainer
+        fx.fused_fronts = fuse_front_trainer(trainer)
     sampler = None
     if sampling:
         from .sampling import install

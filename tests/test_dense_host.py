@@ -1,0 +1,382 @@
+"""CPU: the host side of pw_front_train_forward / pw_front_train_backward and of multiagent_rl_amd.dense (no launch happens without a
+GPU: every call into the library here is refused before one), the float64 restatement tests/dense_ref.py against float64 autograd of
+the stock expression, and the Python plumbing (autograd function, FusedLSTM.forward_gates, fuse_front) with the launches replaced by
+restatements.
+
+Bound.  Restatement in float64 against autograd in float64: 1e-12 relative to the largest entry (the same mathematics; what differs is
+the summation order of dot products of at most 256 terms and of sums over at most 771 rows: a few 1e-14 of the largest entry)."""
+import copy
+import os
+import re
+import sys
+
+import pytest
+
+from multiagent_rl_amd import _lib
+from tests import attention_ref, dense_ref, lstm_ref
+
+torch = pytest.importorskip('torch')
+nn = torch.nn
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL = -1
+SHAPES = [(1, 1, 0, 1), (6, 16, 5, 2), (63, 21, 15, 1), (65, 103, 16, 2), (771, 104, 16, 1), (771, 16, 5, 2)]
+GPU_SHAPES = [(rows, d0, d1, dirs) for rows in (1, 6, 63, 65, 771, 6144) for d0, d1 in ((1, 0), (16, 5), (21, 15), (103, 16), (104, 16))
+              for dirs in (1, 2)]
+
+
+def _f64(inp):
+    c = lambda t: None if t is None else t.double()  # noqa: E731
+    return dict(x0=c(inp['x0']), x1=c(inp['x1']), w1=c(inp['w1']), b1=c(inp['b1']), w_ih=[c(t) for t in inp['w_ih']],
+                b_ih=[c(t) for t in inp['b_ih']], b_hh=[c(t) for t in inp['b_hh']])
+
+
+def _dG(rows, seed=0):
+    return torch.randn(rows, 256, dtype=torch.float64, generator=torch.Generator().manual_seed(rows + seed))
+
+
+# ---- the restatement and its inputs ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('rows,d0,d1,dirs', SHAPES)
+def test_restatement_equals_float64_autograd(rows, d0, d1, dirs):
+    a = _f64(dense_ref.make_inputs(rows, d0, d1, dirs))
+    dG = _dG(rows)
+    G_want, want = dense_ref.stock_grads(lambda G: (G * dG).sum(), **a)
+    hid, G = dense_ref.forward(**a)
+    got = dense_ref.backward(dG, a['x0'], a['x1'], hid, a['w1'], a['w_ih'])
+    rel = lambda x, y: float((x - y).abs().max()) / max(float(y.abs().max()), 1e-300)  # noqa: E731
+    assert rel(G, G_want) <= 1e-12
+    for n, g in got.items():
+        assert rel(g, want[n]) <= 1e-12, n
+    for d in range(dirs):                                           # one vector per direction serves both biases
+        assert rel(got['db_gate%d' % d], want['db_hh%d' % d]) <= 1e-12
+    assert float(want['dW1'].abs().max()) > 0 and float(want['dx0'].abs().max()) > 0
+
+
+def test_redrawn_rows_stay_rare():
+    worst = 0.0
+    for rows, d0, d1, dirs in GPU_SHAPES:
+        if rows < 771:
+            continue
+        inp = dense_ref.make_inputs(rows, d0, d1, dirs)
+        worst = max(worst, inp['redrawn'])
+        pre = dense_ref.pre_activation(inp['x0'], inp['x1'], inp['w1'], inp['b1'])
+        assert float(pre.abs().min()) >= dense_ref.MARGIN
+        err = float((torch.nn.functional.linear(inp['x0'] if inp['x1'] is None else torch.cat([inp['x0'], inp['x1']], -1), inp['w1'], inp['b1'])
+                     .double() - pre).abs().max())
+        assert err < dense_ref.MARGIN / 5, err                      # a float32 pre-activation cannot cross the kink
+    print('largest share of rows redrawn: %.4f' % worst)
+    assert worst < 0.02
+
+
+# ---- the plumbing, with stand-ins for the launches ---------------------------------------------------------------------------------
+@pytest.fixture
+def standins(monkeypatch):
+    from multiagent_rl_amd import attention, dense, lstm
+    calls = []
+
+    def fwd(x0, x1, w1, b1, w_ih, b_ih, b_hh, keep):
+        dense._shape(x0, x1, w1, b1, w_ih, b_ih, b_hh)
+        calls.append(('forward', keep))
+        hid, G = dense_ref.forward(x0, x1, w1, b1, w_ih, b_ih, b_hh)
+        return G.to(x0.dtype), (hid.to(x0.dtype) if keep else None)
+
+    def bwd(dG, x0, x1, hid, w1, w_ih, want_dx0, want_dx1):
+        calls.append(('backward', want_dx0, want_dx1, dG.is_contiguous()))
+        r = dense_ref.backward(dG, x0, x1, hid, w1, w_ih)
+        r = {k: v.to(x0.dtype) for k, v in r.items()}
+        n = len(w_ih)
+        return (r['dW1'], r['db1'], [r['dW_ih%d' % d] for d in range(n)], [r['db_gate%d' % d] for d in range(n)],
+                r['dx0'].contiguous() if want_dx0 else None, r['dx1'].contiguous() if want_dx1 else None)
+    monkeypatch.setattr(dense, 'launch_forward', fwd)
+    monkeypatch.setattr(dense, 'launch_backward', bwd)
+    monkeypatch.setattr(lstm, 'launch_forward', lstm_ref.launch_forward)
+    monkeypatch.setattr(lstm, 'launch_backward', lstm_ref.launch_backward)
+    monkeypatch.setattr(attention, 'launch_forward', attention_ref.launch_forward)
+    monkeypatch.setattr(attention, 'launch_backward', attention_ref.launch_backward)
+    dense.calls = calls
+    yield dense
+    del dense.calls
+
+
+def _leaves(a, grad):
+    """The arguments of front_projection as leaves; ``grad``: the names that need a gradient ('params' = all seven parameter tensors)."""
+    leaf = lambda t, on: None if t is None else t.detach().clone().requires_grad_(on)  # noqa: E731
+    p = 'params' in grad
+    return dict(x0=leaf(a['x0'], 'x0' in grad), x1=leaf(a['x1'], 'x1' in grad), w1=leaf(a['w1'], p), b1=leaf(a['b1'], p),
+                w_ih=[leaf(t, p) for t in a['w_ih']], b_ih=[leaf(t, p) for t in a['b_ih']], b_hh=[leaf(t, p) for t in a['b_hh']])
+
+
+@pytest.mark.parametrize('dirs', [1, 2])
+def test_front_projection_function(standins, dirs):
+    a = _f64(dense_ref.make_inputs(65, 16, 5, dirs))
+    dG = _dG(65)
+    for loss in (lambda G: (G * dG).sum(), lambda G: G.sum()):      # G.sum(): an expanded zero-stride dG arrives contiguous
+        _, want = dense_ref.stock_grads(loss, **a)
+        v = _leaves(a, ('x0', 'x1', 'params'))
+        loss(standins.front_projection(**v)).backward()
+        assert standins.calls == [('forward', True), ('backward', True, True, True)]
+        del standins.calls[:]
+        got = dict(dW1=v['w1'].grad, db1=v['b1'].grad, dx0=v['x0'].grad, dx1=v['x1'].grad)
+        for d in range(dirs):
+            got['dW_ih%d' % d], got['db_gate%d' % d], got['db_hh%d' % d] = v['w_ih'][d].grad, v['b_ih'][d].grad, v['b_hh'][d].grad
+            assert v['b_ih'][d].grad.data_ptr() != v['b_hh'][d].grad.data_ptr()     # two tensors: an in-place clip scales each once
+        for n in want:
+            assert float((got[n] - want[n]).abs().max()) <= 1e-12 * max(1.0, float(want[n].abs().max())), n
+
+
+def test_which_gradients_are_asked_for(standins):
+    a = _f64(dense_ref.make_inputs(6, 16, 5, 1))
+    for grad, asked in ((('params',), (False, False)), (('x1',), (False, True)), (('x0',), (True, False)),
+                        (('x0', 'x1', 'params'), (True, True)), (('x1', 'params'), (False, True))):
+        v = _leaves(a, grad)
+        standins.front_projection(**v).sum().backward()
+        assert standins.calls == [('forward', True), ('backward',) + asked + (True,)], grad
+        del standins.calls[:]
+        assert (v['x0'].grad is not None) == asked[0] and (v['x1'].grad is not None) == asked[1]
+        assert (v['w1'].grad is not None) == ('params' in grad) and (v['b_hh'][0].grad is not None) == ('params' in grad)
+    v = _leaves(a, ())
+    assert not standins.front_projection(**v).requires_grad                                  # nothing needs a gradient: hid is not kept
+    with torch.no_grad():
+        out = standins.front_projection(**_leaves(a, ('x0', 'params')))
+    assert out.grad_fn is None and standins.calls == [('forward', False), ('forward', False)]
+    del standins.calls[:]
+    v = _leaves(a, ('params',))                                                              # no x1 at all; single tensors, not lists
+    w = torch.zeros(64, 16, dtype=torch.float64, requires_grad=True)
+    G = standins.front_projection(v['x0'], None, w, v['b1'], v['w_ih'][0], v['b_ih'][0], v['b_hh'][0])
+    G.sum().backward()
+    assert G.shape == (6, 256) and standins.calls == [('forward', True), ('backward', False, False, True)]
+    xs = a['x0'].t().contiguous().t().requires_grad_()                                       # a strided x0 is made contiguous
+    standins.front_projection(xs, a['x1'], a['w1'], a['b1'], a['w_ih'], a['b_ih'], a['b_hh']).sum().backward()
+    assert xs.grad.shape == xs.shape
+
+
+def test_refusals_and_their_messages():
+    from multiagent_rl_amd import dense
+    a = dense_ref.make_inputs(6, 16, 5, 1)
+    args = lambda **kw: {**{k: a[k] for k in ('x0', 'x1', 'w1', 'b1', 'w_ih', 'b_ih', 'b_hh')}, **kw}  # noqa: E731
+    with pytest.raises(RuntimeError, match='no CPU fallback'):      # the real launch function is in place
+        dense.front_projection(**args())
+    with pytest.raises(RuntimeError, match='no CPU fallback'):
+        dense.launch_backward(torch.zeros(6, 256), a['x0'], a['x1'], torch.zeros(6, 64), a['w1'], list(a['w_ih']), False, False)
+    z = torch.zeros
+    with pytest.raises(ValueError, match='d0 = 105'):
+        dense.front_projection(**args(x0=z(6, 105), x1=None, w1=z(64, 105)))
+    with pytest.raises(ValueError, match='d1 = 17'):
+        dense.front_projection(**args(x1=z(6, 17), w1=z(64, 33)))
+    with pytest.raises(ValueError, match='dirs = 1, H = 32'):
+        dense.front_projection(**args(w_ih=[z(128, 64)], b_ih=[z(128)], b_hh=[z(128)]))
+    with pytest.raises(ValueError, match='dirs = 2, H = 64'):
+        dense.front_projection(**args(w_ih=[z(256, 64)] * 2, b_ih=[z(256)] * 2, b_hh=[z(256)] * 2))
+    with pytest.raises(ValueError, match='at least one row'):
+        dense.front_projection(**args(x0=z(0, 16), x1=z(0, 5)))
+    with pytest.raises(ValueError, match='w1 must be'):
+        dense.front_projection(**args(w1=z(64, 20)))
+    with pytest.raises(ValueError, match=r'\[rows, d\]'):
+        dense.front_projection(**args(x0=z(2, 3, 16)))
+    with pytest.raises(ValueError, match='rows of x0'):
+        dense.front_projection(**args(x1=z(5, 5)))
+    with pytest.raises(ValueError, match='one tensor per direction'):
+        dense.front_projection(**args(b_hh=[z(256), z(256)]))
+    with pytest.raises(ValueError, match='b_ih and b_hh'):
+        dense.front_projection(**args(b_hh=[z(128)]))
+
+
+# ---- FusedLSTM.forward_gates and the swap ------------------------------------------------------------------------------------------
+def _networks():
+    from multiagent_rl_amd import critic as cr, policy as pol
+    return [('critic', cr.CriticNetwork(16 + 5), 'attention'), ('bicnet', cr.BiCNetCritic(16 + 5), None),
+            ('model critic', cr.ModelCriticNetwork(16 + 5), 'model'), ('actor', pol.ActorNetwork(16, 5), None),
+            ('two heads', pol.ActorNetwork(16, [5, 3]), None), ('model actor', pol.ModelActorNetwork(16, 5), None)]
+
+
+def _inputs(net, b, N, parts=1):
+    g = torch.Generator().manual_seed(b * 10 + N)
+    obs = torch.randn(b, N, 16, generator=g)
+    if hasattr(net, 'bilstm'):
+        return (obs,)
+    act = torch.nn.functional.one_hot(torch.randint(0, 5, (b, N), generator=g), 5).float()
+    return (obs, act) if parts == 1 else (obs, [act[..., :2], act[..., 2:]])
+
+
+def _flat(out):
+    if isinstance(out, (list, tuple)):
+        return [t for o in out for t in _flat(o)]
+    return [out]
+
+
+def test_forward_gates_is_forward_without_the_projection(standins):
+    from multiagent_rl_amd import lstm
+    for bidirectional, H in ((False, 64), (True, 32)):
+        m = nn.LSTM(64, H, batch_first=True, bidirectional=bidirectional)
+        assert lstm.fuse_lstm(m) == 1
+        x = torch.randn(5, 3, 64)
+        Y, (h, c) = m(x)
+        names = ['_l0'] + (['_l0_reverse'] if bidirectional else [])
+        G = torch.cat([torch.nn.functional.linear(x, getattr(m, 'weight_ih' + n), getattr(m, 'bias_ih' + n) + getattr(m, 'bias_hh' + n))
+                       for n in names], dim=-1).view(5, 3, len(names), 4 * H)
+        Y2, (h2, c2) = m.forward_gates(G)
+        for p, q in ((Y, Y2), (h, h2), (c, c2)):
+            assert p.shape == q.shape and float((p - q).detach().abs().max()) <= 1e-6
+        with pytest.raises(ValueError, match='forward_gates takes G'):
+            m.forward_gates(G.reshape(5, 3, -1))
+
+
+@pytest.mark.parametrize('order', ['front first', 'attention first'])
+def test_the_swap(standins, order):
+    from multiagent_rl_amd import attention, lstm
+    dense = standins
+    for name, net, form in _networks():
+        torch.manual_seed(1)
+        with pytest.raises(ValueError, match='plain nn.LSTM'):
+            dense.fuse_front(net)
+        assert lstm.fuse_lstm(net) == 1
+        original, keys = type(net), list(net.state_dict())
+        want = {(N, parts): [t.detach() for t in _flat(net(*_inputs(net, 3, N, parts)))] for N in (1, 3) for parts in (1, 2)}
+        fuse_attn = {'attention': attention.fuse_attention, 'model': attention.fuse_model_attention}.get(form)
+        unfuse_attn = {'attention': attention.unfuse_attention, 'model': attention.unfuse_model_attention}.get(form)
+        if fuse_attn and order == 'attention first':
+            assert fuse_attn(net) == 1
+        before = type(net)
+        assert dense.fuse_front(net) == 1 and dense.fuse_front(net) == 0
+        if fuse_attn and order == 'front first':
+            assert fuse_attn(net) == 1 and fuse_attn(net) == 0
+        assert isinstance(net, original) and isinstance(net, dense.FusedFront) and list(net.state_dict()) == keys
+        assert (form is None) or isinstance(net, attention._Fused)
+        twin = copy.deepcopy(net)
+        assert type(twin) is type(net) and list(twin.state_dict()) == keys
+        for (N, parts), outs in want.items():
+            del dense.calls[:]
+            got = _flat(twin(*_inputs(net, 3, N, parts)))
+            assert [c[0] for c in dense.calls] == ['forward'], (name, dense.calls)       # the front ran on front_projection, once
+            for p, q in zip(got, outs):
+                assert p.shape == q.shape and float((p - q).detach().abs().max()) <= 1e-5, (name, N, parts)
+        for p in twin.parameters():
+            p.grad = None
+        del dense.calls[:]
+        sum(t.sum() for t in _flat(twin(*_inputs(net, 3, 3)))).backward()
+        assert [c[:3] for c in dense.calls] == [('forward', True), ('backward', False, False)], name
+        assert all(p.grad is not None for n, p in twin.named_parameters() if 'weight_ih' in n or 'dense1' in n)
+        if fuse_attn and order == 'front first':                     # the attention swap comes off from under... and over the front
+            assert unfuse_attn(net) == 1 and isinstance(net, dense.FusedFront) and not isinstance(net, attention._Fused)
+            assert fuse_attn(net) == 1
+        assert dense.unfuse_front(net) == 1 and dense.unfuse_front(net) == 0
+        if fuse_attn:
+            assert isinstance(net, attention._Fused) and not isinstance(net, dense.FusedFront)
+            if order == 'attention first':
+                assert type(net) is before                          # exactly the class it had, a fused-attention class included
+            assert unfuse_attn(net) == 1
+        assert type(net) is original
+        assert lstm.unfuse_lstm(twin) == 1
+        with pytest.raises(ValueError, match='plain nn.LSTM'):       # a swapped network whose LSTM was put back says so at the call
+            twin(*_inputs(net, 3, 3))
+
+
+def test_swap_inside_a_container_and_on_other_modules(standins):
+    from multiagent_rl_amd import critic as cr, lstm
+    box = nn.ModuleDict(dict(a=cr.CriticNetwork(21), b=nn.Linear(3, 3), c=nn.LSTM(64, 64, batch_first=True)))
+    lstm.fuse_lstm(box)
+    assert standins.fuse_front(box) == 1 and isinstance(box['a'], standins.FusedFront) and type(box['b']) is nn.Linear
+    assert standins.fuse_front(None) == 0 and standins.unfuse_front(box) == 1
+    wide = cr.CriticNetwork(130)
+    lstm.fuse_lstm(wide)
+    with pytest.raises(ValueError, match='serve up to 104'):
+        standins.fuse_front(wide)
+    assert standins.actor_form(cr.CriticNetwork(21)) is None and standins.actor_form(nn.Linear(2, 2)) is None
+
+
+# ---- the C entry points: nothing is launched for a bad argument -------------------------------------------------------------------
+class _Mem(object):
+    """Host memory that is never touched: the refusals come before any launch."""
+
+    def __init__(self):
+        import ctypes
+        self.buf = ctypes.create_string_buffer(64)
+        self.base = (ctypes.addressof(self.buf) + 15) & ~15
+
+
+MEM = _Mem()
+P = MEM.base
+
+
+def _pair(a=P, b=P):
+    import ctypes
+    arr = (ctypes.c_void_p * 2)()
+    arr[0], arr[1] = a, b
+    return arr
+
+
+def _fwd(x0=P, d0=16, x1=P, d1=5, w1=P, b1=P, w_ih=None, b_ih=None, b_hh=None, rows=6, dirs=1, H=64, hid=P, G=P):
+    return _lib.load().pw_front_train_forward(x0, d0, x1, d1, w1, b1, w_ih or _pair(), b_ih or _pair(), b_hh or _pair(), rows, dirs, H,
+                                              hid, G, None)
+
+
+def _bwd(dG=P, x0=P, d0=16, x1=P, d1=5, hid=P, w1=P, w_ih=None, rows=6, dirs=1, H=64, dW1=P, db1=P, dW_ih=None, db_gate=None, dx0=None,
+         dx1=None, scratch=P, scratch_bytes=1 << 30):
+    return _lib.load().pw_front_train_backward(dG, x0, d0, x1, d1, hid, w1, w_ih or _pair(), rows, dirs, H, dW1, db1, dW_ih or _pair(),
+                                               db_gate or _pair(), dx0, dx1, scratch, scratch_bytes, None)
+
+
+def test_symbols_are_exported_and_declared():
+    lib = _lib.load()
+    header = open(os.path.join(ROOT, 'include', 'pworld.h')).read()
+    for name in ('pw_front_train_forward', 'pw_front_train_backward', 'pw_front_train_scratch_bytes'):
+        assert hasattr(lib, name) and name in _lib.SIGNATURES
+        assert re.search(r'\b(int|size_t) %s\(' % name, header)
+    assert lib.pw_version() >= 118 and 'pworld_front.hip' in header
+
+
+@pytest.mark.parametrize('call', [_fwd, _bwd], ids=['forward', 'backward'])
+@pytest.mark.parametrize('kw,word', [
+    (dict(d0=105), b'd0 must'), (dict(d0=0), b'd0 must'), (dict(d1=17), b'd1 must'), (dict(d1=-1), b'd1 must'),
+    (dict(dirs=1, H=32), b'(dirs, H)'), (dict(dirs=2, H=64), b'(dirs, H)'), (dict(dirs=3, H=32), b'(dirs, H)'),
+    (dict(rows=0), b'rows must'), (dict(rows=-5), b'rows must'), (dict(rows=1 << 40), b'rows:'),
+    (dict(x0=None), b'null'), (dict(w1=None), b'null'), (dict(x1=None), b'x1 comes with'), (dict(d1=0), b'x1 comes with'),
+    (dict(x0=P + 2), b'4-byte aligned'), (dict(dirs=2, H=32, w_ih=_pair(P, None)), b'one tensor per direction'),
+], ids=lambda v: str(v) if isinstance(v, dict) else '')
+def test_both_entry_points_refuse_bad_shared_arguments(call, kw, word):
+    assert call(**kw) == EINVAL
+    assert word in _lib.load().pw_last_error(), _lib.load().pw_last_error()
+
+
+def test_entry_points_refuse_bad_buffers_of_their_own():
+    lib = _lib.load()
+    assert _fwd(G=None) == EINVAL and b'null' in lib.pw_last_error()
+    assert _fwd(G=P + 4) == EINVAL and b'16-byte aligned' in lib.pw_last_error()
+    assert _fwd(hid=P + 8) == EINVAL and b'16-byte aligned' in lib.pw_last_error()
+    for name in ('dG', 'hid', 'dW1', 'db1', 'scratch'):
+        assert _bwd(**{name: None}) == EINVAL and b'null' in lib.pw_last_error(), name
+    assert _bwd(dx1=P, x1=None, d1=0) == EINVAL and b'dx1 comes with' in lib.pw_last_error()
+    assert _bwd(scratch_bytes=16) == EINVAL and b'scratch_bytes' in lib.pw_last_error()
+    assert _bwd(dx0=P + 1) == EINVAL and b'4-byte aligned' in lib.pw_last_error()
+
+
+def test_scratch_size_follows_from_the_shape_alone():
+    q = _lib.load().pw_front_train_scratch_bytes
+    per = lambda K: 4 * (256 * 64 + 64 * K + 256 + 64)  # noqa: E731
+    assert q(1, 16, 5) == per(21) and q(16, 16, 5) == per(21) and q(17, 16, 5) == 2 * per(21)
+    assert q(128 * 16, 104, 16) == 128 * per(120) and q(128 * 16 + 1, 104, 16) == 65 * per(120)      # two tiles per workgroup from here
+    assert q(6144, 16, 0) == 128 * per(16)
+    assert q(0, 16, 5) == 0 and q(6, 105, 0) == 0 and q(6, 16, 17) == 0
+
+
+# ---- what the compiler made of the new unit ---------------------------------------------------------------------------------------
+def test_front_unit_carries_exactly_its_own_kernels():
+    sys.path.insert(0, os.path.join(ROOT, 'tools'))
+    try:
+        import code_object
+    finally:
+        sys.path.pop(0)
+    if not code_object.tools_present():
+        pytest.skip('ROCm LLVM binary tools not installed')
+    from multiagent_rl_amd import build_native
+    if not all(os.path.exists(o) for o in build_native.objects()):
+        build_native.build(force=True)
+    src = open(os.path.join(ROOT, 'multiagent_rl_amd', 'csrc', 'pw_kernels_front.hpp')).read()
+    defined = set(re.findall(r'__global__ void (?:__launch_bounds__\(\w+\) )?(pw_\w+_kernel)\(', src))
+    assert defined == {'pw_front_train_forward_kernel', 'pw_front_train_backward_kernel', 'pw_front_train_reduce_kernel'}
+    names = code_object.per_unit_kernels()['pworld_front']
+    assert len(names) == 3 and {re.match(r'(?:void )?(\w+)', n).group(1) for n in names} == defined
+    assert os.path.join(build_native.HERE, 'csrc', 'pworld_front.hip') in build_native.SRCS
+    assert 'pworld_front' in build_native.unit_sources.__doc__
+    unit = [os.path.basename(f) for f in build_native.unit_sources('pworld_front')]
+    assert 'pw_kernels_front.hpp' in unit and 'pw_kernels_lstm.hpp' not in unit
