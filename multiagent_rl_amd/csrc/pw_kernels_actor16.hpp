@@ -230,7 +230,7 @@ __device__ __forceinline__ void actor16_head_chain(const float (&aw2)[16], const
 #pragma unroll
     for (int jx = 0; jx < nj; ++jx) {
         float4 b = hx[jx * 64];
-        if (relu) { b.x = fmaxf(b.x, 0.0f); b.y = fmaxf(b.y, 0.0f); b.z = fmaxf(b.z, 0.0f); b.w = fmaxf(b.w, 0.0f); }
+        if (relu) { b.x = relu_fwd(b.x); b.y = relu_fwd(b.y); b.z = relu_fwd(b.z); b.w = relu_fwd(b.w); }
         actor16_head_frag(aw2, s0 + 4 * jx, b, lg);
     }
 }
@@ -346,7 +346,7 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
             for (int sx = 0; sx < KS; ++sx) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(d1->a1[sx], xb[sx], acc1, 0, 0, 0);
             float v[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = fmaxf(acc1[i] + d1->b1v[i], 0.0f);
+            for (int i = 0; i < 4; ++i) v[i] = relu_fwd(acc1[i] + d1->b1v[i]);
             // hidden unit 16 hq + 4 kq + i in the x1 fragment (pw_kernels_policy3j.hpp): fragment j = hq, lane slot (2 (i & 1) + (kq & 1)) * 16 + n,
             // element 2 (kq / 2) + i / 2 -- registers (0, 2) and (1, 3) are two 8-byte stores
             float4 *dst = S.s_xf + (ts * 4 + hq) * 64 + n16;
@@ -382,7 +382,7 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
         }
         float v[16];
 #pragma unroll
-        for (int q = 0; q < 16; ++q) v[q] = fmaxf(acc1[q] + S.s_b1[m * 32 + mfma_row(q, half)], 0.0f);
+        for (int q = 0; q < 16; ++q) v[q] = relu_fwd(acc1[q] + S.s_b1[m * 32 + mfma_row(q, half)]);
         if (2 * rt + (col >> 4) < N) actor16_store_x1<BF3>(S.s_xf, 2 * rt + (col >> 4), m, half, col & 15, v);
     }
     PW_A16_STAMP(1);
@@ -408,7 +408,7 @@ __device__ __forceinline__ void actor16_forward(const ActorFusedArgs &A, const A
             if (seq_ok) {  // head input: row n16 * N + ts, k = dir * 32 + unit -> fragment 2 dir + hq / 2, same element pair
                 const int rr = n16 * N + ts;
                 reinterpret_cast<float2 *>(S.s_hf + ((rr >> 4) * 4 + 2 * dir + (hq >> 1)) * 64 + kq * 16 + (rr & 15))[hq & 1] =
-                    make_float2(A.relu_out ? fmaxf(h0v, 0.0f) : h0v, A.relu_out ? fmaxf(h1v, 0.0f) : h1v);
+                    make_float2(A.relu_out ? relu_fwd(h0v) : h0v, A.relu_out ? relu_fwd(h1v) : h1v);
             }
             if (s2 + 1 < N) inproj(dir ? N - 2 - s2 : s2 + 1, accn);  // before the barrier: work for the matrix pipe while the workgroup meets
             wg_lds_barrier();  // h(ts) of every unit is in LDS (the last one: the head input is complete)

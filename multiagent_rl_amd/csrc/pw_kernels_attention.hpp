@@ -77,7 +77,7 @@ __global__ void __launch_bounds__(kAttnThreads) pw_attention_pool_forward_kernel
     float c = 0.0f;
     for (int t = 0; t < N; ++t) c = fmaf(attn_lane_value(w, t), y[t * kAttnH + j], c);
     if (valid) {
-        out[(size_t)row * kAttnH + j] = relu ? fmaxf(c, 0.0f) : c;
+        out[(size_t)row * kAttnH + j] = relu ? relu_fwd(c) : c;
         if (weight && step) weight[(size_t)row * N + j] = w;
     }
 }

@@ -95,7 +95,7 @@
         if (n16 < R) {
             float *dst = reinterpret_cast<float *>(Y.s_x + ((ts & 3) * 4 + hq) * FR) + kq;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dst[(i * R + n16) * 4] = fmaxf(acc1[i] + b1v[i], 0.0f);
+            for (int i = 0; i < 4; ++i) dst[(i * R + n16) * 4] = relu_fwd(acc1[i] + b1v[i]);
         }
     };
     // bias + W_ih x1(ts) for the wave's two tiles
@@ -229,7 +229,7 @@
         ctx0 += w * o.x;
         ctx1 += w * o.y;
     }
-    auto clamp = [](const float v) { return MODEL ? v : fmaxf(v, 0.0f); };
+    auto clamp = [](const float v) { return MODEL ? v : relu_fwd(v); };
     float part = C.w2[8 * wave + kq] * clamp(ctx0) + C.w2[8 * wave + 4 + kq] * clamp(ctx1);
     part += lane_xor16(part);
     part += lane_xor32(part);

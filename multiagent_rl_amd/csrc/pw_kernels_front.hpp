@@ -31,6 +31,7 @@
 #pragma once
 
 #include "pw_common.hpp"
+#include "pw_lstm_math.hpp"
 
 namespace {
 
@@ -155,8 +156,8 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_forward_kernel(c
         const front_f4 acc = even + odd;
         const int u = 16 * wave + 4 * hi;
         float4 h;
-        h.x = fmaxf(acc[0] + A.b1[u + 0], 0.0f); h.y = fmaxf(acc[1] + A.b1[u + 1], 0.0f);
-        h.z = fmaxf(acc[2] + A.b1[u + 2], 0.0f); h.w = fmaxf(acc[3] + A.b1[u + 3], 0.0f);
+        h.x = relu_fwd(acc[0] + A.b1[u + 0]); h.y = relu_fwd(acc[1] + A.b1[u + 1]);
+        h.z = relu_fwd(acc[2] + A.b1[u + 2]); h.w = relu_fwd(acc[3] + A.b1[u + 3]);
         *reinterpret_cast<float4 *>(L.hs + lo * kFrontHS + u) = h;
         if (A.hid && row_ok) *reinterpret_cast<float4 *>(A.hid + (size_t)(r0 + lo) * kFrontHid + u) = h;
     }

@@ -97,7 +97,7 @@ __global__ void __launch_bounds__(256) pw_bilstm_kernel(const float *__restrict_
         hs[j] = h;
         wave_lds_sync();  // a sequence's 32 lanes sit in one wave
         lstm_step(w, hs, ai, af, ag, ao, h, c);
-        if (valid) H[((size_t)env * N + t) * 64 + dir * 32 + j] = relu_out ? fmaxf(h, 0.0f) : h;
+        if (valid) H[((size_t)env * N + t) * 64 + dir * 32 + j] = relu_out ? relu_fwd(h) : h;
     }
 }
 
@@ -134,7 +134,7 @@ __global__ void __launch_bounds__(256) pw_dense_kernel(const float *__restrict__
 #pragma unroll
         for (int k = 0; k < KM; ++k)
             if (KT > 0 || k < Kd) acc = __builtin_fmaf(w[k], xr[k], acc);
-        Y[(size_t)r * out_dim + o] = RELU ? fmaxf(acc, 0.0f) : acc;
+        Y[(size_t)r * out_dim + o] = RELU ? relu_fwd(acc) : acc;
     }
 }
 
@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(256) pw_actor_front_kernel(const float *__rest
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc1[m][r] = fmaxf(acc1[m][r] + Y.s_b1[m * 32 + mfma_row(r, half)], 0.0f);
+        for (int r = 0; r < 16; ++r) acc1[m][r] = relu_fwd(acc1[m][r] + Y.s_b1[m * 32 + mfma_row(r, half)]);
 
     // ---- stage 2: eight 32x32 tiles of G^T, one at a time (acc1 stays resident as the B operands)
     float *patch = Y.s_t + wave * 32 * 33;
@@ -525,7 +525,7 @@ __device__ __forceinline__ void actor_forward_wg(const ActorFusedArgs &A, const 
 #pragma unroll
         for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc1[m][r] = fmaxf(acc1[m][r] + S.s_b1[m * 32 + mfma_row(r, half)], 0.0f);
+            for (int r = 0; r < 16; ++r) acc1[m][r] = relu_fwd(acc1[m][r] + S.s_b1[m * 32 + mfma_row(r, half)]);
     }
     PW_STAMP(1);
     // ---- LSTM lane identity: 2 sequences per wave, sequence slot = local environment
@@ -579,7 +579,7 @@ __device__ __forceinline__ void actor_forward_wg(const ActorFusedArgs &A, const 
                 hs[j] = h;
                 wave_lds_sync();
                 lstm_step(w, hs, gi, gf, gg, go, h, c);
-                if (seq_ok) S.s_hid[(se * N + t) * kHs + dir * 32 + j] = A.relu_out ? fmaxf(h, 0.0f) : h;
+                if (seq_ok) S.s_hid[(se * N + t) * kHs + dir * 32 + j] = A.relu_out ? relu_fwd(h) : h;
             }
         }
         PW_STAMP(5);

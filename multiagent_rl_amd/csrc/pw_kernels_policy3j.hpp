@@ -282,7 +282,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
         }
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = fmaxf(acc[i] + b1v[i], 0.0f);
+        for (int i = 0; i < 4; ++i) v[i] = relu_fwd(acc[i] + b1v[i]);
         float4 *dst = S.s_xf + ((buf * 2 + dir) * 4 + hq) * 64 + n16;   // actor16_forward's tile store into slot buf * 2 + dir (kept inline: profiles/actor16_core_codegen.txt)
         reinterpret_cast<float2 *>(dst + (kq & 1) * 16)[kq >> 1] = make_float2(v[0], v[2]);
         reinterpret_cast<float2 *>(dst + (2 + (kq & 1)) * 16)[kq >> 1] = make_float2(v[1], v[3]);
@@ -431,7 +431,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3j_kernel(const PolicyRo
                 } else if (seq_ok) {
                     const int rr = n16 * NP + ts;
                     reinterpret_cast<float2 *>(S.s_hf + ((rr >> 4) * 4 + 2 * dir + (hq >> 1)) * 64 + kq * 16 + (rr & 15))[hq & 1] =
-                        make_float2(A.relu_out ? fmaxf(h0v, 0.0f) : h0v, A.relu_out ? fmaxf(h1v, 0.0f) : h1v);
+                        make_float2(A.relu_out ? relu_fwd(h0v) : h0v, A.relu_out ? relu_fwd(h1v) : h1v);
                 }
                 // x1 ring: buffer s2 & 1 held timestep s2's fragments, consumed by the input projection issued in iteration
                 // s2 - 1 (or above), before that iteration's barrier: free for timestep s2 + 2

@@ -21,6 +21,13 @@ __device__ __forceinline__ float fast_tanh(float x)
     return fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -2.8853900817779268f)), -1.0f);   // exp(-2x) = 2^(-2 log2(e) x): one multiply
 }
 
+// The forward ReLU of every network kernel.  NaN -> NaN, as torch.relu and the float64 restatements have it: fmaxf(v, 0) is v_max_f32,
+// which returns the other operand for a NaN, i.e. turns a poisoned row into hid = 0 and a finite loss.  IEEE 754-2019's maximum
+// carries the NaN and, like v_max_f32, orders -0 below +0, so every other input keeps the bits fmaxf gave it; on gfx950 it is one
+// instruction as before (v_maximum3_f32 v, v, 0, 0).  The compare-and-select spelling "!(v <= 0) ? v : 0" computes the same but
+// costs an instruction per value and took the simple_tag policy rollout (at the 256-register cap) into spilling.
+__device__ __forceinline__ float relu_fwd(const float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+
 // One LSTM cell (PyTorch's gate order i, f, g, o): pre-activations -> new cell state c and output h.  Every kernel form calls this
 // one function, so the forms agree bit for bit whatever the activations' rounding is.
 // (The four gates' exponent arguments and denominators are formed two at a time -- (i, f) and (g, o) sit in adjacent accumulator registers --

@@ -325,6 +325,12 @@ def test_symbols_are_exported_and_declared():
     assert lib.pw_version() >= 118 and 'pworld_front.hip' in header
 
 
+def _case_id(kw):
+    """str(kw) with the two values that are addresses of this process (P + 2, a pointer pair) by name: the same test id in every run."""
+    named = {k: ('P + 2' if k == 'x0' and v is not None else 'pair(P, None)' if k == 'w_ih' else v) for k, v in kw.items()}
+    return str(named)
+
+
 @pytest.mark.parametrize('call', [_fwd, _bwd], ids=['forward', 'backward'])
 @pytest.mark.parametrize('kw,word', [
     (dict(d0=105), b'd0 must'), (dict(d0=0), b'd0 must'), (dict(d1=17), b'd1 must'), (dict(d1=-1), b'd1 must'),
@@ -332,7 +338,7 @@ def test_symbols_are_exported_and_declared():
     (dict(rows=0), b'rows must'), (dict(rows=-5), b'rows must'), (dict(rows=1 << 40), b'rows:'),
     (dict(x0=None), b'null'), (dict(w1=None), b'null'), (dict(x1=None), b'x1 comes with'), (dict(d1=0), b'x1 comes with'),
     (dict(x0=P + 2), b'4-byte aligned'), (dict(dirs=2, H=32, w_ih=_pair(P, None)), b'one tensor per direction'),
-], ids=lambda v: str(v) if isinstance(v, dict) else '')
+], ids=lambda v: _case_id(v) if isinstance(v, dict) else '')
 def test_both_entry_points_refuse_bad_shared_arguments(call, kw, word):
     assert call(**kw) == EINVAL
     assert word in _lib.load().pw_last_error(), _lib.load().pw_last_error()
