@@ -29,6 +29,9 @@ The default is ``F.gumbel_softmax``; the B = 1 ``get_exploration_action`` keeps 
 ``Trainer(..., fused_front=True)``: dense1, the ReLU and the LSTM's input projection of actor and critic (and of the target networks
 copied from them) run, forward and backward, on the HIP kernels (``multiagent_rl_amd.dense.fuse_front``); it needs ``fused_lstm``, and
 the default is the stock expression.
+``Trainer(..., fused_wgrad=True)``: the two ``W_hh`` gradients of every fused LSTM come from ``multiagent_rl_amd.lstm.launch_wgrad`` (two
+device kernels per LSTM backward) instead of two strided copies and a GEMM per direction; it needs ``fused_lstm``, and the default is the
+GEMMs (the sums run in another order).
 """
 import copy
 import os
@@ -59,7 +62,9 @@ class Trainer(object):
 
     def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
                  fused_lstm=False, fused_attention=False, graph_update=False, fused_sampling=False, sampling_seed=None,
-                 fused_front=False):
+                 fused_front=False, fused_wgrad=False):
+        if fused_wgrad and not fused_lstm:
+            raise ValueError('fused_wgrad needs fused_lstm: the W_hh gradients of a plain nn.LSTM are MIOpen\'s')
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self.actor, self.critic = actor.to(self.device), critic.to(self.device)
         self.sampler = None
@@ -71,8 +76,8 @@ class Trainer(object):
             self._fuse_attention(self.critic)
         if fused_lstm:   # before the deep copies: a class swap survives them, so the target networks are fused too
             from multiagent_rl_amd.lstm import fuse_lstm
-            fuse_lstm(self.actor)
-            fuse_lstm(self.critic)
+            fuse_lstm(self.actor, wgrad=bool(fused_wgrad))
+            fuse_lstm(self.critic, wgrad=bool(fused_wgrad))
         if fused_front:   # before the deep copies too; a ValueError says so where an LSTM is still nn.LSTM
             from multiagent_rl_amd.dense import fuse_front
             fuse_front(self.actor)

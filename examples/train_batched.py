@@ -26,7 +26,9 @@ learner's own ``fused_attention`` switch, or ``accelerate_trainer(.., attention=
 ``--fused-sampling`` runs the learner's Gumbel-softmax samples with gradient on the HIP kernels, with the library's own noise stream
 (``multiagent_rl_amd.sampling``: the learner's own ``fused_sampling`` switch, or ``accelerate_trainer(.., sampling=True)`` with ``--reference``),
 ``--fused-front`` runs dense1, the ReLU and the LSTM's input projection of the learner's networks with gradient on the HIP kernels
-(``multiagent_rl_amd.dense``: the learner's own ``fused_front`` switch, or ``accelerate_trainer(.., front=True)`` with ``--reference``; needs ``--fused-lstm``).
+(``multiagent_rl_amd.dense``: the learner's own ``fused_front`` switch, or ``accelerate_trainer(.., front=True)`` with ``--reference``; needs ``--fused-lstm``),
+``--fused-wgrad`` takes the ``W_hh`` gradients of the fused LSTMs from the HIP kernels as well (``multiagent_rl_amd.lstm.launch_wgrad``:
+the learner's own ``fused_wgrad`` switch, or ``accelerate_trainer(.., wgrad=True)`` with ``--reference``; needs ``--fused-lstm``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -92,9 +94,16 @@ def main(argv=None):
                     help="dense1, the ReLU and the LSTM's input projection of the learner's networks run, forward and backward, on the HIP "
                          "kernels (madr_learner's fused_front switch; with --reference: accelerate_trainer(.., front=True)); needs "
                          '--fused-lstm; off by default: the sums run in another order than the stock GEMMs')
+    ap.add_argument('--fused-wgrad', action='store_true',
+                    help="the W_hh gradients of the learner's fused LSTMs come from the HIP kernels, two per LSTM backward, instead of two "
+                         "strided copies and a GEMM per direction (madr_learner's fused_wgrad switch; with --reference: "
+                         'accelerate_trainer(.., wgrad=True)); needs --fused-lstm; off by default: the sums run in another order than '
+                         'the stock GEMMs')
     args = ap.parse_args(argv)
     if args.fused_front and not args.fused_lstm:
         ap.error('--fused-front needs --fused-lstm: the fused front feeds the fused recurrence')
+    if args.fused_wgrad and not args.fused_lstm:
+        ap.error('--fused-wgrad needs --fused-lstm: the W_hh gradients of a plain nn.LSTM are not the kernels\' to form')
     if args.graph_update:
         need = ['--fused-targets', '--fused-optimizer', '--fused-lstm'] + ([] if args.critic == 'bicnet' else ['--fused-attention'])
         lacking = [f for f in need if not getattr(args, f[2:].replace('-', '_'))]
@@ -150,6 +159,8 @@ def main(argv=None):
                 k['fused_sampling'] = True
             if args.fused_front and not args.reference:
                 k['fused_front'] = True
+            if args.fused_wgrad and not args.reference:
+                k['fused_wgrad'] = True
             if args.graph_update and not args.reference:
                 k['graph_update'] = True     # madr_learner installs the fused targets and the graphed update itself
                 return plain_trainer(*a, **k)
@@ -158,7 +169,7 @@ def main(argv=None):
                 accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
                                    lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference,
                                    graph=args.graph_update, sampling=args.fused_sampling and args.reference,
-                                   front=args.fused_front and args.reference)
+                                   front=args.fused_front and args.reference, wgrad=args.fused_wgrad and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

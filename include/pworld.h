@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 119 /* 0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 120 /* 0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -661,9 +661,29 @@ int pw_lstm_train_forward(const float *G, const float *w_hh_fw, const float *w_h
  * tc = tanh(c_t) recomputed with the forward's function:
  *   dh_t = dY_t + dh;  do = dh_t tc o(1-o);  dc_t = dc + dh_t o (1-tc^2);  di = dc_t g i(1-i);  df = dc_t c_prev f(1-f);
  *   dg = dc_t i (1-g^2);  dG_t = [di, df, dg, do];  dh = dG_t . W_hh;  dc = dc_t f.
- * The gradients of W_hh (dG^T against the shifted Y), W_ih, the biases and x are GEMMs and the caller's (multiagent_rl_amd/lstm.py). */
+ * The gradients of W_ih, the biases and x are GEMMs and the caller's (multiagent_rl_amd/lstm.py); those of W_hh (dG^T against the
+ * shifted Y) are the caller's GEMMs too, or pw_lstm_train_wgrad below. */
 int pw_lstm_train_backward(const float *dY, const float *saved, const float *w_hh_fw, const float *w_hh_bw, int64_t b,
                            int32_t N, int32_t dirs, int32_t H, float *dG, void *stream);
+/* The two recurrent-weight gradients (csrc/pw_kernels_lstm_wgrad.hpp, translation unit pworld_lstm_wgrad.hip), from dG [b,N,dirs,4H] as pw_lstm_train_backward writes it and Y [b,N,dirs*H] as
+ * pw_lstm_train_forward writes it, both read in place (no shifted copy exists in memory):
+ *   dw_hh_fw[r][k] = sum over seq and t = 1 .. N-1 of dG[seq][t][0][r] * Y[seq][t-1][k]
+ *   dw_hh_bw[r][k] = sum over seq and t = 0 .. N-2 of dG[seq][t][1][r] * Y[seq][t+1][H+k]          r < 4H, k < H
+ * Both [4H,H], any 4-byte aligned address.  Either may be NULL: that direction is skipped (not multiplied, not written).  With
+ * N = 1 the sums are empty and the outputs are written as exact zeros.  Exact float32 on v_mfma_f32_16x16x4_f32; TWO launches for
+ * both directions together: one forms a partial sum per workgroup (at most 128; rows (seq, t) ascending in tiles of 16, two
+ * accumulator chains per output) in `scratch`, the other adds the partial sums as a balanced tree over the workgroup numbers.  No
+ * floating-point atomics: the order of every sum is a function of (b, N, dirs) alone, so the same inputs give the same bits on every
+ * launch, on every stream, eager or replayed from a graph.  A row without a previous step in its direction (t = 0 forward, t = N-1
+ * reverse) contributes nothing BY A SELECT, not by a product with zero: a NaN in dG[:, 0, 0] or dG[:, N-1, 1] does not reach the
+ * outputs, as it does not reach the sliced GEMMs these sums replace; the shifted row never comes from the neighbouring sequence.
+ * scratch: pw_lstm_train_wgrad_scratch_bytes(b, N, dirs, H) bytes of device memory, 4-byte aligned, contents arbitrary; it belongs to
+ * the call until its launches have run (0 from that function = the shape is not served).
+ * PW_EINVAL, nothing launched: a shape other than dirs = 1, H = 64 / dirs = 2, H = 32, b < 1, N < 1, b N > 2^40, dG / Y / scratch
+ * null, both outputs null, dw_hh_bw set with dirs = 1, a misaligned pointer. */
+size_t pw_lstm_train_wgrad_scratch_bytes(int64_t b, int32_t N, int32_t dirs, int32_t H);
+int pw_lstm_train_wgrad(const float *dG, const float *Y, int64_t b, int32_t N, int32_t dirs, int32_t H, float *dw_hh_fw,
+                        float *dw_hh_bw, void *scratch, void *stream);
 
 /* The attention block of CriticNetwork WITH gradient (csrc/pw_kernels_attention.hpp), one launch each, for the learner's two critic
  * passes per update.  Y [b,N,H] is the LSTM's output; the query is its last step, q = Y[:, N-1] (h_n[-1] of a one-direction LSTM).

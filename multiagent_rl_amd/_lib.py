@@ -184,6 +184,8 @@ SIGNATURES = {
                                  C.c_void_p]),
     'pw_lstm_train_forward': (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     'pw_lstm_train_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
+    'pw_lstm_train_wgrad_scratch_bytes': (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    'pw_lstm_train_wgrad': (C.c_int, [C.c_void_p] * 2 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     'pw_attention_pool_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     'pw_attention_pool_backward': (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 2),
     'pw_gumbel_st_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_int32, C.c_uint64, C.c_uint64] + [C.c_void_p] * 6),

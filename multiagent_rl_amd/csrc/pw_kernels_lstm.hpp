@@ -2,8 +2,9 @@
 // The recurrent part of a one-layer LSTM WITH gradient, for the learner's three passes per update (critic(s0, a0), actor(s0),
 // critic(s0, actor(s0))): pw_lstm_train_forward_kernel walks the steps and keeps what the backward needs (the four gates after
 // their activations -- see saved_sigmoid -- and c of every step), pw_lstm_train_backward_kernel walks them in reverse and returns the gradient at the
-// pre-activations.  The input projection G = x W_ih^T + b_ih + b_hh, its gradient and the W_hh gradient are GEMMs and stay with the
-// caller (rocBLAS through autograd; multiagent_rl_amd/lstm.py).  One launch each instead of MIOpen's ~45 per direction and pass.
+// pre-activations.  The input projection G = x W_ih^T + b_ih + b_hh and its gradient are GEMMs and stay with the caller (rocBLAS
+// through autograd; multiagent_rl_amd/lstm.py); the W_hh gradient is the caller's GEMM too, or pw_lstm_train_wgrad_kernel
+// (pw_kernels_lstm_wgrad.hpp, a unit of its own).  One launch each instead of MIOpen's ~45 per direction and pass.
 //
 // Two shapes, the two the reference's networks have: <H = 64, DIRS = 1> (both critics) and <H = 32, DIRS = 2> (the actor; direction 1
 // walks t = N - 1 .. 0).  Mapping, the same for both kernels and both shapes:

@@ -7,6 +7,11 @@ alone.  Here the recurrent part is ONE launch forward and ONE backward; everythi
 ordinary autograd: the input projection ``G = x W_ih^T + b_ih + b_hh`` (so ``x``, ``W_ih`` and both biases get their gradients from
 ``F.linear``) and the two ``W_hh`` gradients (``dG^T`` against the output shifted by one step).
 
+``wgrad=True`` (``fuse_lstm``, ``lstm_recurrence``; off by default) takes those two ``W_hh`` gradients off torch as well: instead of two
+strided copies and a rocBLAS GEMM per direction, ONE ``pw_lstm_train_wgrad`` (two device kernels for both directions) reads ``dG`` and
+the shifted ``Y`` in place and sums in an order that depends on the shape alone -- another order than rocBLAS's, so the last bits of
+``W_hh.grad`` differ across the switch.
+
 Shapes served, the two the reference's networks have: one direction with 64 hidden units (``CriticNetwork.lstm``,
 ``BiCNetCritic.lstm``) and two directions with 32 (``ActorNetwork.bilstm``); one layer, ``batch_first``, zero initial state,
 float32 on the GPU.  Anything else raises: there is no CPU fallback.  Gate activations are ``v_exp_f32`` / ``v_rcp_f32``
@@ -46,7 +51,7 @@ def _shape(G, w_hh_fw, w_hh_bw):
     return b, N, dirs, H
 
 
-# ---- the overridable pieces: the two launches.  A CPU test replaces them with torch stand-ins of the same signature. ------------
+# ---- the overridable pieces: the launches.  A CPU test replaces them with torch stand-ins of the same signature. ------------
 def launch_forward(G, w_hh_fw, w_hh_bw, keep):
     """G [b,N,dirs,4H] contiguous -> (Y [b,N,dirs*H], saved [b,N,dirs,5,H] or None when not ``keep``): one ``pw_lstm_train_forward``."""
     b, N, dirs, H = _shape(G, w_hh_fw, w_hh_bw)
@@ -74,12 +79,48 @@ def launch_backward(dY, saved, w_hh_fw, w_hh_bw):
     return dG
 
 
+def launch_wgrad(dG, Y, want_fw, want_bw):
+    """dG [b,N,dirs,4H] as ``launch_backward`` returned it, Y [b,N,dirs*H] as ``launch_forward`` did -> (dW_hh forward [4H,H] or None,
+    dW_hh reverse [4H,H] or None), each where wanted: one ``pw_lstm_train_wgrad``.  The scratch is a torch tensor: a graph capture
+    sees an ordinary allocation."""
+    if dG.dim() != 4 or dG.shape[3] % 4:
+        raise ValueError('dG must be [b, N, dirs, 4 H] (got %r)' % (tuple(dG.shape),))
+    b, N, dirs, H = dG.shape[0], dG.shape[1], dG.shape[2], dG.shape[3] // 4
+    if not _served(dirs, H):
+        raise ValueError('dirs = %d, H = %d: the shapes served are %s' % (dirs, H, ' and '.join('dirs = %d, H = %d' % s for s in SERVED)))
+    if b < 1 or N < 1:
+        raise ValueError('dG must hold at least one sequence of at least one step (got %r)' % (tuple(dG.shape),))
+    if tuple(Y.shape) != (b, N, dirs * H):
+        raise ValueError('Y must be %r (got %r)' % ((b, N, dirs * H), tuple(Y.shape)))
+    if want_bw and dirs == 1:
+        raise ValueError('want_bw comes with dirs = 2 and only then')
+    if not (want_fw or want_bw):
+        raise ValueError('launch_wgrad: neither direction is wanted')
+    _lib.check_f32(dG, 'dG', FAMILY)
+    _lib.check_f32(Y, 'Y', FAMILY, dG.device, 'dG')
+    lib = _lib.load()
+    d_fw = torch.empty((4 * H, H), dtype=torch.float32, device=dG.device) if want_fw else None
+    d_bw = torch.empty((4 * H, H), dtype=torch.float32, device=dG.device) if want_bw else None
+    scratch = torch.empty(lib.pw_lstm_train_wgrad_scratch_bytes(b, N, dirs, H) // 4, dtype=torch.float32, device=dG.device)
+    p = _lib.ptr
+    _lib.check(lib.pw_lstm_train_wgrad(p(dG), p(Y), b, N, dirs, H, p(d_fw), p(d_bw), p(scratch), _lib.stream(dG.device)))
+    return d_fw, d_bw
+
+
+# Sequence lengths at which ``wgrad=True`` still takes the two GEMMs, per (dirs, H): read from profiles/lstm_wgrad.txt
+# (tools/lstm_wgrad_bench.py part (a): an N at which the GEMM path is ahead by more than the spread of its own repeats).
+WGRAD_HANDED_BACK = {(1, 64): (), (2, 32): ()}
+
+
 class _Recurrence(torch.autograd.Function):
-    """(G, w_hh_fw, w_hh_bw or None, keep) -> (Y, saved or None).  ``saved`` carries no gradient; it is kept when an input needs a
-    gradient or the caller asks for it (``FusedLSTM`` reads ``c_n`` from it)."""
+    """(G, w_hh_fw, w_hh_bw or None, keep, wgrad) -> (Y, saved or None).  ``saved`` carries no gradient; it is kept when an input needs a
+    gradient or the caller asks for it (``FusedLSTM`` reads ``c_n`` from it).  ``wgrad``: the W_hh gradients from ``launch_wgrad``."""
 
     @staticmethod
-    def forward(ctx, G, w_hh_fw, w_hh_bw, keep):
+    def forward(ctx, G, w_hh_fw, w_hh_bw, keep, wgrad=False):
+        ctx.wgrad = bool(wgrad)
+        if ctx.wgrad:   # no gradient ever arrives for ``saved``: without this autograd fills a tensor of its size with zeros per backward
+            ctx.set_materialize_grads(False)
         need = any(ctx.needs_input_grad[:3])
         Y, saved = launch_forward(G.contiguous(), w_hh_fw, w_hh_bw, need or keep)
         if need:
@@ -93,29 +134,37 @@ class _Recurrence(torch.autograd.Function):
     def backward(ctx, dY, _):
         saved, Y, w_hh_fw, w_hh_bw = ctx.saved_tensors
         H = saved.shape[4]
+        if dY is None:   # only with the switch on (gradients not materialised): nothing reached Y
+            return None, None, None, None, None
         dG = launch_backward(dY.contiguous(), saved, w_hh_fw, w_hh_bw)   # autograd hands over expanded zero-stride gradients (Y.sum())
         d_fw = d_bw = None
+        if ctx.wgrad and dG.shape[1] not in WGRAD_HANDED_BACK[(dG.shape[2], H)]:
+            want_fw, want_bw = ctx.needs_input_grad[1], w_hh_bw is not None and ctx.needs_input_grad[2]
+            if want_fw or want_bw:
+                d_fw, d_bw = launch_wgrad(dG, Y, want_fw, want_bw)
+            return (dG if ctx.needs_input_grad[0] else None), d_fw, d_bw, None, None
         # dW_hh = sum over the steps of dG_t^T h_prev: the forward direction's previous step is t - 1, the reverse direction's t + 1
         if ctx.needs_input_grad[1]:
             d_fw = dG[:, 1:, 0].reshape(-1, 4 * H).t() @ Y[:, :-1, :H].reshape(-1, H)
         if w_hh_bw is not None and ctx.needs_input_grad[2]:
             d_bw = dG[:, :-1, 1].reshape(-1, 4 * H).t() @ Y[:, 1:, H:].reshape(-1, H)
-        return (dG if ctx.needs_input_grad[0] else None), d_fw, d_bw, None
+        return (dG if ctx.needs_input_grad[0] else None), d_fw, d_bw, None, None
 
 
-def _recurrence(G, w_hh_fw, w_hh_bw, keep):
+def _recurrence(G, w_hh_fw, w_hh_bw, keep, wgrad=False):
     if not torch.is_grad_enabled():   # under no_grad the function still sees requires_grad inputs: detached, it stores nothing
         G, w_hh_fw, w_hh_bw = G.detach(), w_hh_fw.detach(), None if w_hh_bw is None else w_hh_bw.detach()
-    return _Recurrence.apply(G, w_hh_fw, w_hh_bw, keep)
+    return _Recurrence.apply(G, w_hh_fw, w_hh_bw, keep, wgrad)
 
 
-def lstm_recurrence(G, w_hh_fw, w_hh_bw=None):
+def lstm_recurrence(G, w_hh_fw, w_hh_bw=None, wgrad=False):
     """The recurrent part of a one-layer LSTM from zero initial state, differentiable once in ``G`` and both ``W_hh``.
 
     ``G [b,N,dirs,4H] = x W_ih^T + b_ih + b_hh`` (gate order i, f, g, o; direction 1 walks the steps backwards), ``w_hh_* [4H,H]`` as
     ``nn.LSTM`` keeps them, ``w_hh_bw`` with ``dirs = 2`` only.  Returns ``Y [b,N,dirs*H] = [h_forward | h_reverse]``.  When no input
-    needs a gradient the launch stores no activations."""
-    return _recurrence(G, w_hh_fw, w_hh_bw, False)[0]
+    needs a gradient the launch stores no activations.  ``wgrad``: the backward forms the ``W_hh`` gradients with ``launch_wgrad`` (one
+    call for the directions that need one, none when neither does) instead of two sliced copies and a GEMM per direction."""
+    return _recurrence(G, w_hh_fw, w_hh_bw, False, wgrad)[0]
 
 
 # Sequence lengths that FusedLSTM.forward hands back to nn.LSTM.forward, per (dirs, H): read from profiles/lstm_train.txt (tools/lstm_train_bench.py
@@ -189,7 +238,7 @@ class FusedLSTM(nn.LSTM):
 
     def _from_gates(self, G, w_bw):
         dirs, H = G.shape[2], self.hidden_size
-        Y, saved = _recurrence(G, self.weight_hh_l0, w_bw, True)
+        Y, saved = _recurrence(G, self.weight_hh_l0, w_bw, True, getattr(self, 'wgrad', False))
         if dirs == 2:
             h_n = torch.stack([Y[:, -1, :H], Y[:, 0, H:]], dim=0)
             c_n = torch.stack([saved[:, -1, 0, 4], saved[:, 0, 1, 4]], dim=0)
@@ -202,11 +251,15 @@ def _modules(module):
     return module.modules() if isinstance(module, nn.Module) else ()
 
 
-def fuse_lstm(module):
+def fuse_lstm(module, wgrad=False):
     """Every plain ``nn.LSTM`` inside ``module`` that ``FusedLSTM`` serves becomes one, by a swap of ``__class__``: parameters and
     ``state_dict`` keys stay (saved ``*_actor.pt`` / ``*_critic.pt`` files load unchanged, ``FusedActor`` / ``FusedCritic`` keep
     reading the same tensors in place), and ``copy.deepcopy`` of the network keeps it -- an instance-level ``forward`` would not
-    survive the deep copy a Trainer takes for its target networks.  Returns the number of modules swapped."""
+    survive the deep copy a Trainer takes for its target networks.  Returns the number of modules swapped.
+
+    ``wgrad=True``: the swapped LSTMs, and those ``module`` already holds fused, take their ``W_hh`` gradients from ``launch_wgrad``.
+    The mode is a plain instance attribute (``m.wgrad``): a deep copy keeps it, ``state_dict`` does not hold it, ``unfuse_lstm`` removes
+    it.  Those already fused are not counted."""
     n = 0
     for m in _modules(module):
         if type(m) is nn.LSTM:
@@ -215,6 +268,8 @@ def fuse_lstm(module):
                 m.__class__ = nn.LSTM
             else:
                 n += 1
+        if wgrad and type(m) is FusedLSTM:
+            m.wgrad = True
     return n
 
 
@@ -224,6 +279,7 @@ def unfuse_lstm(module):
     for m in _modules(module):
         if type(m) is FusedLSTM:
             m.__class__ = nn.LSTM
+            m.__dict__.pop('wgrad', None)
             n += 1
     return n
 
@@ -232,3 +288,18 @@ def fuse_trainer(trainer):
     """``fuse_lstm`` on ``trainer.actor``, ``trainer.critic`` and on the target networks that are still modules (``accelerate_trainer(
     targets=True)`` has replaced them by wrappers on the no-gradient kernels).  Returns the number of LSTMs swapped."""
     return sum(fuse_lstm(getattr(trainer, name, None)) for name in ('actor', 'critic', 'target_actor', 'target_critic'))
+
+
+def wgrad_trainer(trainer, dry=False):
+    """Every ``FusedLSTM`` of ``trainer.actor``, ``trainer.critic`` and the target networks that are still modules takes its ``W_hh``
+    gradients from ``launch_wgrad`` (``fuse_lstm(wgrad=True)``'s mode, for LSTMs that are fused already).  Returns their number;
+    ``ValueError`` when there is none.  ``dry``: only the check."""
+    found = [m for name in ('actor', 'critic', 'target_actor', 'target_critic') for m in _modules(getattr(trainer, name, None))
+             if type(m) is FusedLSTM]
+    if not found:
+        raise ValueError('wgrad=True: the trainer holds no fused LSTM (accelerate_trainer(..., lstm=True, wgrad=True) / fused_lstm=True); '
+                         'the W_hh gradients of a plain nn.LSTM are MIOpen\'s')
+    if not dry:
+        for m in found:
+            m.wgrad = True
+    return len(found)

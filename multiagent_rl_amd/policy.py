@@ -365,7 +365,7 @@ class FusedExploration(object):
 
 
 def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False, graph=False, graph_warmup=3,
-                       sampling=False, sampling_seed=None, front=False):
+                       sampling=False, sampling_seed=None, front=False, wgrad=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -418,7 +418,15 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     kernels with gradient (``multiagent_rl_amd.dense.fuse_front``: a class swap to a subclass of the network's own class, one launch
     forward and two backward instead of a dozen) for ``trainer.actor``, ``trainer.critic`` and the target networks that are still
     modules.  It needs ``lstm=True`` or LSTMs that are fused already (``ValueError`` otherwise) and composes with ``attention`` in
-    either order.  Opt-in because the sums run in another order than rocBLAS's; it is not a precondition of ``graph=True``."""
+    either order.  Opt-in because the sums run in another order than rocBLAS's; it is not a precondition of ``graph=True``.
+
+    ``wgrad=True`` takes the two ``W_hh`` gradients of every fused LSTM off torch (``multiagent_rl_amd.lstm.launch_wgrad``: one call of
+    two device kernels per LSTM backward instead of two strided copies and a GEMM per direction).  It needs ``lstm=True`` or LSTMs that
+    are fused already: ``ValueError`` if no LSTM is or becomes fused.  Opt-in because the sums run in another order than rocBLAS's; it
+    is not a precondition of ``graph=True``."""
+    if wgrad and not lstm:   # refused before anything is patched
+        from .lstm import wgrad_trainer
+        wgrad_trainer(trainer, dry=True)
     if graph:   # what this call will not put right is refused before anything is patched (and before the GPU is needed)
         from .graph import missing_for_graph
         mended = [name for name, on in (('targets', targets), ('optimizer', optimizer), ('lstm', lstm), ('attention', attention)) if on]
@@ -439,6 +447,9 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     if lstm:
         from .lstm import fuse_trainer
         fx.fused_lstms = fuse_trainer(trainer)
+    if wgrad:
+        from .lstm import wgrad_trainer
+        fx.wgrad_lstms = wgrad_trainer(trainer)   # ValueError: lstm=True found no LSTM that FusedLSTM serves
     if attention:
         from .attention import fuse_trainer as fuse_attention_trainer
         fx.fused_attentions = fuse_attention_trainer(trainer)
