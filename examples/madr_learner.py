@@ -32,6 +32,9 @@ the default is the stock expression.
 ``Trainer(..., fused_wgrad=True)``: the two ``W_hh`` gradients of every fused LSTM come from ``multiagent_rl_amd.lstm.launch_wgrad`` (two
 device kernels per LSTM backward) instead of two strided copies and a GEMM per direction; it needs ``fused_lstm``, and the default is the
 GEMMs (the sums run in another order).
+``Trainer(..., fused_heads=True)``: the ReLU on the actor's BiLSTM output and every output layer of actor and critic (and of the target
+networks copied from them) run, forward and backward, on the HIP kernels (``multiagent_rl_amd.heads.fuse_heads``: one launch forward
+for all heads of a network, two backward); it needs ``fused_front``, and the default is the stock expression.
 """
 import copy
 import os
@@ -62,7 +65,9 @@ class Trainer(object):
 
     def __init__(self, actor, critic, memory, action_type='Discrete', batch_size=1024, lr=1e-2, device=None, fused_optimizer=False,
                  fused_lstm=False, fused_attention=False, graph_update=False, fused_sampling=False, sampling_seed=None,
-                 fused_front=False, fused_wgrad=False):
+                 fused_front=False, fused_wgrad=False, fused_heads=False):
+        if fused_heads and not fused_front:
+            raise ValueError('fused_heads needs fused_front: the fused output layers are the last lines of the swapped forwards')
         if fused_wgrad and not fused_lstm:
             raise ValueError('fused_wgrad needs fused_lstm: the W_hh gradients of a plain nn.LSTM are MIOpen\'s')
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
@@ -82,6 +87,10 @@ class Trainer(object):
             from multiagent_rl_amd.dense import fuse_front
             fuse_front(self.actor)
             fuse_front(self.critic)
+        if fused_heads:   # before the deep copies: the mode is an instance attribute, which they keep
+            from multiagent_rl_amd.heads import fuse_heads
+            fuse_heads(self.actor)
+            fuse_heads(self.critic)
         self.target_actor, self.target_critic = copy.deepcopy(self.actor).eval(), copy.deepcopy(self.critic).eval()
         self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr)
         self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr)

@@ -28,7 +28,10 @@ learner's own ``fused_attention`` switch, or ``accelerate_trainer(.., attention=
 ``--fused-front`` runs dense1, the ReLU and the LSTM's input projection of the learner's networks with gradient on the HIP kernels
 (``multiagent_rl_amd.dense``: the learner's own ``fused_front`` switch, or ``accelerate_trainer(.., front=True)`` with ``--reference``; needs ``--fused-lstm``),
 ``--fused-wgrad`` takes the ``W_hh`` gradients of the fused LSTMs from the HIP kernels as well (``multiagent_rl_amd.lstm.launch_wgrad``:
-the learner's own ``fused_wgrad`` switch, or ``accelerate_trainer(.., wgrad=True)`` with ``--reference``; needs ``--fused-lstm``).
+the learner's own ``fused_wgrad`` switch, or ``accelerate_trainer(.., wgrad=True)`` with ``--reference``; needs ``--fused-lstm``),
+``--fused-heads`` runs the ReLU on the actor's BiLSTM output and every output layer of the learner's networks with gradient on the HIP
+kernels (``multiagent_rl_amd.heads``: the learner's own ``fused_heads`` switch, or ``accelerate_trainer(.., heads=True)`` with
+``--reference``; needs ``--fused-front``).
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -99,7 +102,14 @@ def main(argv=None):
                          "strided copies and a GEMM per direction (madr_learner's fused_wgrad switch; with --reference: "
                          'accelerate_trainer(.., wgrad=True)); needs --fused-lstm; off by default: the sums run in another order than '
                          'the stock GEMMs')
+    ap.add_argument('--fused-heads', action='store_true',
+                    help="the ReLU on the actor's BiLSTM output and every output layer of the learner's networks run, forward and "
+                         "backward, on the HIP kernels (madr_learner's fused_heads switch; with --reference: "
+                         'accelerate_trainer(.., heads=True)); needs --fused-front; off by default: the sums run in another order than '
+                         'the stock GEMMs')
     args = ap.parse_args(argv)
+    if args.fused_heads and not args.fused_front:
+        ap.error('--fused-heads needs --fused-front: the fused output layers are the last lines of the swapped forwards')
     if args.fused_front and not args.fused_lstm:
         ap.error('--fused-front needs --fused-lstm: the fused front feeds the fused recurrence')
     if args.fused_wgrad and not args.fused_lstm:
@@ -161,6 +171,8 @@ def main(argv=None):
                 k['fused_front'] = True
             if args.fused_wgrad and not args.reference:
                 k['fused_wgrad'] = True
+            if args.fused_heads and not args.reference:
+                k['fused_heads'] = True
             if args.graph_update and not args.reference:
                 k['graph_update'] = True     # madr_learner installs the fused targets and the graphed update itself
                 return plain_trainer(*a, **k)
@@ -169,7 +181,8 @@ def main(argv=None):
                 accelerate_trainer(learner, targets=args.fused_targets, optimizer=args.fused_optimizer and args.reference,
                                    lstm=args.fused_lstm and args.reference, attention=args.fused_attention and args.reference,
                                    graph=args.graph_update, sampling=args.fused_sampling and args.reference,
-                                   front=args.fused_front and args.reference, wgrad=args.fused_wgrad and args.reference)
+                                   front=args.fused_front and args.reference, wgrad=args.fused_wgrad and args.reference,
+                                   heads=args.fused_heads and args.reference)
             return learner
 
     rank, world = int(os.environ.get('RANK', '0')), int(os.environ.get('WORLD_SIZE', '1'))

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 120 /* 0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 121 /* 0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -739,6 +739,31 @@ int pw_front_train_backward(const float *dG, const float *x0, int32_t d0, const 
                             size_t scratch_bytes, void *stream);
 /* The bytes of scratch one pw_front_train_backward of this shape needs (0 for a shape that is not served). */
 size_t pw_front_train_scratch_bytes(int64_t rows, int32_t d0, int32_t d1);
+
+/* ---- the output layers of the learner's networks with gradient (translation unit pworld_head.hip) -----------------------------------
+ * A = relu ? max(X, 0) : X (a NaN stays one);  out_k = A W_k^T + b_k for k < heads, exact float32:
+ *   X [rows,64]; w[k] [n[k],64], b[k] [n[k]] as nn.Linear keeps them, read in place; out[k] [rows,n[k]]; w, b, n and out hold `heads` entries.
+ * Served: 1 <= heads <= 3, 1 <= n[k] <= 104, rows >= 1; anything else, a null argument or a pointer that is not 4-byte aligned:
+ * PW_EINVAL naming it, nothing launched.  One launch for all heads; X is read once and A is never stored. */
+int pw_head_train_forward(const float *X, int64_t rows, int32_t relu, int32_t heads, const float *const *w, const float *const *b,
+                          const int32_t *n, float *const *out, void *stream);
+/* dOut[k] [rows,n[k]] contiguous, or NULL for a head that received no gradient, and the forward's X ->
+ *   dX [rows,64] = (sum over the heads with a dOut of dOut_k W_k) o (relu ? X > 0 : 1), or nothing when dX is NULL;
+ *   dW[k] [n[k],64] = dOut_k^T A;  db[k] [n[k]] = sum over rows of dOut_k   for every head with a dOut.
+ * A head whose dOut is NULL adds nothing to dX, its dW[k] and db[k] must be NULL too and nothing is computed for it; a launch in which
+ * only head 0 has a dOut gives the bits of the one-head launch.  Every dOut NULL, a dW or db beside a NULL dOut, a missing dW or db
+ * beside a dOut, a dX that is not 16-byte aligned, any other pointer that is not 4-byte aligned: PW_EINVAL, nothing launched.
+ * Two launches: the main kernel leaves one partial sum per workgroup and element in `scratch` (at least
+ * pw_head_train_scratch_bytes(rows, heads, n) bytes), the second adds them as a balanced tree over the workgroups (db, and that tree, as
+ * compensated sums: a bias gradient that nearly cancels keeps one rounding of its result, not of its partial sums); with rows <= 16 one
+ * workgroup holds every row and the main kernel stores the results itself (one launch).  The number of workgroups and the rows of
+ * each follow from `rows` alone and no floating-point atomic exists: the same inputs give the same bits on every launch. */
+int pw_head_train_backward(const float *const *dOut, const float *X, int64_t rows, int32_t relu, int32_t heads, const float *const *w,
+                           const int32_t *n, float *dX, float *const *dW, float *const *db, void *scratch, size_t scratch_bytes,
+                           void *stream);
+/* The bytes of scratch one pw_head_train_backward of this shape needs, whichever of its heads have a dOut (0 for a shape that is not
+ * served). */
+size_t pw_head_train_scratch_bytes(int64_t rows, int32_t heads, const int32_t *n);
 
 #ifdef __cplusplus
 }

@@ -196,6 +196,12 @@ SIGNATURES = {
                                           C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)] +
                                 [C.c_void_p] * 3 + [C.c_size_t, C.c_void_p]),
     'pw_front_train_scratch_bytes': (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    'pw_head_train_forward': (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_void_p]),
+    'pw_head_train_backward': (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
+                                         C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
+    'pw_head_train_scratch_bytes': (C.c_size_t, [C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
 }
 
 

@@ -24,6 +24,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from .heads import output_layers
 
 HIDDEN = 64       # the hidden size served
 MAX_STEPS = 64    # the longest agent axis served (pw_critic_forward's bound)
@@ -177,7 +178,7 @@ class _Fused(object):
             return self._unfused.forward(self, obs, action)
         steps, _ = lstm_trunk(self, obs, action)   # the query is steps[:, -1] = h_n[-1] (nn.LSTM computes the same number; FusedLSTM slices it)
         ctx = attention_pool(steps, relu=not self._model)
-        return (self.dense2(ctx), self.dense3(ctx)) if self._model else self.dense2(ctx)
+        return output_layers(self, ctx, 'model' if self._model else 'attention')
 
 
 class FusedAttention(_Fused):

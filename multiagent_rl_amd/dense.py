@@ -19,12 +19,12 @@ does not reproduce across the switch -- which is why it is opt-in everywhere (``
 """
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from . import attention as _attention
 from .attention import _fused_class, _linear, _reclass, _without, attend, attention_pool, critic_form
+from .heads import output_layers
 from .lstm import SERVED, FusedLSTM
 
 HIDDEN = 64       # dense1's width = the LSTM's input size
@@ -215,26 +215,24 @@ class FusedFrontCritic(FusedFront):
         form = critic_form(self)[0]
         steps, h_n = self._front_trunk(obs, action)
         if form == 'steps':
-            return self.dense2(steps)
+            return output_layers(self, steps, 'steps')
         model = form == 'model'
         if isinstance(self, _attention._Fused) and 1 <= steps.shape[1] <= _attention.MAX_STEPS and steps.shape[1] not in _attention.HANDED_BACK:
             ctx = attention_pool(steps, relu=not model)
         else:
             ctx = attend(steps, h_n[-1], relu=not model)
-        return (self.dense2(ctx), self.dense3(ctx)) if model else self.dense2(ctx)
+        return output_layers(self, ctx, form)
 
 
 class FusedFrontActor(FusedFront):
     """An actor recognised by ``actor_form``: ``front_gates`` on the observation alone, then the ReLU and the head(s) as
-    ``policy.ActorNetwork`` / ``policy.ModelActorNetwork`` write them."""
+    ``policy.ActorNetwork`` / ``policy.ModelActorNetwork`` write them (``heads.output_layers``)."""
 
     def forward(self, obs):
         if obs.dim() == 3 and obs.shape[1] in HANDED_BACK:
             return self._unfused.forward(self, obs)
         hid, _ = front_gates(_linear(self.dense1, wrapped=True), self.bilstm, obs, None)
-        hid = F.relu(hid)
-        policy = [self.dense2_1(hid), self.dense2_2(hid)] if actor_form(self) == 2 else self.dense2(hid)
-        return (policy, self.dense3(hid)) if getattr(self, 'dense3', None) is not None else policy
+        return output_layers(self, hid, 'actor')
 
 
 def actor_form(m):
@@ -288,7 +286,10 @@ def fuse_front(module):
 
 def unfuse_front(module):
     """The reverse of ``fuse_front``: every swapped network gets exactly the class it had without it (a fused-attention class stays
-    one).  Returns the number swapped back."""
+    one).  The ``fused_heads`` mode (``heads.fuse_heads``), which lives in the swapped forwards' last lines, goes with it.  Returns the
+    number swapped back."""
+    from .heads import unfuse_heads
+    unfuse_heads(module)
     return _reclass(module, lambda m: _without(type(m), FusedFront) if isinstance(m, FusedFront) else None)
 
 

@@ -365,7 +365,7 @@ class FusedExploration(object):
 
 
 def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=False, attention=False, graph=False, graph_warmup=3,
-                       sampling=False, sampling_seed=None, front=False, wgrad=False):
+                       sampling=False, sampling_seed=None, front=False, wgrad=False, heads=False):
     """Patch an instance of the reference's ``Trainer`` in place: ``get_exploration_action`` runs on the one-launch
     HIP actor, and the weight snapshot is refreshed after every ``optimize()`` (and ``load_models``).  Everything
     else of the learner is untouched.  Returns the ``FusedExploration`` object.
@@ -423,7 +423,17 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     ``wgrad=True`` takes the two ``W_hh`` gradients of every fused LSTM off torch (``multiagent_rl_amd.lstm.launch_wgrad``: one call of
     two device kernels per LSTM backward instead of two strided copies and a GEMM per direction).  It needs ``lstm=True`` or LSTMs that
     are fused already: ``ValueError`` if no LSTM is or becomes fused.  Opt-in because the sums run in another order than rocBLAS's; it
-    is not a precondition of ``graph=True``."""
+    is not a precondition of ``graph=True``.
+
+    ``heads=True`` runs what every pass with gradient ends with -- the ReLU on the actor's BiLSTM output and every output layer
+    (``dense2``, ``dense2_1`` + ``dense2_2``, ``dense3``) -- on the HIP kernels with gradient (``multiagent_rl_amd.heads.fuse_heads``: a
+    plain attribute on the swapped networks, one launch forward for all heads and two backward) for ``trainer.actor``,
+    ``trainer.critic`` and the target networks that are still modules.  It needs ``front=True`` or networks that ``dense.fuse_front``
+    has swapped already (``ValueError`` otherwise): the fused output layers are the last lines of the swapped forwards.  Opt-in because
+    the sums run in another order than rocBLAS's; it is not a precondition of ``graph=True`` and composes with it."""
+    if heads and not front:   # refused before anything is patched
+        from .heads import fuse_trainer as fuse_heads_trainer
+        fuse_heads_trainer(trainer, dry=True)
     if wgrad and not lstm:   # refused before anything is patched
         from .lstm import wgrad_trainer
         wgrad_trainer(trainer, dry=True)
@@ -456,6 +466,9 @@ def accelerate_trainer(trainer, seed=0, targets=False, optimizer=False, lstm=Fal
     if front:
         from .dense import fuse_trainer as fuse_front_trainer
         fx.fused_fronts = fuse_front_trainer(trainer)
+    if heads:
+        from .heads import fuse_trainer as fuse_heads_trainer
+        fx.fused_heads = fuse_heads_trainer(trainer)
     sampler = None
     if sampling:
         from .sampling import install
