@@ -35,6 +35,9 @@ int fail(int code, const std::string &msg)
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the address is no multiple of `to` (a power of two); NULL is aligned
+bool misaligned(const void *p, uintptr_t to = 4) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
+
 // Kernels that ask for more than 64 KB of dynamic LDS need the opt-in once per (kernel, DEVICE): a process driving
 // several GPUs must not skip it on the second one.  The device's bit is set only AFTER hipFuncSetAttribute succeeded
 // (lds_optin_done), atomically: a failed call is retried by the next launch, and two host threads on different devices

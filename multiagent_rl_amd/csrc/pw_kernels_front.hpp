@@ -10,7 +10,7 @@
 // four accumulator registers are four consecutive features of one row and leave as one 16-byte store.
 // Long sums are split so that no chain is much longer than 64 terms (a chain's rounding error grows with its length, and a dependent
 // chain of matrix instructions also waits for itself): a dot product's k steps go round-robin into 2 or 4 chains that are added as a
-// balanced tree at the end, a tile's 16 rows of a column sum are a balanced tree, and so are the partial sums of the workgroups.
+// balanced tree at the end; the sums over the rows are pw_train_sums.hpp's.
 //
 // Forward: a workgroup of four waves owns a tile of 16 rows.  The input rows are staged side by side in LDS (no concatenated copy
 // exists in memory; columns up to the next multiple of 8 are zero).  Wave w forms hidden units 16 w .. 16 w + 15 (two chains over the k
@@ -18,57 +18,39 @@
 // forms gate columns 64 w .. 64 w + 63 (two chains over the 64 hidden units) and adds b_ih + b_hh.  Weights are read where nn.Linear /
 // nn.LSTM keep them, one direction's W_ih after the other's: nothing is concatenated.
 //
-// Backward: workgroup g owns the row tiles g T .. g T + T - 1 (T and the number of workgroups follow from `rows` alone:
-// front_bwd_split).  Per tile: dG, [x0 | x1] and hid staged in LDS; dHid = (dG W_ih) o (hid > 0) by wave w for its 16 units (four
-// chains over the 256 gate columns), to LDS; then the tile's contribution to dW_ih (= dG^T hid), dW1 (= dHid^T [x0 | x1]) and the
-// two column sums (db_gate, db1) is ADDED INTO REGISTERS that live across the workgroup's tiles (rows ascending), and dx = dHid W1 leaves
-// for the columns whose pointer is given.  At the end every workgroup stores its partial sums (front_partial_floats numbers) to its
-// slot of the caller's scratch.  pw_front_train_reduce_kernel then adds the slots of every element as a balanced tree over the slot
-// numbers, one thread per element: no floating-point atomics anywhere, and the order of every sum is a function of (rows, d0, d1)
-// only -- the same inputs give the same bits on every launch, eager or replayed from a graph.
+// Backward: the ordered sums of pw_train_sums.hpp (tiles, workgroups, slots, tree; all plain, none compensated).  Per tile: dG,
+// [x0 | x1] and hid staged in LDS; dHid = (dG W_ih) o (hid > 0) by wave w for its 16 units (four chains over the 256 gate columns), to
+// LDS; then the tile's contribution to dW_ih (= dG^T hid), dW1 (= dHid^T [x0 | x1]) and the two column sums (db_gate, db1) is added
+// into the workgroup's registers, and dx = dHid W1 leaves for the columns whose pointer is given.  A slot holds front_partial_floats
+// numbers; pw_front_train_reduce_kernel adds the slots and scatters the sums to the six results.  The order of every sum is a
+// function of (rows, d0, d1) only.
 // Addresses: parameters and inputs are read with 4-byte loads (nn.LSTM's tensors may be views of one flat buffer); hid, G and the
 // scratch, which the caller allocates for these launches, are 16-byte aligned.
 #pragma once
 
 #include "pw_common.hpp"
 #include "pw_lstm_math.hpp"
+#include "pw_train_sums.hpp"
 
 namespace {
 
 constexpr int kFrontHid = 64;        // dense1's width = the LSTM's input size
 constexpr int kFrontGates = 256;     // dirs * 4 H
-constexpr int kFrontTile = 16;       // rows per tile = the columns of the matrix instruction
-constexpr int kFrontThreads = 256;   // four waves
 constexpr int kFrontMaxD0 = 104, kFrontMaxD1 = 16;
 constexpr int kFrontKTiles = 8;      // 16-column tiles of [x0 | x1]: ceil(120 / 16)
-// LDS row strides in words, each = 20 mod 32: a tile is read both along its rows (B operand: lane = row) and across them
-// (A operand: lane = column), and this residue keeps both to at most three lanes per bank; a multiple of 4 for the 16-byte writes
-constexpr int kFrontXS = 128 + 20, kFrontHS = 64 + 20, kFrontGS = 256 + 20;
-constexpr int kFrontMaxGroups = 128; // workgroups (= partial sums per element) of one backward launch
-
-typedef float front_f4 __attribute__((ext_vector_type(4)));
+constexpr int kFrontXS = train_lds_stride(128), kFrontHS = train_lds_stride(64), kFrontGS = train_lds_stride(256);   // LDS row strides
 
 struct FrontLds { float *xs, *hs, *dgs, *dhs; uint32_t bytes; };
 // xs [16][kFrontXS]: [x0 | x1] of the tile's rows; hs [16][kFrontHS]: hid; backward only: dgs [16][kFrontGS]: dG, dhs [16][kFrontHS]: dHid
 __host__ __device__ inline FrontLds front_lds(bool backward, unsigned char *raw = nullptr)
 {
     LdsCursor c{reinterpret_cast<float *>(raw)}; FrontLds o;
-    o.xs = c.take<float>(kFrontTile * kFrontXS, 16); o.hs = c.take<float>(kFrontTile * kFrontHS, 16);
+    o.xs = c.take<float>(kTrainTile * kFrontXS, 16); o.hs = c.take<float>(kTrainTile * kFrontHS, 16);
     o.dgs = o.dhs = nullptr;
-    if (backward) { o.dgs = c.take<float>(kFrontTile * kFrontGS, 16); o.dhs = c.take<float>(kFrontTile * kFrontHS, 16); }
+    if (backward) { o.dgs = c.take<float>(kTrainTile * kFrontGS, 16); o.dhs = c.take<float>(kTrainTile * kFrontHS, 16); }
     o.bytes = 4 * c.at; return o;
 }
 
-// How a backward launch splits `rows`: T tiles per workgroup, `groups` workgroups; the summation order follows from it
-struct FrontSplit { long tiles; long per_group; int groups; };
-__host__ __device__ inline FrontSplit front_bwd_split(long rows)
-{
-    FrontSplit s;
-    s.tiles = (rows + kFrontTile - 1) / kFrontTile;
-    s.per_group = (s.tiles + kFrontMaxGroups - 1) / kFrontMaxGroups;
-    s.groups = (int)((s.tiles + s.per_group - 1) / s.per_group);
-    return s;
-}
 // one workgroup's partial sums: dW_ih [256][64] (direction 0's rows, then direction 1's), dW1 [64][d0 + d1], db_gate [256], db1 [64]
 __host__ __device__ inline long front_partial_floats(int K) { return (long)kFrontGates * kFrontHid + (long)kFrontHid * K + kFrontGates + kFrontHid; }
 
@@ -98,16 +80,11 @@ struct FrontReduceArgs {
     int groups, K, dirs;
 };
 
-__device__ __forceinline__ front_f4 front_mfma(const float a, const float b, const front_f4 acc)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-}
-
 // [x0 | x1] of rows r0 .. r0 + 15 -> xs, columns 0 .. width - 1 (width a multiple of 4, <= 128); zero past d0 + d1 and past the last row
 __device__ __forceinline__ void front_stage_x(float *xs, const float *__restrict__ x0, const float *__restrict__ x1, const int d0,
                                               const int d1, const long r0, const long rows, const int width, const int tid)
 {
-    for (int i = tid; i < kFrontTile * width; i += kFrontThreads) {
+    for (int i = tid; i < kTrainTile * width; i += kTrainThreads) {
         const int r = i / width, k = i - r * width;
         float v = 0.0f;
         if (r0 + r < rows) {
@@ -118,25 +95,12 @@ __device__ __forceinline__ void front_stage_x(float *xs, const float *__restrict
     }
 }
 
-// the sum of a tile's 16 rows of one column, as a balanced tree (rows 2 i and 2 i + 1 first)
-__device__ __forceinline__ float front_column_sum(const float *col, const int stride)
-{
-    float v[kFrontTile];
-#pragma unroll
-    for (int r = 0; r < kFrontTile; ++r) v[r] = col[r * stride];
-#pragma unroll
-    for (int n = kFrontTile / 2; n >= 1; n >>= 1)
-#pragma unroll
-        for (int i = 0; i < n; ++i) v[i] = v[2 * i] + v[2 * i + 1];
-    return v[0];
-}
-
-__global__ void __launch_bounds__(kFrontThreads) pw_front_train_forward_kernel(const FrontFwdArgs A)
+__global__ void __launch_bounds__(kTrainThreads) pw_front_train_forward_kernel(const FrontFwdArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char front_smem[];
     const FrontLds L = front_lds(false, front_smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 15, hi = lane >> 4;
-    const long r0 = (long)blockIdx.x * kFrontTile;
+    const long r0 = (long)blockIdx.x * kTrainTile;
     const int K = A.d0 + A.d1, kpairs = (K + 7) >> 3;
     const bool row_ok = r0 + lo < A.rows;
 
@@ -145,15 +109,15 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_forward_kernel(c
 
     // dense1: units 16 wave .. + 15 of the tile's rows; even and odd k steps in two chains, k ascending in each
     {
-        front_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
+        train_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
         const float *wrow = A.w1 + (size_t)(16 * wave + lo) * K;
         const float *xrow = L.xs + lo * kFrontXS;
         for (int s = 0; s < kpairs; ++s) {
             const int k = 8 * s + hi;
-            even = front_mfma(k < K ? wrow[k] : 0.0f, xrow[k], even);
-            odd = front_mfma(k + 4 < K ? wrow[k + 4] : 0.0f, xrow[k + 4], odd);
+            even = train_mfma(k < K ? wrow[k] : 0.0f, xrow[k], even);
+            odd = train_mfma(k + 4 < K ? wrow[k + 4] : 0.0f, xrow[k + 4], odd);
         }
-        const front_f4 acc = even + odd;
+        const train_f4 acc = even + odd;
         const int u = 16 * wave + 4 * hi;
         float4 h;
         h.x = relu_fwd(acc[0] + A.b1[u + 0]); h.y = relu_fwd(acc[1] + A.b1[u + 1]);
@@ -169,16 +133,16 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_forward_kernel(c
     const int g0 = second ? c0 - 128 : c0;                             // first gate row inside the direction's tensors
     const float *w = (second ? A.w_ih1 : A.w_ih0) + (size_t)(g0 + lo) * kFrontHid + hi;
     const float *hrow = L.hs + lo * kFrontHS + hi;
-    front_f4 g[4], g_odd[4];                                          // even and odd k steps in two chains, as above
+    train_f4 g[4], g_odd[4];                                          // even and odd k steps in two chains, as above
 #pragma unroll
-    for (int t = 0; t < 4; ++t) g[t] = g_odd[t] = front_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int t = 0; t < 4; ++t) g[t] = g_odd[t] = train_f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int s = 0; s < 16; s += 2) {
         const float b0 = hrow[4 * s], b1 = hrow[4 * s + 4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            g[t] = front_mfma(w[t * 16 * kFrontHid + 4 * s], b0, g[t]);
-            g_odd[t] = front_mfma(w[t * 16 * kFrontHid + 4 * s + 4], b1, g_odd[t]);
+            g[t] = train_mfma(w[t * 16 * kFrontHid + 4 * s], b0, g[t]);
+            g_odd[t] = train_mfma(w[t * 16 * kFrontHid + 4 * s + 4], b1, g_odd[t]);
         }
     }
 #pragma unroll
@@ -194,32 +158,32 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_forward_kernel(c
     }
 }
 
-__global__ void __launch_bounds__(kFrontThreads) pw_front_train_backward_kernel(const FrontBwdArgs A)
+__global__ void __launch_bounds__(kTrainThreads) pw_front_train_backward_kernel(const FrontBwdArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char front_smem[];
     const FrontLds L = front_lds(true, front_smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 15, hi = lane >> 4;
     const int K = A.d0 + A.d1, ktiles = (K + 15) >> 4;
-    const FrontSplit S = front_bwd_split(A.rows);
+    const TrainSplit S = train_split(A.rows);
     const long first = (long)blockIdx.x * A.per_group;
     const long last = first + A.per_group < S.tiles ? first + A.per_group : S.tiles;
 
-    front_f4 dwih[16], dw1[kFrontKTiles];
+    train_f4 dwih[16], dw1[kFrontKTiles];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) dwih[i] = front_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = 0; i < 16; ++i) dwih[i] = train_f4{0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-    for (int i = 0; i < kFrontKTiles; ++i) dw1[i] = front_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int i = 0; i < kFrontKTiles; ++i) dw1[i] = train_f4{0.0f, 0.0f, 0.0f, 0.0f};
     float gate_sum = 0.0f, hid_sum = 0.0f;   // column tid of dG; column tid of dHid (tid < 64)
 
     // W_ih^T as the A operand of dHid: row = unit 16 wave + lo, k = gate column
     const float *wt0 = A.w_ih0 + 16 * wave + lo, *wt1 = (A.dirs == 2 ? A.w_ih1 : A.w_ih0 + 128 * kFrontHid) + 16 * wave + lo;
 
     for (long tile = first; tile < last; ++tile) {
-        const long r0 = tile * kFrontTile;
+        const long r0 = tile * kTrainTile;
         const bool row_ok = r0 + lo < A.rows;
         front_stage_x(L.xs, A.x0, A.x1, A.d0, A.d1, r0, A.rows, 16 * ktiles, tid);
 #pragma unroll
-        for (int r = 0; r < kFrontTile; ++r)
+        for (int r = 0; r < kTrainTile; ++r)
             L.dgs[r * kFrontGS + tid] = r0 + r < A.rows ? A.dG[(size_t)(r0 + r) * kFrontGates + tid] : 0.0f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -230,19 +194,19 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_backward_kernel(
 
         // dHid of units 16 wave .. + 15: k ascending over the gate columns; the ReLU's mask from hid
         {
-            front_f4 part[4];                                         // k step s into chain s % 4; (0 + 1) + (2 + 3) at the end
+            train_f4 part[4];                                         // k step s into chain s % 4; (0 + 1) + (2 + 3) at the end
 #pragma unroll
-            for (int j = 0; j < 4; ++j) part[j] = front_f4{0.0f, 0.0f, 0.0f, 0.0f};
+            for (int j = 0; j < 4; ++j) part[j] = train_f4{0.0f, 0.0f, 0.0f, 0.0f};
             const float *grow = L.dgs + lo * kFrontGS + hi;
 #pragma unroll 2
             for (int s = 0; s < 32; s += 4)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) part[j] = front_mfma(wt0[(4 * (s + j) + hi) * kFrontHid], grow[4 * (s + j)], part[j]);
+                for (int j = 0; j < 4; ++j) part[j] = train_mfma(wt0[(4 * (s + j) + hi) * kFrontHid], grow[4 * (s + j)], part[j]);
 #pragma unroll 2
             for (int s = 0; s < 32; s += 4)
 #pragma unroll
-                for (int j = 0; j < 4; ++j) part[j] = front_mfma(wt1[(4 * (s + j) + hi) * kFrontHid], grow[128 + 4 * (s + j)], part[j]);
-            const front_f4 acc = (part[0] + part[1]) + (part[2] + part[3]);
+                for (int j = 0; j < 4; ++j) part[j] = train_mfma(wt1[(4 * (s + j) + hi) * kFrontHid], grow[128 + 4 * (s + j)], part[j]);
+            const train_f4 acc = (part[0] + part[1]) + (part[2] + part[3]);
             const int u = 16 * wave + 4 * hi;
             const float4 h = *reinterpret_cast<const float4 *>(L.hs + lo * kFrontHS + u);
             float4 d;
@@ -250,7 +214,7 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_backward_kernel(
             d.z = h.z > 0.0f ? acc[2] : 0.0f; d.w = h.w > 0.0f ? acc[3] : 0.0f;
             *reinterpret_cast<float4 *>(L.dhs + lo * kFrontHS + u) = d;
         }
-        gate_sum += front_column_sum(L.dgs + tid, kFrontGS);
+        gate_sum += train_column_sum(L.dgs + tid, kFrontGS);
         __syncthreads();
 
         // the tile's 16 rows into the parameter gradients, rows ascending (four k steps of four rows)
@@ -263,13 +227,13 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_backward_kernel(
 #pragma unroll
             for (int t = 0; t < 4; ++t)
 #pragma unroll
-                for (int v = 0; v < 4; ++v) dwih[4 * t + v] = front_mfma(a[t], b[v], dwih[4 * t + v]);
+                for (int v = 0; v < 4; ++v) dwih[4 * t + v] = train_mfma(a[t], b[v], dwih[4 * t + v]);
             const float dh = L.dhs[r * kFrontHS + 16 * wave + lo];
 #pragma unroll
             for (int j = 0; j < kFrontKTiles; ++j)
-                if (j < ktiles) dw1[j] = front_mfma(dh, L.xs[r * kFrontXS + 16 * j + lo], dw1[j]);
+                if (j < ktiles) dw1[j] = train_mfma(dh, L.xs[r * kFrontXS + 16 * j + lo], dw1[j]);
         }
-        if (tid < kFrontHid) hid_sum += front_column_sum(L.dhs + tid, kFrontHS);
+        if (tid < kFrontHid) hid_sum += train_column_sum(L.dhs + tid, kFrontHS);
 
         // dx = dHid W1 for the columns asked for: k tile j by wave j % 4, k ascending over the hidden units
         if (A.dx0 || A.dx1) {
@@ -279,14 +243,14 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_backward_kernel(
                 const int kk = 16 * j + lo;
                 const float *wcol = A.w1 + (kk < K ? kk : 0);
                 const float *drow = L.dhs + lo * kFrontHS + hi;
-                front_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
+                train_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll 2
                 for (int s = 0; s < 16; s += 2) {
                     const float w0 = wcol[(size_t)(4 * s + hi) * K], w4 = wcol[(size_t)(4 * s + 4 + hi) * K];
-                    even = front_mfma(kk < K ? w0 : 0.0f, drow[4 * s], even);
-                    odd = front_mfma(kk < K ? w4 : 0.0f, drow[4 * s + 4], odd);
+                    even = train_mfma(kk < K ? w0 : 0.0f, drow[4 * s], even);
+                    odd = train_mfma(kk < K ? w4 : 0.0f, drow[4 * s + 4], odd);
                 }
-                const front_f4 acc = even + odd;
+                const train_f4 acc = even + odd;
                 if (row_ok) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -322,26 +286,12 @@ __global__ void __launch_bounds__(kFrontThreads) pw_front_train_backward_kernel(
     if (tid < kFrontHid) P2[kFrontGates + tid] = hid_sum;
 }
 
-// element e of the parameter gradients = the sum of element e of every slot, slots ascending
-__global__ void __launch_bounds__(kFrontThreads) pw_front_train_reduce_kernel(const FrontReduceArgs A)
+// element e of the parameter gradients = the sum of element e of every slot
+__global__ void __launch_bounds__(kTrainThreads) pw_front_train_reduce_kernel(const FrontReduceArgs A)
 {
-    const long e = (long)blockIdx.x * kFrontThreads + threadIdx.x;
+    const long e = (long)blockIdx.x * kTrainThreads + threadIdx.x;
     if (e >= A.per_slot) return;
-    const float *p = A.partial + e;
-    // a balanced tree over the kFrontMaxGroups slots (slots 2 i and 2 i + 1 first); a slot past `groups` counts as zero
-    float c[kFrontMaxGroups / 8];
-#pragma unroll
-    for (int i = 0; i < kFrontMaxGroups / 8; ++i) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = 8 * i + j < A.groups ? p[(size_t)(8 * i + j) * A.per_slot] : 0.0f;
-        c[i] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-#pragma unroll
-    for (int n = kFrontMaxGroups / 16; n >= 1; n >>= 1)
-#pragma unroll
-        for (int i = 0; i < n; ++i) c[i] = c[2 * i] + c[2 * i + 1];
-    const float sum = c[0];
+    const float sum = train_slot_sum(A.partial + e, A.groups, A.per_slot);
     const long n_ih = (long)kFrontGates * kFrontHid, n_w1 = (long)kFrontHid * A.K;
     if (e < n_ih) {
         if (A.dirs == 2 && e >= n_ih / 2) A.dw_ih1[e - n_ih / 2] = sum;

@@ -20,46 +20,35 @@
 // which sum over the rows).
 // Long sums are split into short chains that are added as trees: a dot product's k steps go alternately into two chains (even and
 // odd steps, k ascending in each) that are added at the end; the heads' contributions to dX are added in head order (a launch's first
-// head starts the sum: no zero is added); a tile's 16 rows of a column sum are a balanced tree; and so are the partial sums of the
-// workgroups.  The column sums db, and the tree over the workgroups' partial sums, are COMPENSATED (two-sum pairs: every addition's
-// rounding error is carried beside the sum and added at the end): a bias gradient is one sum of `rows` numbers of either sign, and
-// when it nearly cancels (a Q head's dOut of mean zero) a plain float32 sum keeps the rounding of its large partial sums, several
-// times one rounding of the small result -- measured: 5.8 times at rows = 65 -- whatever the order.  The pairs cost six additions per
-// element on a few hundred columns.
+// head starts the sum: no zero is added); the sums over the rows are pw_train_sums.hpp's, and here they are the COMPENSATED ones: the
+// column sums db as two-sum pairs, and the tree over the slots as two-sum pairs for every element (a dW element's lo part starts at 0).
 //
 // Forward: a workgroup of four waves owns 64 rows; all stage A (4-byte loads, a lane per column), then wave w forms every head's
 // columns for rows 16 w .. 16 w + 15, 16 columns at a time, and adds the bias.  X is read once for all heads.
 //
-// Backward: workgroup g owns the row tiles g T .. g T + T - 1 (T and the number of workgroups follow from `rows` alone:
-// head_bwd_split).  Per tile of 16 rows: A and every head's dOut staged in LDS (a head's columns padded with zeros to a multiple of 16);
-// dX of features 16 w .. 16 w + 15 by wave w; then the tile's contribution to dW (for wave w: columns 16 w .. 16 w + 15 of every head's
-// dW, one accumulator per 16 rows of dW) is ADDED INTO REGISTERS that live across the workgroup's tiles (rows ascending), and the
-// column sums of dOut likewise.  At the end a workgroup stores its partial sums (head_partial_floats numbers) to its slot of the
-// caller's scratch, and pw_head_train_reduce_kernel adds the slots of every element as a balanced tree over the slot numbers, one
-// thread per element -- or, when the split gives ONE workgroup (rows <= 16), the main kernel stores the results themselves and no second
-// launch follows.  No floating-point atomics anywhere, and the order of every sum is a function of (rows, the heads' widths) only: the
-// same inputs give the same bits on every launch, eager or replayed from a graph.
+// Backward: the ordered sums of pw_train_sums.hpp (tiles, workgroups, slots, tree).  Per tile of 16 rows: A and every head's dOut
+// staged in LDS (a head's columns padded with zeros to a multiple of 16); dX of features 16 w .. 16 w + 15 by wave w; then the tile's
+// contribution to dW (for wave w: columns 16 w .. 16 w + 15 of every head's dW, one accumulator per 16 rows of dW) is added into the
+// workgroup's registers, and the column sums of dOut likewise.  A slot holds head_partial_floats numbers per head, and
+// pw_head_train_reduce_kernel adds the slots -- or, when the split gives ONE workgroup (rows <= 16), the main kernel stores the
+// results themselves (hi + lo of a column sum's pair) and no second launch follows.  The order of every sum is a function of
+// (rows, the heads' widths) only.
 // Addresses: X, dOut, weights, biases and every result are read and written with 4-byte accesses (a parameter may be a view into a
 // flat buffer; out_k's rows are n_k numbers long); dX, which the caller allocates for this launch, is 16-byte aligned.
 #pragma once
 
 #include "pw_common.hpp"
 #include "pw_lstm_math.hpp"
+#include "pw_train_sums.hpp"
 
 namespace {
 
 constexpr int kHeadK = 64;            // the width of X = the heads' input size
 constexpr int kHeadMaxHeads = 3;
 constexpr int kHeadMaxN = 104;        // the widest head
-constexpr int kHeadTile = 16;         // rows per tile = the columns of the matrix instruction
-constexpr int kHeadThreads = 256;     // four waves
 constexpr int kHeadFwdRows = 64;      // rows of one forward workgroup: a tile per wave
 constexpr int kHeadMaxColTiles = 21;  // 16-column tiles of all heads: 3 * ceil(104 / 16)
-// LDS row strides in words, each = 20 mod 32 (a tile is read both along its rows and across them: see pw_kernels_front.hpp)
-constexpr int kHeadXS = 64 + 20, kHeadDS = 16 * kHeadMaxColTiles + 4;
-constexpr int kHeadMaxGroups = 128;   // workgroups (= partial sums per element) of one backward launch
-
-typedef float head_f4 __attribute__((ext_vector_type(4)));
+constexpr int kHeadXS = train_lds_stride(kHeadK), kHeadDS = train_lds_stride(16 * kHeadMaxColTiles);   // LDS row strides
 
 struct HeadLds { float *xs, *ds; uint32_t bytes; };
 // xs [rows of the workgroup][kHeadXS]: A of the workgroup's rows (forward: 64, backward: 16); backward only: ds [16][kHeadDS]: the
@@ -67,22 +56,12 @@ struct HeadLds { float *xs, *ds; uint32_t bytes; };
 __host__ __device__ inline HeadLds head_lds(bool backward, unsigned char *raw = nullptr)
 {
     LdsCursor c{reinterpret_cast<float *>(raw)}; HeadLds o;
-    o.xs = c.take<float>((backward ? kHeadTile : kHeadFwdRows) * kHeadXS, 16);
+    o.xs = c.take<float>((backward ? kTrainTile : kHeadFwdRows) * kHeadXS, 16);
     o.ds = nullptr;
-    if (backward) o.ds = c.take<float>(kHeadTile * kHeadDS, 16);
+    if (backward) o.ds = c.take<float>(kTrainTile * kHeadDS, 16);
     o.bytes = 4 * c.at; return o;
 }
 
-// How a backward launch splits `rows`: T tiles per workgroup, `groups` workgroups; the summation order follows from it
-struct HeadSplit { long tiles; long per_group; int groups; };
-__host__ __device__ inline HeadSplit head_bwd_split(long rows)
-{
-    HeadSplit s;
-    s.tiles = (rows + kHeadTile - 1) / kHeadTile;
-    s.per_group = (s.tiles + kHeadMaxGroups - 1) / kHeadMaxGroups;
-    s.groups = (int)((s.tiles + s.per_group - 1) / s.per_group);
-    return s;
-}
 // one head's share of a workgroup's partial sums: dW [n][64], then db as two-sum pairs: hi [n], lo [n]
 __host__ __device__ inline long head_partial_floats(int n) { return (long)n * kHeadK + 2 * n; }
 
@@ -117,16 +96,11 @@ struct HeadReduceArgs {
     int heads, groups;
 };
 
-__device__ __forceinline__ head_f4 head_mfma(const float a, const float b, const head_f4 acc)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0);
-}
-
 // A of rows r0 .. r0 + count - 1 -> xs; zero past the last row
 __device__ __forceinline__ void head_stage_x(float *xs, const float *__restrict__ x, const long r0, const long rows, const int count,
                                              const int relu, const int tid)
 {
-    for (int i = tid; i < count * kHeadK; i += kHeadThreads) {
+    for (int i = tid; i < count * kHeadK; i += kTrainThreads) {
         const int r = i >> 6, k = i & 63;
         float v = 0.0f;
         if (r0 + r < rows) v = x[(size_t)(r0 + r) * kHeadK + k];
@@ -134,34 +108,7 @@ __device__ __forceinline__ void head_stage_x(float *xs, const float *__restrict_
     }
 }
 
-// (hi, lo) += (b_hi, b_lo): the rounding error of hi + b_hi (Knuth's two-sum, exact without fused contraction or reassociation --
-// the unit is compiled with -ffp-contract=off -fno-fast-math) is kept in lo.  The value is hi + lo.
-__device__ __forceinline__ void head_two_sum(float &hi, float &lo, const float b_hi, const float b_lo)
-{
-    const float s = hi + b_hi, bb = s - hi;
-    const float err = (hi - (s - bb)) + (b_hi - bb);
-    hi = s;
-    lo = (lo + b_lo) + err;
-}
-
-// (hi, lo) += the sum of a tile's 16 rows of one column, as a balanced tree of two-sums (rows 2 i and 2 i + 1 first)
-__device__ __forceinline__ void head_column_sum(float &hi, float &lo, const float *col, const int stride)
-{
-    float v[kHeadTile], e[kHeadTile];
-#pragma unroll
-    for (int r = 0; r < kHeadTile; ++r) { v[r] = col[r * stride]; e[r] = 0.0f; }
-#pragma unroll
-    for (int n = kHeadTile / 2; n >= 1; n >>= 1)
-#pragma unroll
-        for (int i = 0; i < n; ++i) {
-            float h = v[2 * i], l = e[2 * i];
-            head_two_sum(h, l, v[2 * i + 1], e[2 * i + 1]);
-            v[i] = h; e[i] = l;
-        }
-    head_two_sum(hi, lo, v[0], e[0]);
-}
-
-__global__ void __launch_bounds__(kHeadThreads) pw_head_train_forward_kernel(const HeadFwdArgs A)
+__global__ void __launch_bounds__(kTrainThreads) pw_head_train_forward_kernel(const HeadFwdArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char head_smem[];
     const HeadLds L = head_lds(false, head_smem);
@@ -171,11 +118,11 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_forward_kernel(con
     head_stage_x(L.xs, A.x, r0, A.rows, kHeadFwdRows, A.relu, tid);
     __syncthreads();
 
-    const long row = r0 + kHeadTile * wave + lo;                      // this lane's row: a column of every tile
-    if (r0 + kHeadTile * wave >= A.rows) return;                      // wave-uniform: a tile past the last row
+    const long row = r0 + kTrainTile * wave + lo;                      // this lane's row: a column of every tile
+    if (r0 + kTrainTile * wave >= A.rows) return;                      // wave-uniform: a tile past the last row
     const bool row_ok = row < A.rows;
     float xb[16];                                                     // the row's 64 numbers, k = 4 s + hi
-    const float *xrow = L.xs + (kHeadTile * wave + lo) * kHeadXS + hi;
+    const float *xrow = L.xs + (kTrainTile * wave + lo) * kHeadXS + hi;
 #pragma unroll
     for (int s = 0; s < 16; ++s) xb[s] = xrow[4 * s];
 
@@ -185,17 +132,17 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_forward_kernel(con
         const int n = A.n[k];
         const float *__restrict__ w = A.w[k], *__restrict__ b = A.b[k];
         float *__restrict__ out = A.out[k];
-        for (int c0 = 0; c0 < n; c0 += kHeadTile) {
+        for (int c0 = 0; c0 < n; c0 += kTrainTile) {
             const int j = c0 + lo;                                    // the output column whose weights this lane feeds
             const float *wrow = w + (size_t)(j < n ? j : 0) * kHeadK + hi;
-            head_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
+            train_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int s = 0; s < 16; s += 2) {
                 const float w0 = wrow[4 * s], w4 = wrow[4 * s + 4];
-                even = head_mfma(j < n ? w0 : 0.0f, xb[s], even);
-                odd = head_mfma(j < n ? w4 : 0.0f, xb[s + 1], odd);
+                even = train_mfma(j < n ? w0 : 0.0f, xb[s], even);
+                odd = train_mfma(j < n ? w4 : 0.0f, xb[s + 1], odd);
             }
-            const head_f4 acc = even + odd;
+            const train_f4 acc = even + odd;
             if (row_ok) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -207,31 +154,31 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_forward_kernel(con
     }
 }
 
-__global__ void __launch_bounds__(kHeadThreads) pw_head_train_backward_kernel(const HeadBwdArgs A)
+__global__ void __launch_bounds__(kTrainThreads) pw_head_train_backward_kernel(const HeadBwdArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char head_smem[];
     const HeadLds L = head_lds(true, head_smem);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, lo = lane & 15, hi = lane >> 4;
-    const HeadSplit S = head_bwd_split(A.rows);
+    const TrainSplit S = train_split(A.rows);
     const long first = (long)blockIdx.x * A.per_group;
     const long last = first + A.per_group < S.tiles ? first + A.per_group : S.tiles;
-    const int cols = kHeadTile * A.ntiles;                            // the staged columns of dOut, padding included
+    const int cols = kTrainTile * A.ntiles;                            // the staged columns of dOut, padding included
 
-    head_f4 dw[kHeadMaxColTiles];                                     // rows 16 t .. + 15 (t a column tile of dOut), columns 16 wave .. + 15 of dW
+    train_f4 dw[kHeadMaxColTiles];                                     // rows 16 t .. + 15 (t a column tile of dOut), columns 16 wave .. + 15 of dW
 #pragma unroll
-    for (int t = 0; t < kHeadMaxColTiles; ++t) dw[t] = head_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int t = 0; t < kHeadMaxColTiles; ++t) dw[t] = train_f4{0.0f, 0.0f, 0.0f, 0.0f};
     float col_hi0 = 0.0f, col_lo0 = 0.0f, col_hi1 = 0.0f, col_lo1 = 0.0f;   // staged columns tid and tid + 256 of dOut, as two-sum pairs
 
     for (long tile = first; tile < last; ++tile) {
-        const long r0 = tile * kHeadTile;
-        head_stage_x(L.xs, A.x, r0, A.rows, kHeadTile, A.relu, tid);
+        const long r0 = tile * kTrainTile;
+        head_stage_x(L.xs, A.x, r0, A.rows, kTrainTile, A.relu, tid);
 #pragma unroll
         for (int a = 0; a < kHeadMaxHeads; ++a) {
             if (a >= A.heads) break;
-            const int n = A.n[a], width = ((n + kHeadTile - 1) / kHeadTile) * kHeadTile;
+            const int n = A.n[a], width = ((n + kTrainTile - 1) / kTrainTile) * kTrainTile;
             const float *__restrict__ d = A.dout[a];
-            float *dst = L.ds + kHeadTile * A.tile0[a];
-            for (int i = tid; i < kHeadTile * width; i += kHeadThreads) {
+            float *dst = L.ds + kTrainTile * A.tile0[a];
+            for (int i = tid; i < kTrainTile * width; i += kTrainThreads) {
                 const int r = i / width, c = i - r * width;
                 dst[r * kHeadDS + c] = (r0 + r < A.rows && c < n) ? d[(size_t)(r0 + r) * n + c] : 0.0f;
             }
@@ -240,24 +187,24 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_backward_kernel(co
 
         // dX of features 16 wave .. + 15: per head two chains over its columns (k ascending), the heads added in order
         if (A.dx) {
-            head_f4 sum = {0.0f, 0.0f, 0.0f, 0.0f};
+            train_f4 sum = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int a = 0; a < kHeadMaxHeads; ++a) {
                 if (a >= A.heads) break;
                 const int n = A.n[a];
-                const float *wcol = A.w[a] + kHeadTile * wave + lo;   // W^T as the A operand: row = feature, k = the head's column
-                const float *drow = L.ds + lo * kHeadDS + kHeadTile * A.tile0[a] + hi;
-                head_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
+                const float *wcol = A.w[a] + kTrainTile * wave + lo;   // W^T as the A operand: row = feature, k = the head's column
+                const float *drow = L.ds + lo * kHeadDS + kTrainTile * A.tile0[a] + hi;
+                train_f4 even = {0.0f, 0.0f, 0.0f, 0.0f}, odd = {0.0f, 0.0f, 0.0f, 0.0f};
                 for (int j0 = 0; j0 < n; j0 += 8) {                   // the padding to 16 columns holds zeros
                     const int j = j0 + hi;
                     const float w0 = wcol[(size_t)(j < n ? j : 0) * kHeadK], w4 = wcol[(size_t)(j + 4 < n ? j + 4 : 0) * kHeadK];
-                    even = head_mfma(j < n ? w0 : 0.0f, drow[j0], even);
-                    odd = head_mfma(j + 4 < n ? w4 : 0.0f, drow[j0 + 4], odd);
+                    even = train_mfma(j < n ? w0 : 0.0f, drow[j0], even);
+                    odd = train_mfma(j + 4 < n ? w4 : 0.0f, drow[j0 + 4], odd);
                 }
-                const head_f4 part = even + odd;
+                const train_f4 part = even + odd;
                 sum = a == 0 ? part : sum + part;
             }
-            const int u = kHeadTile * wave + 4 * hi;
+            const int u = kTrainTile * wave + 4 * hi;
             if (A.relu) {
                 const float4 h = *reinterpret_cast<const float4 *>(L.xs + lo * kHeadXS + u);
                 sum[0] = h.x > 0.0f ? sum[0] : 0.0f; sum[1] = h.y > 0.0f ? sum[1] : 0.0f;
@@ -273,14 +220,14 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_backward_kernel(co
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
             const int r = 4 * s + hi;
-            const float b = L.xs[r * kHeadXS + kHeadTile * wave + lo];
+            const float b = L.xs[r * kHeadXS + kTrainTile * wave + lo];
             const float *drow = L.ds + r * kHeadDS + lo;
 #pragma unroll
             for (int t = 0; t < kHeadMaxColTiles; ++t)
-                if (t < A.ntiles) dw[t] = head_mfma(drow[kHeadTile * t], b, dw[t]);
+                if (t < A.ntiles) dw[t] = train_mfma(drow[kTrainTile * t], b, dw[t]);
         }
-        if (tid < cols) head_column_sum(col_hi0, col_lo0, L.ds + tid, kHeadDS);
-        if (tid + kHeadThreads < cols) head_column_sum(col_hi1, col_lo1, L.ds + tid + kHeadThreads, kHeadDS);
+        if (tid < cols) train_column_sum_comp(col_hi0, col_lo0, L.ds + tid, kHeadDS);
+        if (tid + kTrainThreads < cols) train_column_sum_comp(col_hi1, col_lo1, L.ds + tid + kTrainThreads, kHeadDS);
         __syncthreads();
     }
 
@@ -295,19 +242,19 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_backward_kernel(co
             float *to = A.direct ? (a == 0 ? A.dw[0] : a == 1 ? A.dw[1] : A.dw[2]) : P + (a == 0 ? A.base[0] : a == 1 ? A.base[1] : A.base[2]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const int j = kHeadTile * (t - t0) + 4 * hi + i;
-                if (j < n) to[(size_t)j * kHeadK + kHeadTile * wave + lo] = dw[t][i];
+                const int j = kTrainTile * (t - t0) + 4 * hi + i;
+                if (j < n) to[(size_t)j * kHeadK + kTrainTile * wave + lo] = dw[t][i];
             }
         }
     }
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-        const int c = tid + half * kHeadThreads;
+        const int c = tid + half * kTrainThreads;
         if (c < cols) {
             const int t = c >> 4;
             const int a = (A.heads > 1 && t >= A.tile0[1]) + (A.heads > 2 && t >= A.tile0[2]);
             const int n = a == 0 ? A.n[0] : a == 1 ? A.n[1] : A.n[2];
-            const int j = c - kHeadTile * (a == 0 ? A.tile0[0] : a == 1 ? A.tile0[1] : A.tile0[2]);
+            const int j = c - kTrainTile * (a == 0 ? A.tile0[0] : a == 1 ? A.tile0[1] : A.tile0[2]);
             float *to = A.direct ? (a == 0 ? A.db[0] : a == 1 ? A.db[1] : A.db[2])
                                  : P + (a == 0 ? A.base[0] : a == 1 ? A.base[1] : A.base[2]) + (size_t)n * kHeadK;
             const float hi_sum = half ? col_hi1 : col_hi0, lo_sum = half ? col_lo1 : col_lo0;
@@ -319,10 +266,10 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_backward_kernel(co
     }
 }
 
-// element e of the parameter gradients = the sum of element e of every slot, slots ascending
-__global__ void __launch_bounds__(kHeadThreads) pw_head_train_reduce_kernel(const HeadReduceArgs A)
+// element e of the parameter gradients = the sum of element e of every slot
+__global__ void __launch_bounds__(kTrainThreads) pw_head_train_reduce_kernel(const HeadReduceArgs A)
 {
-    const long e = (long)blockIdx.x * kHeadThreads + threadIdx.x;
+    const long e = (long)blockIdx.x * kTrainThreads + threadIdx.x;
     if (e >= A.per_slot) return;
     const int a = (A.heads > 1 && e >= A.base[1]) + (A.heads > 2 && e >= A.base[2]);
     const int n = a == 0 ? A.n[0] : a == 1 ? A.n[1] : A.n[2];
@@ -331,10 +278,11 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_reduce_kernel(cons
     if (off >= n_w + n) return;                                       // the lo half of a db pair: its hi thread reads it
     const bool pair = off >= n_w;
     const float *p = A.partial + e, *q = p + (pair ? n : 0);
-    // a balanced tree of two-sums over the kHeadMaxGroups slots (slots 2 i and 2 i + 1 first); a slot past `groups` counts as zero
-    float c[kHeadMaxGroups / 8], d[kHeadMaxGroups / 8];
+    // train_slot_sum's tree (pw_train_sums.hpp, which says why this body is here and not there) over two-sum pairs: the hi parts at p,
+    // the lo parts at q when `pair` (else they count as zero)
+    float c[kTrainSlots / 8], d[kTrainSlots / 8];
 #pragma unroll
-    for (int i = 0; i < kHeadMaxGroups / 8; ++i) {
+    for (int i = 0; i < kTrainSlots / 8; ++i) {
         float v[8], w[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -347,17 +295,17 @@ __global__ void __launch_bounds__(kHeadThreads) pw_head_train_reduce_kernel(cons
 #pragma unroll
             for (int j = 0; j < m; ++j) {
                 float h = v[2 * j], l = w[2 * j];
-                head_two_sum(h, l, v[2 * j + 1], w[2 * j + 1]);
+                train_two_sum(h, l, v[2 * j + 1], w[2 * j + 1]);
                 v[j] = h; w[j] = l;
             }
         c[i] = v[0]; d[i] = w[0];
     }
 #pragma unroll
-    for (int m = kHeadMaxGroups / 16; m >= 1; m >>= 1)
+    for (int m = kTrainSlots / 16; m >= 1; m >>= 1)
 #pragma unroll
         for (int i = 0; i < m; ++i) {
             float h = c[2 * i], l = d[2 * i];
-            head_two_sum(h, l, c[2 * i + 1], d[2 * i + 1]);
+            train_two_sum(h, l, c[2 * i + 1], d[2 * i + 1]);
             c[i] = h; d[i] = l;
         }
     const float sum = c[0] + d[0];

@@ -3,56 +3,42 @@
 // pw_lstm_train_backward_kernel writes it and Y as pw_lstm_train_forward_kernel writes it (pw_kernels_lstm.hpp), both read in place:
 //     dw_fw[r][k] = sum over (seq, t = 1 .. N - 1) of dG[seq][t][0][r] Y[seq][t - 1][k]
 //     dw_bw[r][k] = sum over (seq, t = 0 .. N - 2) of dG[seq][t][1][r] Y[seq][t + 1][H + k]            (r < 4 H, k < H)
-// Exact float32 on v_mfma_f32_16x16x4_f32, laid out as the dense front's dW_ih (pw_kernels_front.hpp): the flat rows (seq, t) are cut
-// into tiles of 16 without regard to sequence ends; workgroup g owns tiles g P .. g P + P - 1 (lstm_wgrad_split: P and the number of
-// workgroups, at most kLstmWgradMaxGroups, follow from b N alone).  Per tile the 256 gate columns of dG and the 64 columns of the
+// Exact float32 on v_mfma_f32_16x16x4_f32, laid out as the dense front's dW_ih (pw_kernels_front.hpp), summed by the ordered sums of
+// pw_train_sums.hpp (plain, not compensated): the flat rows (seq, t) are cut into tiles of 16 without regard to sequence ends, and P
+// below is a workgroup's number of tiles.  Per tile the 256 gate columns of dG and the 64 columns of the
 // SHIFTED Y row (row - 1 under direction 0's columns, row + 1 under direction 1's) are staged in LDS.  A row that has no previous step
 // in its direction (t = 0 forward, t = N - 1 reverse) or lies past the last sequence is staged as zeros on BOTH sides by a select: its
 // dG is never multiplied, so a NaN there stays out of the sums, and the shifted row of a live (row, direction) is always a row of the
 // same sequence.  Wave w owns gate columns 64 w .. 64 w + 63 (with two directions: waves 0, 1 direction 0, waves 2, 3 direction 1,
 // against that direction's 32 columns of Y); a tile is four matrix steps of four rows, rows ascending, steps 0 and 2 into one
 // accumulator chain and 1 and 3 into another (kept in registers across the workgroup's tiles, added at the end), so a chain is
-// 2 P steps long.  Every workgroup stores its sums to its slot of the caller's scratch ([4 H][H] per direction, direction 0 first);
-// pw_lstm_train_wgrad_reduce_kernel adds the slots of every element as a balanced tree over the slot numbers, one thread per element.
-// No floating-point atomics; the order of every sum is a function of (b, N, dirs) alone.  A direction whose output is not asked for
-// is neither multiplied nor stored nor reduced.
+// 2 P steps long.  A slot holds [4 H][H] per direction, direction 0 first; pw_lstm_train_wgrad_reduce_kernel adds the slots.  The
+// order of every sum is a function of (b, N, dirs) alone.  A direction whose output is not asked for is neither multiplied nor
+// stored nor reduced.
 #pragma once
 
 #include "pw_common.hpp"
+#include "pw_train_sums.hpp"
 
 namespace {
 
-constexpr int kLstmWgradThreads = 256;   // four waves
-constexpr int kLstmWgradTile = 16;
-constexpr int kLstmWgradMaxGroups = 128;
 constexpr int kLstmWgradCols = 256, kLstmWgradYCols = 64;                   // dirs * 4 H, dirs * H: the same for both shapes
-constexpr int kLstmWgradGS = 256 + 20, kLstmWgradYS = 64 + 20;              // LDS row strides, = 20 mod 32 as the dense front's
+constexpr int kLstmWgradGS = train_lds_stride(kLstmWgradCols), kLstmWgradYS = train_lds_stride(kLstmWgradYCols);   // LDS row strides
 constexpr int kLstmWgradSlot = kLstmWgradCols * kLstmWgradYCols;            // floats of one slot at dirs = 1; half of it at dirs = 2
 
-typedef float lstm_f4 __attribute__((ext_vector_type(4)));
-
-struct LstmWgradSplit { long tiles; long per_group; int groups; };
-__host__ __device__ inline LstmWgradSplit lstm_wgrad_split(long rows)
-{
-    LstmWgradSplit s;
-    s.tiles = (rows + kLstmWgradTile - 1) / kLstmWgradTile;
-    s.per_group = (s.tiles + kLstmWgradMaxGroups - 1) / kLstmWgradMaxGroups;
-    s.groups = (int)((s.tiles + s.per_group - 1) / s.per_group);
-    return s;
-}
 __host__ __device__ inline long lstm_wgrad_slot_floats(int dirs) { return kLstmWgradSlot / dirs; }
 
 struct LstmWgradLds { float *dgs, *ys; uint32_t bytes; };
 __host__ __device__ inline LstmWgradLds lstm_wgrad_lds(unsigned char *raw = nullptr)
 {
     LdsCursor c{reinterpret_cast<float *>(raw)}; LstmWgradLds o;
-    o.dgs = c.take<float>(kLstmWgradTile * kLstmWgradGS, 16); o.ys = c.take<float>(kLstmWgradTile * kLstmWgradYS, 16);
+    o.dgs = c.take<float>(kTrainTile * kLstmWgradGS, 16); o.ys = c.take<float>(kTrainTile * kLstmWgradYS, 16);
     o.bytes = 4 * c.at; return o;
 }
 
 // dG [b][N][DIRS][4 H], Y [b][N][DIRS H] -> partial [groups][lstm_wgrad_slot_floats]; want: bit d set = direction d is asked for
 template <int H, int DIRS>
-__global__ void __launch_bounds__(kLstmWgradThreads) pw_lstm_train_wgrad_kernel(const float *__restrict__ dG, const float *__restrict__ Y,
+__global__ void __launch_bounds__(kTrainThreads) pw_lstm_train_wgrad_kernel(const float *__restrict__ dG, const float *__restrict__ Y,
                                                                            const long rows, const int N, const long per_group,
                                                                            const int want, float *__restrict__ partial)
 {
@@ -65,21 +51,21 @@ __global__ void __launch_bounds__(kLstmWgradThreads) pw_lstm_train_wgrad_kernel(
     const bool wave_on = (want >> wdir) & 1;
     const int gdir = DIRS == 2 ? tid >> 7 : 0;                               // the direction of gate column tid (staging)
     const int ydir = DIRS == 2 ? (tid & 63) >> 5 : 0;                        // the direction of Y column tid & 63 (staging)
-    const LstmWgradSplit S = lstm_wgrad_split(rows);
+    const TrainSplit S = train_split(rows);
     const long first = (long)blockIdx.x * per_group;
     const long last = first + per_group < S.tiles ? first + per_group : S.tiles;
 
-    lstm_f4 acc[2][4 * V];
+    train_f4 acc[2][4 * V];
 #pragma unroll
     for (int c = 0; c < 2; ++c)
 #pragma unroll
-        for (int i = 0; i < 4 * V; ++i) acc[c][i] = lstm_f4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int i = 0; i < 4 * V; ++i) acc[c][i] = train_f4{0.0f, 0.0f, 0.0f, 0.0f};
 
     for (long tile = first; tile < last; ++tile) {
-        const long r0 = tile * kLstmWgradTile;
+        const long r0 = tile * kTrainTile;
         const int t0 = (int)(r0 % N);
 #pragma unroll
-        for (int r = 0; r < kLstmWgradTile; ++r) {
+        for (int r = 0; r < kTrainTile; ++r) {
             const int t = (t0 + r) % N;
             const bool live = r0 + r < rows && ((want >> gdir) & 1) && (gdir ? t < N - 1 : t > 0);
             L.dgs[r * kLstmWgradGS + tid] = live ? dG[(size_t)(r0 + r) * kLstmWgradCols + tid] : 0.0f;
@@ -106,7 +92,7 @@ __global__ void __launch_bounds__(kLstmWgradThreads) pw_lstm_train_wgrad_kernel(
                 for (int t = 0; t < 4; ++t)
 #pragma unroll
                     for (int v = 0; v < V; ++v)
-                        acc[s & 1][V * t + v] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t], y[v], acc[s & 1][V * t + v], 0, 0, 0);
+                        acc[s & 1][V * t + v] = train_mfma(a[t], y[v], acc[s & 1][V * t + v]);
             }
         }
         __syncthreads();
@@ -119,36 +105,22 @@ __global__ void __launch_bounds__(kLstmWgradThreads) pw_lstm_train_wgrad_kernel(
     for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int v = 0; v < V; ++v) {
-            const lstm_f4 sum = acc[0][V * t + v] + acc[1][V * t + v];
+            const train_f4 sum = acc[0][V * t + v] + acc[1][V * t + v];
 #pragma unroll
             for (int i = 0; i < 4; ++i) P[(64 * wave + 16 * t + 4 * hi + i) * H + 16 * v + lo] = sum[i];
         }
 }
 
-// element e of [dw_fw | dw_bw] = the sum of element e of every slot: a balanced tree over the kLstmWgradMaxGroups slot numbers
-// (slots 2 i and 2 i + 1 first); a slot past `groups` counts as zero.  An output that is NULL is neither read nor written.
-__global__ void __launch_bounds__(kLstmWgradThreads) pw_lstm_train_wgrad_reduce_kernel(const float *__restrict__ partial, const int groups,
+// element e of [dw_fw | dw_bw] = the sum of element e of every slot.  An output that is NULL is neither read nor written.
+__global__ void __launch_bounds__(kTrainThreads) pw_lstm_train_wgrad_reduce_kernel(const float *__restrict__ partial, const int groups,
                                                                                   const long per_slot, const long per_dir,
                                                                                   float *__restrict__ dw_fw, float *__restrict__ dw_bw)
 {
-    const long e = (long)blockIdx.x * kLstmWgradThreads + threadIdx.x;
+    const long e = (long)blockIdx.x * kTrainThreads + threadIdx.x;
     if (e >= per_slot) return;
     float *out = e < per_dir ? dw_fw : dw_bw;
     if (!out) return;
-    const float *p = partial + e;
-    float c[kLstmWgradMaxGroups / 8];
-#pragma unroll
-    for (int i = 0; i < kLstmWgradMaxGroups / 8; ++i) {
-        float v[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = 8 * i + j < groups ? p[(size_t)(8 * i + j) * per_slot] : 0.0f;
-        c[i] = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    }
-#pragma unroll
-    for (int n = kLstmWgradMaxGroups / 16; n >= 1; n >>= 1)
-#pragma unroll
-        for (int i = 0; i < n; ++i) c[i] = c[2 * i] + c[2 * i + 1];
-    out[e < per_dir ? e : e - per_dir] = c[0];
+    out[e < per_dir ? e : e - per_dir] = train_slot_sum(partial + e, groups, per_slot);
 }
 
 }  // namespace

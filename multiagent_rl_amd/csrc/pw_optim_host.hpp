@@ -11,8 +11,6 @@ namespace {
 
 constexpr int64_t kOptMaxElements = (int64_t)1 << 20;
 
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 // tile_begin[] of a table whose tensor k has numel(k) elements; refuses what the launch form does not serve.
 template <typename Args, typename Numel>
 int opt_tiles(Args &A, int32_t count, Numel numel)

@@ -7,8 +7,6 @@
 
 namespace {
 
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 // what both entry points check of their shared arguments
 int attention_args(const float *Y, int64_t b, int32_t N, int32_t H)
 {

@@ -8,8 +8,6 @@
 
 namespace {
 
-bool misaligned(const void *p, uintptr_t to = 4) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 // what the entry points check of the shape they share
 int front_shape(int64_t rows, int32_t d0, int32_t d1, int32_t dirs, int32_t H)
 {
@@ -17,8 +15,7 @@ int front_shape(int64_t rows, int32_t d0, int32_t d1, int32_t dirs, int32_t H)
         return fail(PW_EINVAL, "(dirs, H): the shapes served are (1, 64) and (2, 32)");
     if (d0 < 1 || d0 > kFrontMaxD0) return fail(PW_EINVAL, "d0 must be in [1, 104]");
     if (d1 < 0 || d1 > kFrontMaxD1) return fail(PW_EINVAL, "d1 must be in [0, 16]");
-    if (rows < 1) return fail(PW_EINVAL, "rows must be >= 1");
-    if (rows > (int64_t)0x7fffffff * kFrontTile) return fail(PW_EINVAL, "rows: more rows than one launch's grid holds");
+    if (const char *why = train_rows_refused(rows)) return fail(PW_EINVAL, why);
     return PW_OK;
 }
 
@@ -29,7 +26,7 @@ extern "C" {
 size_t pw_front_train_scratch_bytes(int64_t rows, int32_t d0, int32_t d1)
 {
     if (rows < 1 || d0 < 1 || d0 > kFrontMaxD0 || d1 < 0 || d1 > kFrontMaxD1) return 0;
-    return sizeof(float) * (size_t)front_bwd_split((long)rows).groups * (size_t)front_partial_floats(d0 + d1);
+    return train_scratch_bytes((long)rows, (size_t)front_partial_floats(d0 + d1));
 }
 
 int pw_front_train_forward(const float *x0, int32_t d0, const float *x1, int32_t d1, const float *w1, const float *b1,
@@ -50,8 +47,7 @@ int pw_front_train_forward(const float *x0, int32_t d0, const float *x1, int32_t
         if (misaligned(p)) return fail(PW_EINVAL, "inputs and parameters must be 4-byte aligned");
     if (misaligned(hid, 16) || misaligned(G, 16)) return fail(PW_EINVAL, "hid and G must be 16-byte aligned");
     A.hid = hid; A.G = G; A.rows = (long)rows; A.d0 = d0; A.d1 = d1; A.dirs = dirs;
-    const long tiles = (A.rows + kFrontTile - 1) / kFrontTile;
-    hipLaunchKernelGGL(pw_front_train_forward_kernel, dim3((unsigned)tiles), dim3(kFrontThreads), front_lds(false).bytes,
+    hipLaunchKernelGGL(pw_front_train_forward_kernel, dim3((unsigned)train_split(A.rows).tiles), dim3(kTrainThreads), front_lds(false).bytes,
                        static_cast<hipStream_t>(stream), A);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
@@ -75,20 +71,19 @@ int pw_front_train_backward(const float *dG, const float *x0, int32_t d0, const 
                           (const void *)(dirs == 2 ? dW_ih[1] : nullptr), (const void *)db_gate[0],
                           (const void *)(dirs == 2 ? db_gate[1] : nullptr), (const void *)dx0, (const void *)dx1, (const void *)scratch})
         if (misaligned(p)) return fail(PW_EINVAL, "every pointer must be 4-byte aligned");
-    const FrontSplit S = front_bwd_split((long)rows);
+    const TrainSplit S = train_split((long)rows);
     FrontBwdArgs A;
     A.dG = dG; A.x0 = x0; A.x1 = x1; A.hid = hid; A.w1 = w1; A.w_ih0 = w_ih[0]; A.w_ih1 = dirs == 2 ? w_ih[1] : nullptr;
     A.partial = static_cast<float *>(scratch); A.dx0 = dx0; A.dx1 = dx1;
     A.rows = (long)rows; A.per_group = S.per_group; A.d0 = d0; A.d1 = d1; A.dirs = dirs;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pw_front_train_backward_kernel, dim3((unsigned)S.groups), dim3(kFrontThreads), front_lds(true).bytes, s, A);
+    hipLaunchKernelGGL(pw_front_train_backward_kernel, dim3((unsigned)S.groups), dim3(kTrainThreads), front_lds(true).bytes, s, A);
     PW_HIP_CHECK(hipGetLastError());
     FrontReduceArgs R;
     R.partial = A.partial; R.dw_ih0 = dW_ih[0]; R.dw_ih1 = dirs == 2 ? dW_ih[1] : nullptr; R.dw1 = dW1;
     R.db_gate0 = db_gate[0]; R.db_gate1 = dirs == 2 ? db_gate[1] : nullptr; R.db1 = db1;
     R.per_slot = front_partial_floats(d0 + d1); R.groups = S.groups; R.K = d0 + d1; R.dirs = dirs;
-    hipLaunchKernelGGL(pw_front_train_reduce_kernel, dim3((unsigned)((R.per_slot + kFrontThreads - 1) / kFrontThreads)),
-                       dim3(kFrontThreads), 0, s, R);
+    hipLaunchKernelGGL(pw_front_train_reduce_kernel, dim3(train_reduce_blocks(R.per_slot)), dim3(kTrainThreads), 0, s, R);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }

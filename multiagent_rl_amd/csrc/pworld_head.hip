@@ -8,8 +8,6 @@
 
 namespace {
 
-bool misaligned(const void *p, uintptr_t to = 4) { return (reinterpret_cast<uintptr_t>(p) & (to - 1)) != 0; }
-
 // what the entry points check of the shape they share
 int head_shape(int64_t rows, int32_t heads, const int32_t *n)
 {
@@ -17,8 +15,7 @@ int head_shape(int64_t rows, int32_t heads, const int32_t *n)
     if (!n) return fail(PW_EINVAL, "null argument: n");
     for (int k = 0; k < heads; ++k)
         if (n[k] < 1 || n[k] > kHeadMaxN) return fail(PW_EINVAL, "n: every head holds 1 to 104 columns");
-    if (rows < 1) return fail(PW_EINVAL, "rows must be >= 1");
-    if (rows > (int64_t)0x7fffffff * kHeadTile) return fail(PW_EINVAL, "rows: more rows than one launch's grid holds");
+    if (const char *why = train_rows_refused(rows)) return fail(PW_EINVAL, why);
     return PW_OK;
 }
 
@@ -34,7 +31,7 @@ size_t pw_head_train_scratch_bytes(int64_t rows, int32_t heads, const int32_t *n
         if (n[k] < 1 || n[k] > kHeadMaxN) return 0;
         per_slot += (size_t)head_partial_floats(n[k]);
     }
-    return sizeof(float) * (size_t)head_bwd_split((long)rows).groups * per_slot;
+    return train_scratch_bytes((long)rows, per_slot);
 }
 
 int pw_head_train_forward(const float *X, int64_t rows, int32_t relu, int32_t heads, const float *const *w, const float *const *b,
@@ -51,7 +48,7 @@ int pw_head_train_forward(const float *X, int64_t rows, int32_t relu, int32_t he
     if (misaligned(X)) return fail(PW_EINVAL, "every pointer must be 4-byte aligned");
     A.x = X; A.rows = (long)rows; A.heads = heads; A.relu = relu != 0;
     const long groups = (A.rows + kHeadFwdRows - 1) / kHeadFwdRows;
-    hipLaunchKernelGGL(pw_head_train_forward_kernel, dim3((unsigned)groups), dim3(kHeadThreads), head_lds(false).bytes,
+    hipLaunchKernelGGL(pw_head_train_forward_kernel, dim3((unsigned)groups), dim3(kTrainThreads), head_lds(false).bytes,
                        static_cast<hipStream_t>(stream), A);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
@@ -67,7 +64,7 @@ int pw_head_train_backward(const float *const *dOut, const float *X, int64_t row
     if (misaligned(dX, 16)) return fail(PW_EINVAL, "dX must be 16-byte aligned");
     if (scratch_bytes < pw_head_train_scratch_bytes(rows, heads, n))
         return fail(PW_EINVAL, "scratch_bytes is less than pw_head_train_scratch_bytes(rows, heads, n)");
-    const HeadSplit S = head_bwd_split((long)rows);
+    const TrainSplit S = train_split((long)rows);
     HeadBwdArgs A = {};
     HeadReduceArgs R = {};
     int used = 0, tiles = 0, floats = 0;
@@ -81,7 +78,7 @@ int pw_head_train_backward(const float *const *dOut, const float *X, int64_t row
             return fail(PW_EINVAL, "every pointer must be 4-byte aligned");
         A.dout[used] = dOut[k]; A.w[used] = w[k]; A.dw[used] = R.dw[used] = dW[k]; A.db[used] = R.db[used] = db[k];
         A.n[used] = R.n[used] = n[k]; A.tile0[used] = tiles; A.base[used] = R.base[used] = floats;
-        tiles += (n[k] + kHeadTile - 1) / kHeadTile; floats += (int)head_partial_floats(n[k]);
+        tiles += (n[k] + kTrainTile - 1) / kTrainTile; floats += (int)head_partial_floats(n[k]);
         ++used;
     }
     if (!used) return fail(PW_EINVAL, "dOut: every head's is NULL, there is nothing to compute");
@@ -89,12 +86,11 @@ int pw_head_train_backward(const float *const *dOut, const float *X, int64_t row
     A.rows = (long)rows; A.per_group = S.per_group; A.per_slot = floats;
     A.heads = used; A.relu = relu != 0; A.ntiles = tiles; A.direct = S.groups == 1;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(pw_head_train_backward_kernel, dim3((unsigned)S.groups), dim3(kHeadThreads), head_lds(true).bytes, s, A);
+    hipLaunchKernelGGL(pw_head_train_backward_kernel, dim3((unsigned)S.groups), dim3(kTrainThreads), head_lds(true).bytes, s, A);
     PW_HIP_CHECK(hipGetLastError());
     if (A.direct) return PW_OK;
     R.partial = A.partial; R.per_slot = floats; R.heads = used; R.groups = S.groups;
-    hipLaunchKernelGGL(pw_head_train_reduce_kernel, dim3((unsigned)((R.per_slot + kHeadThreads - 1) / kHeadThreads)), dim3(kHeadThreads),
-                       0, s, R);
+    hipLaunchKernelGGL(pw_head_train_reduce_kernel, dim3(train_reduce_blocks(R.per_slot)), dim3(kTrainThreads), 0, s, R);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }

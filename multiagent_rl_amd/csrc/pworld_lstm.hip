@@ -8,8 +8,6 @@
 
 namespace {
 
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 // what both entry points check of their shared arguments; *groups = b * dirs (one per sequence and direction)
 int lstm_args(const float *w_hh_fw, const float *w_hh_bw, int64_t b, int32_t N, int32_t dirs, int32_t H, int64_t *groups)
 {

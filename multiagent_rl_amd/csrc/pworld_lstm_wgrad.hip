@@ -7,8 +7,6 @@
 
 namespace {
 
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 template <int H, int DIRS>
 int lstm_wgrad_launch(const float *dG, const float *Y, int64_t b, int32_t N, float *dw_fw, float *dw_bw, float *partial, hipStream_t stream)
 {
@@ -17,13 +15,13 @@ int lstm_wgrad_launch(const float *dG, const float *Y, int64_t b, int32_t N, flo
     const size_t lds = lstm_wgrad_lds().bytes;
     PW_LDS_OPTIN(&optin_mask, kernel);
     const long rows = (long)b * N;
-    const LstmWgradSplit S = lstm_wgrad_split(rows);
+    const TrainSplit S = train_split(rows);
     const int want = (dw_fw ? 1 : 0) | (dw_bw ? 2 : 0);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)S.groups), dim3(kLstmWgradThreads), lds, stream, dG, Y, rows, N, S.per_group, want, partial);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)S.groups), dim3(kTrainThreads), lds, stream, dG, Y, rows, N, S.per_group, want, partial);
     PW_HIP_CHECK(hipGetLastError());
     const long per_slot = lstm_wgrad_slot_floats(DIRS), per_dir = 4L * H * H;
-    hipLaunchKernelGGL(pw_lstm_train_wgrad_reduce_kernel, dim3((unsigned)((per_slot + kLstmWgradThreads - 1) / kLstmWgradThreads)), dim3(kLstmWgradThreads),
-                       0, stream, partial, S.groups, per_slot, per_dir, dw_fw, dw_bw);
+    hipLaunchKernelGGL(pw_lstm_train_wgrad_reduce_kernel, dim3(train_reduce_blocks(per_slot)), dim3(kTrainThreads), 0, stream, partial,
+                       S.groups, per_slot, per_dir, dw_fw, dw_bw);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
 }
@@ -45,7 +43,7 @@ extern "C" {
 size_t pw_lstm_train_wgrad_scratch_bytes(int64_t b, int32_t N, int32_t dirs, int32_t H)
 {
     if (wgrad_shape(b, N, dirs, H)) return 0;
-    return (size_t)lstm_wgrad_split((long)b * N).groups * (size_t)lstm_wgrad_slot_floats(dirs) * sizeof(float);
+    return train_scratch_bytes((long)b * N, (size_t)lstm_wgrad_slot_floats(dirs));
 }
 
 int pw_lstm_train_wgrad(const float *dG, const float *Y, int64_t b, int32_t N, int32_t dirs, int32_t H, float *dw_hh_fw, float *dw_hh_bw,

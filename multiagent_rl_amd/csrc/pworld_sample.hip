@@ -7,8 +7,6 @@
 
 namespace {
 
-bool misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
-
 // what both entry points check of their shared arguments
 int sample_args(int64_t rows, int32_t n, float tau)
 {

@@ -16,7 +16,7 @@ from tests import head_ref, lstm_ref, nonfinite
 
 pytestmark = pytest.mark.gpu
 
-# 2049 = 128 tiles of 16 rows and one row: the smallest count at which head_bwd_split gives a workgroup two tiles (129 tiles, 65
+# 2049 = 128 tiles of 16 rows and one row: the smallest count at which train_split gives a workgroup two tiles (129 tiles, 65
 # workgroups) and the last workgroup fewer than the others (one).  6144: the length at which one summation chain failed the bound.
 ROWS = (1, 15, 16, 17, 63, 65, 2049, 6144)
 WIDTHS = ((1,), (5,), (16,), (1, 1), (5, 10), (5, 16), (5, 10, 21), (16, 16, 104))
