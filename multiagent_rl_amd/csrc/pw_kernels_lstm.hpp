@@ -47,8 +47,8 @@ __host__ __device__ inline LstmTrainLds lstm_train_lds(int H, int dirs, bool bac
 // its reciprocal at the size of 1: measured, a backward fed those values was 4.3 x stock float32's error at saturated gates over 64 steps, fed
 // exact gates 1.04 x (profiles/lstm_train_saturated.txt).  So the SAVED copy is formed from the small side: q = e / (1 + e) with
 // e = exp(-|x|) <= 1 carries a few ulp of relative error however small it is, and the gate is q or 1 - q (tanh: e = exp(-2 |x|), 1 - 2 q with
-// the sign of x); the difference from the value lstm_cell used for c and h is the last bits that function loses (<= ~2.5e-7).  c and h stay
-// lstm_cell's, bit for bit with and without saving.  Finite for every finite x: e in [0, 1], 1 + e in [1, 2].
+// the sign of x); the difference from the value the cell used for c and h is the last bits (<= ~2.5e-7).  c and h stay
+// lstm_cell_train's (below), bit for bit with and without saving.  Finite for every finite x: e in [0, 1], 1 + e in [1, 2].
 __device__ __forceinline__ float saved_sigmoid(const float x)
 {
     const float e = __builtin_amdgcn_exp2f(fabsf(x) * -1.4426950408889634f);
@@ -59,6 +59,22 @@ __device__ __forceinline__ float saved_tanh(const float x)
 {
     const float e = __builtin_amdgcn_exp2f(fabsf(x) * -2.8853900817779268f);
     return copysignf(1.0f - 2.0f * (e / (1.0f + e)), x);
+}
+
+// The cell of the passes with gradient.  fast_tanh forms 2 / (1 + e) - 1, a difference of numbers near 1: its ABSOLUTE error is one rounding
+// of 1 (~1e-7) however small the value is, and with the learner's pre-activations tanh(g) and tanh(c) are a few tenths and less -- the LSTM
+// output then carried 3.4 x MIOpen's rms error, part of it of one sign, which the row sums of the layers behind it keep (the critic's
+// dense2.weight gradient was 4.97 x stock float32's against float64 in a whole update, tests/test_gpu_update_parity.py).  Here both are
+// tanhf, accurate relative to the value; the sigmoids are lstm_cell's operations (a gate near 0.5 has that rounding anyway).  The no-gradient
+// kernels keep lstm_cell.
+__device__ __forceinline__ float train_tanh(const float x) { return tanhf(x); }
+__device__ __forceinline__ void lstm_cell_train(const float gi, const float gf, const float gg, const float go, float &c, float &h)
+{
+    const float si = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gi * -1.4426950408889634f));
+    const float sf = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(gf * -1.4426950408889634f));
+    const float so = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(go * -1.4426950408889634f));
+    c = sf * c + si * train_tanh(gg);
+    h = so * train_tanh(c);
 }
 
 // G [b][N][DIRS][4 H], Y [b][N][DIRS H], saved [b][N][DIRS][5][H] (i, f, g, o after activation, c) or NULL
@@ -106,7 +122,7 @@ __global__ void __launch_bounds__(kLstmThreads) pw_lstm_train_forward_kernel(con
             }
             wave_lds_sync();   // every read of h done before the next step overwrites it
         }
-        lstm_cell(ai, af, ag, ao, c, h);
+        lstm_cell_train(ai, af, ag, ao, c, h);
         if (valid) {
             Y[(seq * N + t) * (DIRS * H) + dir * H + j] = h;
             if (saved) {
@@ -155,7 +171,7 @@ __global__ void __launch_bounds__(kLstmThreads) pw_lstm_train_backward_kernel(co
         const int t = dir ? N - 1 - s : s;
         LstmSavedStep prev = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // c_prev = 0 at the forward's first step
         if (s > 0) prev = lstm_saved_step<H, DIRS>(saved, dY, seq, N, dir ? t + 1 : t - 1, dir, j);
-        const float tc = fast_tanh(cur.c);
+        const float tc = train_tanh(cur.c);
         const float dht = cur.dy + dh;
         const float d_o = dht * tc * (cur.o * (1.0f - cur.o));
         const float dct = dc + dht * cur.o * (1.0f - tc * tc);

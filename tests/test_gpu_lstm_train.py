@@ -163,6 +163,20 @@ def test_saturated_gates(shape):
     _check('saturated (G x 30, W_hh x 4) %s' % (shape,), *_kernel_level(shape, 30.0, 4.0))
 
 
+@pytest.mark.parametrize('shape', [lstm_ref.SHAPES[1], lstm_ref.SHAPES[2]], ids=[IDS[1], IDS[2]])
+def test_small_outputs_keep_their_relative_accuracy(shape):
+    """G x 0.05: tanh(g), tanh(c) and the output are a few hundredths.  The forward's Y is held to the gradients' bound here, 4 x
+    max(e_stock, 2^-23 max|ref|): with the cell's tanh formed as 2 / (1 + e) - 1 (one rounding of 1, ~1e-7 absolute, whatever the value)
+    Y missed it several times over, and in a whole update the critic's dense2.weight gradient stood at 4.97 x stock
+    (tests/test_gpu_update_parity.py, two_head-b33).  The gradients are held as everywhere."""
+    kernel, stock, ref = _kernel_level(shape, 0.05)
+    assert float(ref['Y'].abs().max()) < 0.05
+    ratio, _, e_k, e_s = lstm_ref.worst_ratio(kernel, stock, {'Y': ref['Y']})
+    _report('small outputs (G x 0.05) %-34s Y kernel %.3e  stock %.3e  largest %.3e  ratio %.2f' % (shape, e_k, e_s, float(ref['Y'].abs().max()), ratio))
+    assert ratio <= 4.0, (shape, e_k, e_s, ratio)
+    _check('small outputs (G x 0.05) %s' % (shape,), kernel, stock, ref)
+
+
 # ---- 4. gradient patterns ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('shape', lstm_ref.SHAPES, ids=IDS)
 def test_gradient_patterns(shape):
