@@ -153,7 +153,10 @@ size_t pw_state_bytes(const pw_handle *h);
 int pw_bind_state(pw_handle *h, void *device_state_block);
 
 /* AoS <-> SoA: pos/vel [B,N,2], lm [B,L,2] f32 device (upstream p_pos / p_vel arrays);
- * ep_step/ep_count [B] may be NULL (set: zeroed / get: skipped). */
+ * ep_step/ep_count [B] may be NULL (set: zeroed / get: skipped), each on its own: a set with ep_step alone keeps
+ * the steps and zeroes ep_count, and the other way round.  pos, vel and lm may each be NULL as well: a set leaves
+ * that part of the state as it is (a set with all five NULL only zeroes the counters), a get skips it
+ * (tests/test_gpu_aux_entry_points.py). */
 int pw_set_state(pw_handle *h, const float *pos, const float *vel, const float *lm,
                  const int32_t *ep_step, const uint32_t *ep_count, void *stream);
 int pw_get_state(pw_handle *h, float *pos, float *vel, float *lm,
@@ -169,7 +172,8 @@ int pw_get_comm_state(pw_handle *h, float *comm, int32_t *goal, void *stream);
 int pw_reset(pw_handle *h, const uint8_t *env_mask, float *obs, void *stream);
 /* scenario.observation for every agent from the current state. */
 int pw_observe(pw_handle *h, float *obs, void *stream);
-/* scenario.reward / is_collision from the current state (no step). */
+/* scenario.reward / is_collision from the current state (no step).  rew or coll may be NULL (both: PW_EINVAL); the
+ * communication scenarios have no collisions and take coll = NULL only (PW_EINVAL otherwise). */
 int pw_reward(pw_handle *h, float *rew, uint64_t *coll, void *stream);
 
 /* MultiAgentEnv.step(): _set_action, World.step (apply_action_force,
@@ -519,9 +523,11 @@ typedef struct pw_rollout_sink {
 /* Policy-in-the-loop rollout as ONE launch: num_steps x (actor forward + Gumbel sampling + environment step +
  * auto-reset) on the handle's bound state, starting from the observation of the current state; observations,
  * sampled actions and world state stay on the CU between steps.  io: the pw_rollout outputs ([num_steps, ...];
- * no action inputs, no coll); act_out [num_steps,B,N] int32 receives the sampled indices.  Without a ring sink
- * act_out and obs, rew, rew_shared, done, terminal are required (final_obs optional); with one every output is
- * optional.  The Gumbel noise of step t is keyed (seed; step + t, row) exactly as pw_actor_fused / pw_actor_head, so
+ * no action inputs, no coll); act_out [num_steps,B,N] int32 receives the sampled indices.  Without a sink (sink NULL,
+ * or one with neither a ring nor episode_return) act_out and obs, rew, rew_shared, done, terminal are required (final_obs
+ * optional); with one -- a ring, the episode bookkeeping or both -- every output is optional, each on its own: what is
+ * left out changes no other output, no ring slot, no statistic and not the state the launch leaves
+ * (tests/test_gpu_rollout_output_subsets.py).  The Gumbel noise of step t is keyed (seed; step + t, row) exactly as pw_actor_fused / pw_actor_head, so
  * the results equal a loop of pw_actor_fused + pw_step (+ pw_replay_add_tail).
  * simple_spread fast-path configurations (local observation, homogeneous agents, L <= N; observation rows up to
  * D = 104, i.e. N = L <= 50: rows longer than 64 numbers on the just-in-time kernel form only) and simple_tag with homogeneous roles (9 <= D <= 48; good agents' rows zero-padded to D), one

@@ -23,6 +23,10 @@ ActorFusedArgs actor_args(const float *frag, const float *b1, const float *b_ih,
     return a;
 }
 
+// A sink that takes something off the launch -- the ring, the episode bookkeeping or both: only then may step outputs be left out
+// (a launch that writes nothing at all is refused).  FusedActor.rollout(out=False, stats=...) is the statistics-only caller.
+bool sink_takes(const pw_rollout_sink *sink) { return sink && (sink->ring || sink->episode_return); }
+
 // A rollout sink's ring has the rollout's row shape and room for the chunk of `rows` transitions from a valid cursor, and its
 // bookkeeping pointers come together.
 int sink_fits(const pw_rollout_sink *sink, int N, int D, int64_t rows)

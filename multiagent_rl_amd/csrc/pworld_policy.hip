@@ -131,8 +131,8 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
         }
         if (io->act_idx || io->act_vec || io->act_comm || io->coll)
             return fail(PW_EINVAL, "pw_policy_rollout produces the actions itself (act_out) and has no coll output");
-        if (!(sink && sink->ring) && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
-            return fail(PW_EINVAL, "without a ring sink, act_out and the obs, rew, rew_shared, done, terminal outputs are required");
+        if (!sink_takes(sink) && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
+            return fail(PW_EINVAL, "without a sink (a ring or the episode bookkeeping), act_out and the obs, rew, rew_shared, done, terminal outputs are required");
         if ((reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(frag) |
              reinterpret_cast<uintptr_t>(w_hh_fw) | reinterpret_cast<uintptr_t>(w_hh_bw)) & 15)
             return fail(PW_EINVAL, "obs, final_obs, frag and w_hh must be 16-byte aligned");
@@ -183,9 +183,9 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     if (kp.N > 64 || kp.D > 104) return fail(PW_EINVAL, "N must be <= 64 and the observation length <= 104");
     if (io->act_idx || io->act_vec || io->act_comm || io->coll)
         return fail(PW_EINVAL, "pw_policy_rollout produces the actions itself (act_out) and has no coll output");
-    const bool have_sink = sink && sink->ring;
-    if (!have_sink && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
-        return fail(PW_EINVAL, "without a ring sink, act_out and the obs, rew, rew_shared, done, terminal outputs are required");
+    const bool have_sink = sink && sink->ring;   // a ring: its planes join the alignment check below
+    if (!sink_takes(sink) && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
+        return fail(PW_EINVAL, "without a sink (a ring or the episode bookkeeping), act_out and the obs, rew, rew_shared, done, terminal outputs are required");
     if (sink) {
         if (sink->ring && sink->ring->state_rows) {   // a STATE ring as the sink: {vel, pos} + the episode's landmarks instead of the two rows
             if (int rc = state_ring_ok(sink->ring, "pw_policy_rollout sink")) return rc;

@@ -44,9 +44,9 @@ int pw_internal_policy_rollout_generic(pw_handle *h, const float *frag, const fl
         return fail(PW_EINVAL, "pw_policy_rollout serves simple_spread, simple_tag and simple_reference");
     if (io->act_idx || io->act_vec || io->act_comm || io->coll)
         return fail(PW_EINVAL, "pw_policy_rollout produces the actions itself (act_out) and has no coll output");
-    const bool have_sink = sink && sink->ring;
-    if (!have_sink && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
-        return fail(PW_EINVAL, "without a ring sink, act_out and the obs, rew, rew_shared, done, terminal outputs are required");
+    const bool have_sink = sink && sink->ring;   // a ring: its planes join the alignment check below
+    if (!sink_takes(sink) && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
+        return fail(PW_EINVAL, "without a sink (a ring or the episode bookkeeping), act_out and the obs, rew, rew_shared, done, terminal outputs are required");
     if (sink) {
         // a full row is not a function of the stored state alone for every configuration served here: the plain row ring only
         if (int rc = plain_ring_only(sink->ring, "pw_policy_rollout sink (generic form)")) return rc;

@@ -315,12 +315,14 @@ class BatchedParticleEnv(object):
 
     def step(self, actions, out=None):
         """actions: int [B,N] indices (0 noop, 1 +x, 2 -x, 3 +y, 4 -y) or float [B,N,5]
-        one-hot/soft vectors as run.py:38 builds them -> (obs, rew, done, info)."""
+        one-hot/soft vectors as run.py:38 builds them -> (obs, rew, done, info).
+        ``out``: the output tensors to write, as ``alloc_outputs()`` names them; any of them may be left out (pw_step_io: that output
+        is skipped, and its place in the returned tuple is None) -- ``out={}`` only advances the state."""
         out = self.alloc_outputs() if out is None else out
         io, keep = self._io(actions, out, None)
         check(self.lib.pw_step(self._h, C.byref(io), self._stream()))
         info = {k: out[k] for k in ('terminal', 'rew_shared', 'final_obs', 'coll') if k in out}
-        return out['obs'], out['rew'], out['done'], info
+        return out.get('obs'), out.get('rew'), out.get('done'), info
 
     def last_kernel(self):
         """Name of the device kernel the last step / rollout launched, e.g. 'pw_spread_quad_kernel<true>' (pw_rollout_kernel)."""

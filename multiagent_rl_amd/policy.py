@@ -284,7 +284,10 @@ class FusedActor(object):
 
         ``memory`` (a device ``ReplayBuffer``): the transitions go straight into the ring from the same launch;
         ``stats`` = (episode_return [B], finished_sum, finished_count) tensors: the episode bookkeeping too.  With a
-        sink, ``out=False`` skips the step outputs altogether (only the ring / statistics are written)."""
+        sink, ``out=False`` skips the step outputs altogether (only the ring / statistics are written), and a caller's ``out`` may
+        hold any subset of them (``'act': None`` leaves the sampled actions out; an absent ``'act'`` is allocated here).  What is left
+        out changes nothing else.  Without a sink the library refuses a launch that lacks ``act``, ``obs``, ``rew``, ``rew_shared``,
+        ``done`` or ``terminal`` (``PworldError``, nothing launched)."""
         T, B, N = int(num_steps), env.num_envs, env.n
         two = len(self.heads) == 2   # MultiDiscrete actor: simple_reference, act [T,B,N,2] = (movement, symbol); the sink is a two-head ring
         if two:
@@ -302,9 +305,10 @@ class FusedActor(object):
             if 'act' not in out:
                 out['act'] = torch.empty((T, B, N, 2) if two else (T, B, N), dtype=torch.int32, device=self.device)
             # a caller-supplied action buffer of the single-head shape under a two-head actor would be overrun by the kernel
-            # (it writes act[2 row], act[2 row + 1]): refuse it here, whoever built the dict
+            # (it writes act[2 row], act[2 row + 1]): refuse it here, whoever built the dict.  out['act'] = None: the caller does not
+            # want the sampled actions (pw_policy_rollout's act_out = NULL: served with a sink, refused by the library without one)
             want = (T, B, N, 2) if two else (T, B, N)
-            if tuple(out['act'].shape) != want or out['act'].dtype != torch.int32 or not out['act'].is_contiguous():
+            if out['act'] is not None and (tuple(out['act'].shape) != want or out['act'].dtype != torch.int32 or not out['act'].is_contiguous()):
                 raise ValueError('rollout: out["act"] must be a contiguous int32 tensor of shape %r (%s actor), got %r %s'
                                  % (want, 'two-head' if two else 'one-head', tuple(out['act'].shape), out['act'].dtype))
         io = _lib.step_io(out, ('obs', 'final_obs', 'rew', 'rew_shared', 'done', 'terminal'), lead=(T,))
