@@ -14,7 +14,9 @@ critic from the reference checkout on ``sys.path`` (``rls.agent.multiagent.ddpg_
 learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).  ``--critic attention`` gives
 it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``); ``--critic bicnet`` is the BiCNet baseline: per-agent
 transitions (``train_batched(per_agent_transition=True)``), ``multiagent_rl_amd.critic.BiCNetCritic`` and the per-agent stand-in learner
-(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only; ``--critic model`` is the
+(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only -- where the other critics get a
+STATE ring (simple_spread with the local observation, simple_tag; not ``--policy-form 5``) the script builds the per-agent STATE ring itself
+and passes it as ``memory=``, the row ring otherwise or under ``--ring rows`` (the batches are bit-identical); ``--critic model`` is the
 paper's own method, the model-learning variant: ``ModelActorNetwork`` / ``ModelCriticNetwork`` and ``madr_learner.ModelTrainer`` (with
 ``--reference``: ``model_ddpg_gumbel_fix.Trainer`` and ``ac_network_model_multi_gumbel``) on the shared-reward ring, any number of ranks.  ``--fused-targets`` runs its target networks'
 forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
@@ -55,6 +57,10 @@ def main(argv=None):
                          'runs on the generic one-launch kernel and the ring keeps rows')
     ap.add_argument('--policy-form', type=int, default=0,
                     help='pw_dispatch.policy_form of the rollout: 0 automatic, 3 / 4 the simple_spread forms, 5 the generic form')
+    ap.add_argument('--ring', default='auto', choices=['auto', 'rows', 'state'],
+                    help='the replay ring: state = {vel, pos} + landmarks per transition, rows rebuilt when a batch is sampled (bit-identical '
+                         'batches, a third of the bytes; simple_spread with the local observation and simple_tag on the specialised rollout '
+                         'forms); rows = the observation rows themselves; auto = state wherever it is served')
     ap.add_argument('--episodes', type=int, default=None, help='arglist.num_episodes (finished episodes over all envs of a rank)')
     ap.add_argument('--seeds', type=int, default=1, help='cnt in range(seeds), main.py:37')
     ap.add_argument('--chunk', type=int, default=100, help='batched env steps per launch')
@@ -217,7 +223,18 @@ def main(argv=None):
             if args.policy_form:
                 env.set_dispatch(policy_form=args.policy_form)
             # a STATE ring holds {vel, pos} + landmarks: enough for the local observation and simple_tag on the specialised rollout forms only
-            state_ok = scenario_name in ('simple_spread', 'simple_tag') and not args.full_observation and args.policy_form != 5 and not bicnet
+            state_ok = scenario_name in ('simple_spread', 'simple_tag') and not args.full_observation and args.policy_form != 5
+            if args.ring == 'state' and not state_ok:
+                ap.error('--ring state serves simple_spread with the local observation and simple_tag on the specialised rollout forms '
+                         '(not --full-observation, not --policy-form 5)')
+            state_ok = state_ok and args.ring != 'rows'
+            memory = None
+            if bicnet and state_ok:
+                # the per-agent STATE ring: train_batched(per_agent_transition=True) builds the row ring only, this one comes in as memory=
+                from multiagent_rl_amd.replay_buffer import ReplayBuffer
+                memory = ReplayBuffer(int(1e6), env.n, env.obs_dim, per_agent=True, device_index='counter' if args.graph_update else True,
+                                      state_ring=dict(scenario=scenario_name, num_landmarks=env.num_landmarks,
+                                                      num_adversaries=env.cfg.num_adversaries if scenario_name == 'simple_tag' else 0))
             dim_obs, dim_action, action_type = dims_from_env(env)             # main.py:51-58
             actor = ActorNetwork(input_dim=dim_obs, out_dim=dim_action)       # main.py:60-61
             n_act = sum(dim_action) if isinstance(dim_action, list) else dim_action
@@ -234,7 +251,7 @@ def main(argv=None):
                 gather.prime()
             hist = train_batched(env, actor, critic, Trainer, scenario_name, action_type, cnt=cnt, out_dir=args.out_dir,
                                  chunk=args.chunk, max_updates_per_chunk=args.max_updates_per_chunk, gather=gather,
-                                 ring='state' if (gather is None and state_ok) else 'rows',
+                                 ring='state' if (gather is None and state_ok and not bicnet) else 'rows', memory=memory,
                                  rank=rank, world=world, log=print if rank == 0 else (lambda *a: None), per_agent_transition=bicnet,
                                  graph_update=args.graph_update)
             results.append((scenario_name, cnt, hist['stats']))

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 121 /* 0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 122 /* 0.1.22: the ring of pw_rollout_sink may be a per-agent ring (pw_replay_store.per_agent: rew / done [cap,N]) in every form of pw_policy_rollout -- the row ring and the STATE ring of the simple_spread / simple_tag forms, the row ring of the generic form, the two-head ring of simple_reference: every live lane stores its own reward, the value the launch writes to rew[t, env, a], and done = 0; a STATE ring may be per-agent (single head; pw_replay_gather / pw_replay_sample then return out_rew / out_done [b,N]).  The tail / packed / wire entry points keep refusing a per-agent ring.  No entry point changed.  0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -243,8 +243,11 @@ size_t pw_algorithmic_bytes_per_env_step(const pw_handle *h);
  *     experiments/run.py:39-41; head_width = {5, dim_c} sizes the one-hot rows pw_replay_gather returns
  *     (head_width[0] = 0 means 5);
  *   per_agent = 1: rew and done are [cap,N] f32 -- the BiCNet tuple of experiments/run_BIC.py:46,50.
- * pw_replay_add and pw_replay_gather serve every variant, pw_replay_add_rollout the plain and the two-head ring; the tail /
- * packed / wire entry points and the pw_policy_rollout sink take the plain ring only (PW_EINVAL otherwise).
+ * pw_replay_add, pw_replay_add_rollout, pw_replay_gather and pw_replay_sample serve every variant of the row ring.  The
+ * pw_policy_rollout sink (0.1.22) takes the single-head ring on simple_spread / simple_tag and the two-head ring on simple_reference,
+ * each with the shared reward or per-agent.  The tail / packed / wire entry points (pw_replay_add_tail, pw_replay_add_packed,
+ * pw_replay_add_wire, pw_replay_add_state_wire, pw_replay_add_ref_wire) take the shared-reward ring only: their blocks carry the
+ * shared reward (PW_EINVAL otherwise).
  *   state_rows = 1 (0.1.6): a STATE ring.  obs / next_obs are [cap,N,4] f32 planes holding {vx, vy, px, py} of every agent (the
  *     first four columns of its observation row) and lm [cap,L,2] the landmarks of the transition's episode: 32N + 8L bytes per
  *     transition instead of 8ND (C2: 240 instead of 768) -- what the learner rank writes per gathered transition.  obs_dim stays D:
@@ -252,7 +255,9 @@ size_t pw_algorithmic_bytes_per_env_step(const pw_handle *h);
  *     batch is bit-identical to the row ring's).  scenario / num_landmarks / num_adversaries name the row layout: PW_SIMPLE_SPREAD
  *     with the local observation (D = 4 + 2L) or PW_SIMPLE_TAG (D = 4 + 2L + 2(N - 1) + 2(N - A), good agents' rows zero-padded).
  *     Filled by pw_replay_add_state_wire and by the pw_policy_rollout ring sink (which hold the state itself); the writers that are
- *     handed ROWS return PW_EINVAL (a row cannot be turned back into the landmarks it was built from).  Plain single-head, shared-reward rings only. */
+ *     handed ROWS return PW_EINVAL (a row cannot be turned back into the landmarks it was built from).  Single-head rings only.  0.1.22: per_agent = 1 is served
+ *     -- rew / done [cap,N], filled by the pw_policy_rollout sink alone (pw_replay_add_state_wire returns PW_EINVAL: the wire blocks
+ *     carry the shared reward); pw_replay_gather / pw_replay_sample return out_rew / out_done [b,N] and the rows of the shared STATE ring. */
 typedef struct pw_replay_store {
     float *obs, *next_obs, *rew, *done;
     uint8_t *act;
@@ -510,7 +515,10 @@ int pw_actor_fused(const float *X, const float *frag, const float *b1, const flo
  * ring may be NULL (bookkeeping only) and episode_return may be NULL (ring only).  0.1.6: the ring may be a STATE ring
  * (pw_replay_store.state_rows) of the handle's scenario (simple_spread with the local observation, simple_tag): the launch then leaves
  * {vel, pos} of every agent before / after the step and the episode's landmarks per transition -- 254 B at C2 instead of 782 -- and
- * pw_replay_gather rebuilds the rows when a batch is sampled (bit-identical to the row ring's batch). */
+ * pw_replay_gather rebuilds the rows when a batch is sampled (bit-identical to the row ring's batch).  0.1.22: the ring may be a
+ * per-agent ring (pw_replay_store.per_agent, rew / done [cap,N]) wherever the form takes a ring: rew[slot, a] is then the value the
+ * launch writes to io->rew[t, env, a] and done[slot, a] = 0 (a shared ring: rew[slot] = io->rew_shared[t, env]); slot order, obs,
+ * next_obs, act and lm are those of the shared ring, and the episode bookkeeping stays on the shared sum. */
 typedef struct pw_rollout_sink {
     const pw_replay_store *ring;
     int64_t ring_start;
@@ -535,14 +543,14 @@ typedef struct pw_rollout_sink {
  * simple_reference (the MultiDiscrete scenario of main.py:24,52-54; 3 landmarks, D = 21): the two-head actor -- w2 [5 + PW_DIM_C,
  * 64] / b2 = dense2_1 and dense2_2 concatenated, one Gumbel-argmax per head exactly as pw_actor_fused(n_out0 = 5, n_out1 =
  * PW_DIM_C) -- and act_out [num_steps,B,N,2] = (movement, symbol); the ring sink must be the two-head ring (act_heads = 2, head widths
- * 5 | PW_DIM_C; 0.1.5 -- before, the chunk went into it with a second launch, pw_replay_add_rollout); results equal a loop of
+ * 5 | PW_DIM_C, shared-reward or per-agent; 0.1.5 -- before, the chunk went into it with a second launch, pw_replay_add_rollout); results equal a loop of
  * pw_actor_fused + pw_step(act_idx, act_comm).
  * Every other simple_spread / simple_tag configuration pw_step serves (0.1.9: the full observation, L > N, landmark contact on
  * simple_spread, per-agent sizes / accelerations / speed clamps, a simple_tag roster with one agent unlike its role, a handle with
  * pw_dispatch.force_generic): the generic form, pw_policy_rollout_generic_kernel -- the arithmetic of pw_rollout_kernel, so the same
  * bits as the pw_actor_fused + pw_step loop; one 5-logit head, exact float32 only, rows of at most 64 numbers, at most 96 rows and
- * 160 KB of LDS per workgroup (pw_policy_generic_envs_per_workgroup; PW_EINVAL naming N and D otherwise); the sink takes the plain
- * row ring only (a STATE, two-head or per-agent ring is PW_EINVAL).  Selected automatically for the handles the forms above refuse
+ * 160 KB of LDS per workgroup (pw_policy_generic_envs_per_workgroup; PW_EINVAL naming N and D otherwise); the sink takes the single-head
+ * row ring only, shared-reward or per-agent (a STATE or two-head ring is PW_EINVAL).  Selected automatically for the handles the forms above refuse
  * -- except handles whose agents differ within a role (size, acceleration, force scale or speed clamp unlike the role's first
  * agent), which stay PW_EINVAL under automatic dispatch -- and on any simple_spread / simple_tag handle by pw_dispatch.policy_form = 5. */
 int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const float *b_ih, const float *w_hh_fw,

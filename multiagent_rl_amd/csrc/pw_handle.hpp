@@ -77,21 +77,32 @@ int check_ready(const pw_handle *h)
     return PW_OK;
 }
 
-// The chunk / tail / packed / wire entry points and the rollout sink write the plain ring layout only.
-int plain_ring_only(const pw_replay_store *st, const char *who)
+// The rollout sink of the single-head forms writes a single-head ROW ring, with the shared reward or (0.1.22) per agent.
+int row_ring_only(const pw_replay_store *st, const char *who)
 {
-    if (st && (st->act_heads > 1 || st->per_agent))
-        return fail(PW_EINVAL, std::string(who) + ": two-head / per-agent rings are served by pw_replay_add and pw_replay_gather only");
+    if (st && st->act_heads > 1)
+        return fail(PW_EINVAL, std::string(who) + ": a two-head ring is served by pw_replay_add, pw_replay_add_rollout, pw_replay_gather and "
+                                                  "the simple_reference rollout sink only");
     if (st && st->state_rows)
         return fail(PW_EINVAL, std::string(who) + ": a STATE ring (pw_replay_store.state_rows) is filled by pw_replay_add_state_wire and read by "
                                                   "pw_replay_gather only -- observation rows cannot be turned back into the landmarks they were built from");
     return PW_OK;
 }
 
-// A state ring's own consistency (pw_replay_add_state_wire, pw_replay_gather).
+// The tail / packed / wire entry points write the plain ring layout only: the blocks they read carry the shared reward.
+int plain_ring_only(const pw_replay_store *st, const char *who)
+{
+    if (st && st->per_agent)
+        return fail(PW_EINVAL, std::string(who) + ": a per-agent ring is served by pw_replay_add, pw_replay_add_rollout, pw_replay_gather, "
+                                                  "pw_replay_sample and the pw_policy_rollout sink only (two-head / per-agent wire blocks are not served)");
+    return row_ring_only(st, who);
+}
+
+// A state ring's own consistency (pw_replay_add_state_wire, pw_replay_gather, pw_replay_sample, the rollout sink).  Single-head; the
+// reward planes may be per-agent (0.1.22: filled by the rollout sink alone -- pw_replay_add_state_wire refuses that ring itself).
 int state_ring_ok(const pw_replay_store *st, const char *who)
 {
-    if (st->act_heads > 1 || st->per_agent) return fail(PW_EINVAL, std::string(who) + ": a STATE ring is a plain single-head, shared-reward ring");
+    if (st->act_heads > 1) return fail(PW_EINVAL, std::string(who) + ": a STATE ring is a single-head ring (two-head rings are row rings)");
     const int N = st->num_agents, L = st->num_landmarks, A = st->num_adversaries;
     if (!st->lm && L > 0) return fail(PW_EINVAL, std::string(who) + ": STATE ring without a landmark plane");
     if (N < 1 || L < 0 || A < 0 || A > N) return fail(PW_EINVAL, std::string(who) + ": bad STATE ring shape");

@@ -276,7 +276,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout3_kernel(const PolicyRol
             if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
                 if (P.sink.ring.state_rows) sink_state_next(P.sink.ring, slot, N, a, px, py, vx, vy);
                 else stream_write_obs<LT>(P.sink.ring.next_obs + (slot * N + a) * D, L, lmv, px, py, vx, vy);
-                if (a == 0) { P.sink.ring.rew[slot] = t_acc; P.sink.ring.done[slot] = 0.0f; }
+                sink_reward(P.sink.ring, slot, N, a, t_rw, t_acc);
             }
             if (with_obs && V.obs) stream_write_obs<LT>(V.obs + (tBN + g) * D, L, lmv, px, py, vx, vy);
         }

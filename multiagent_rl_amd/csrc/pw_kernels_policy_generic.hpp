@@ -156,7 +156,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_generic_kernel(const Po
                 float *dst = P.sink.ring.next_obs + (slot * N + ln.a) * D;
                 if (with_obs) for (int c = 0; c < D / 2; ++c) reinterpret_cast<float2 *>(dst)[c] = src[c];
                 else write_obs<SCEN, OBS>(K, ln, dst, px, py, vx, vy, s_pos, s_vel, s_lm);
-                if (ln.a == 0) { P.sink.ring.rew[slot] = t_acc; P.sink.ring.done[slot] = 0.0f; }
+                sink_reward(P.sink.ring, slot, N, ln.a, t_rw, t_acc);
             }
             if (with_obs && P.obs) {
                 float2 *dst = reinterpret_cast<float2 *>(P.obs + row * D);

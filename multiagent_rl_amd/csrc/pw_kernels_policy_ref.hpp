@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_ref_kernel(const Policy
             if (with_obs && P.obs) ref_write_obs<DC, false>(V, s, co, a, P.obs + row * D);
             if (SINK && P.sink.has_ring) {  // next_obs is the PRE-reset observation (run.py:52 vs :60)
                 ref_write_obs<DC, false>(V, s, co, a, P.sink.ring.next_obs + (slot * N + a) * D);
-                if (a == 0) { P.sink.ring.rew[slot] = tail.acc; P.sink.ring.done[slot] = 0.0f; }
+                sink_reward(P.sink.ring, slot, N, a, tail.rw, tail.acc);
             }
         }
     };

@@ -208,7 +208,7 @@ __global__ void __launch_bounds__(512) pw_policy_rollout_tag_kernel(const Policy
                 if (P.sink.ring.state_rows) sink_state_next(P.sink.ring, slot, N, a, px, py, vx, vy);
                 else if (with_obs) copy_row2(dst, row, D / 2);
                 else write_row(dst);
-                if (a == 0) { P.sink.ring.rew[slot] = tail.acc; P.sink.ring.done[slot] = 0.0f; }
+                sink_reward(P.sink.ring, slot, N, a, tail.rw, tail.acc);
             }
             if (with_obs && V.obs) copy_row2(V.obs + (tBN + g) * D, row, D / 2);
         }

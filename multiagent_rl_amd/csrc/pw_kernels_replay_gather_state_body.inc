@@ -19,7 +19,10 @@
                 float *row = out_act + ea * W0;
                 for (int q = 0; q < W0; ++q) row[q] = a0 == q ? 1.0f : 0.0f;
             }
-            if (a == 0) {
+            if (st.per_agent) {  // the BiCNet tuple: planes [cap,N] -> [b,N]
+                if (out_rew) out_rew[ea] = st.rew[slot * N + a];
+                if (out_done) out_done[ea] = st.done[slot * N + a];
+            } else if (a == 0) {
                 if (out_rew) out_rew[e] = st.rew[slot];
                 if (out_done) out_done[e] = st.done[slot];
             }

@@ -28,7 +28,8 @@ ActorFusedArgs actor_args(const float *frag, const float *b1, const float *b_ih,
 bool sink_takes(const pw_rollout_sink *sink) { return sink && (sink->ring || sink->episode_return); }
 
 // A rollout sink's ring has the rollout's row shape and room for the chunk of `rows` transitions from a valid cursor, and its
-// bookkeeping pointers come together.
+// bookkeeping pointers come together.  The planes are the caller's: rew / done hold `capacity` floats, capacity * N on a per-agent ring
+// (pw_replay_store.per_agent), and every slot the launch writes is below capacity.
 int sink_fits(const pw_rollout_sink *sink, int N, int D, int64_t rows)
 {
     const pw_replay_store *ring = sink->ring;

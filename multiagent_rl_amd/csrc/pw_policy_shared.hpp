@@ -144,6 +144,20 @@ __device__ __forceinline__ void sink_state_next(const pw_replay_store &ring, con
     reinterpret_cast<float4 *>(ring.next_obs)[slot * N + a] = make_float4(vx, vy, px, py);
 }
 
+// Reward and done flag of transition `slot`, by every live lane of the env: the shared ring takes the ordered sum `acc` from agent 0's
+// lane; a per-agent ring (pw_replay_store.per_agent: planes [cap,N], the BiCNet tuple) takes the lane's own reward `rw` -- the value the
+// launch writes to rew[t, env, a].  done is 0: these scenarios have no done callback.  The ring's kind is wave-uniform (a kernel argument).
+__device__ __forceinline__ void sink_reward(const pw_replay_store &ring, const size_t slot, const int N, const int a, const float rw,
+                                            const float acc)
+{
+    const bool pa = ring.per_agent != 0;
+    if (pa || a == 0) {   // one pair of stores for both rings: the ring's kind selects the index and the value
+        const size_t i = pa ? slot * N + a : slot;
+        ring.rew[i] = pa ? rw : acc;
+        ring.done[i] = 0.0f;
+    }
+}
+
 // Ring slot of transition (t, env) of a chunk that starts at ring_start: (ring_start + t * B + env) mod capacity WITHOUT the 64-bit
 // division (~150 instructions on the environment waves' critical path, every step): the host guarantees 0 <= ring_start < capacity and
 // T * B <= capacity, so the sum is below 2 * capacity and one conditional subtraction is the modulo.

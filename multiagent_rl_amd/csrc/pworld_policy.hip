@@ -124,9 +124,10 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
     if (h->cfg.scenario == PW_SIMPLE_REFERENCE) {
         // the MultiDiscrete scenario: two-head actor [5 | PW_DIM_C] (w2 [15,64], b2 [15]), act_out [T,B,N,2]
         if (sink) {
-            if (sink->ring && (sink->ring->act_heads != 2 || sink->ring->per_agent || sink->ring->head_width[1] != PW_DIM_C ||
+            if (sink->ring && (sink->ring->act_heads != 2 || sink->ring->state_rows || sink->ring->head_width[1] != PW_DIM_C ||
                                (sink->ring->head_width[0] != 0 && sink->ring->head_width[0] != 5)))
-                return fail(PW_EINVAL, "pw_policy_rollout sink on simple_reference: the ring must be the two-head ring (act_heads = 2, widths 5 | dim_c)");
+                return fail(PW_EINVAL, "pw_policy_rollout sink on simple_reference: the ring must be the two-head row ring (act_heads = 2, widths 5 | dim_c; "
+                                       "shared-reward or per-agent)");
             if (int rc = sink_fits(sink, 2, kp.D, (int64_t)num_steps * kp.B)) return rc;
         }
         if (io->act_idx || io->act_vec || io->act_comm || io->coll)
@@ -191,7 +192,7 @@ int pw_policy_rollout(pw_handle *h, const float *frag, const float *b1, const fl
             if (int rc = state_ring_ok(sink->ring, "pw_policy_rollout sink")) return rc;
             if (sink->ring->scenario != h->cfg.scenario || sink->ring->num_landmarks != kp.L || sink->ring->num_adversaries != (tag ? kp.A : 0))
                 return fail(PW_EINVAL, "pw_policy_rollout sink: the STATE ring belongs to another scenario / shape");
-        } else if (int rc = plain_ring_only(sink->ring, "pw_policy_rollout sink")) return rc;
+        } else if (int rc = row_ring_only(sink->ring, "pw_policy_rollout sink")) return rc;   // shared-reward or per-agent
         if (int rc = sink_fits(sink, kp.N, kp.D, (int64_t)num_steps * kp.B)) return rc;
     }
     if ((reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(frag) |

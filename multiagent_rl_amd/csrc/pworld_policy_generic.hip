@@ -48,8 +48,9 @@ int pw_internal_policy_rollout_generic(pw_handle *h, const float *frag, const fl
     if (!sink_takes(sink) && (!act_out || !io->obs || !io->rew || !io->rew_shared || !io->done || !io->terminal))
         return fail(PW_EINVAL, "without a sink (a ring or the episode bookkeeping), act_out and the obs, rew, rew_shared, done, terminal outputs are required");
     if (sink) {
-        // a full row is not a function of the stored state alone for every configuration served here: the plain row ring only
-        if (int rc = plain_ring_only(sink->ring, "pw_policy_rollout sink (generic form)")) return rc;
+        // a full row is not a function of the stored state alone for every configuration served here: the single-head row ring only
+        // (shared-reward or per-agent)
+        if (int rc = row_ring_only(sink->ring, "pw_policy_rollout sink (generic form)")) return rc;
         if (int rc = sink_fits(sink, kp.N, kp.D, (int64_t)num_steps * kp.B)) return rc;
     }
     if ((reinterpret_cast<uintptr_t>(io->obs) | reinterpret_cast<uintptr_t>(io->final_obs) | reinterpret_cast<uintptr_t>(frag) |

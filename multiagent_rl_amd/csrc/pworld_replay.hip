@@ -414,6 +414,8 @@ int pw_replay_add_state_wire(const pw_replay_store *st, int64_t start, const pw_
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t agents = (size_t)w->T * w->B * w->N;
     if (st->state_rows) {  // STATE ring: copy what the block carries; pw_replay_gather rebuilds the rows
+        if (st->per_agent)
+            return fail(PW_EINVAL, "pw_replay_add_state_wire: a per-agent STATE ring is filled by the pw_policy_rollout sink only (the wire blocks carry the shared reward)");
         if (int rc = state_ring_ok(st, "pw_replay_add_state_wire")) return rc;
         if (st->scenario != w->scenario || st->num_landmarks != w->L || st->num_adversaries != w->num_adversaries)
             return fail(PW_EINVAL, "STATE ring / wire scenario mismatch");
@@ -466,7 +468,9 @@ int pw_replay_add_ref_wire(const pw_replay_store *st, int64_t start, const pw_re
 {
     if (!st) return fail(PW_EINVAL, "null argument");
     if (int rc = check_ref_wire(w, wire)) return rc;
-    if (st->state_rows || st->per_agent || st->act_heads != 2 || st->head_width[1] != PW_DIM_C || (st->head_width[0] != 0 && st->head_width[0] != 5))
+    if (st->per_agent)
+        return fail(PW_EINVAL, "pw_replay_add_ref_wire: a per-agent ring is not served (the compact-row blocks carry the shared reward only)");
+    if (st->state_rows || st->act_heads != 2 || st->head_width[1] != PW_DIM_C || (st->head_width[0] != 0 && st->head_width[0] != 5))
         return fail(PW_EINVAL, "pw_replay_add_ref_wire: the ring must be the two-head ring of simple_reference (act_heads = 2, head widths 5 | dim_c)");
     if (st->num_agents != kRefN || st->obs_dim != kRefD) return fail(PW_EINVAL, "ring / wire shape mismatch (simple_reference: N = 2, D = 21)");
     if (!ring_fits(st, (int64_t)w->T * w->B, start))

@@ -282,7 +282,8 @@ class FusedActor(object):
         from the env's current state.  -> dict of [T, ...] outputs as ``BatchedParticleEnv.rollout`` plus
         ``act`` [T,B,N] int32.  Same results as ``num_steps`` iterations of ``act = self(obs); env.step(act)``.
 
-        ``memory`` (a device ``ReplayBuffer``): the transitions go straight into the ring from the same launch;
+        ``memory`` (a device ``ReplayBuffer``): the transitions go straight into the ring from the same launch (a ``per_agent`` ring takes
+        every agent's own reward, ``out['rew']``, into its [cap, N] planes; a shared ring ``out['rew_shared']``);
         ``stats`` = (episode_return [B], finished_sum, finished_count) tensors: the episode bookkeeping too.  With a
         sink, ``out=False`` skips the step outputs altogether (only the ring / statistics are written), and a caller's ``out`` may
         hold any subset of them (``'act': None`` leaves the sampled actions out; an absent ``'act'`` is allocated here).  What is left

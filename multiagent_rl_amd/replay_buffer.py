@@ -27,7 +27,9 @@ Ring variants (what ``add`` receives decides, or pass them to the constructor):
     768) -- and ``sample_index`` REBUILDS the observation rows it returns (every entry is the state itself or one float32
     subtraction: the batch is bit-identical to the row ring's).  It is the learner rank's ring of the multi-GPU gather
     (``dist.FullTransitionGather(..., ring='state')`` fills it from state-only wire blocks); ``add`` / ``add_batch`` /
-    ``add_rollout`` raise on it -- a row cannot be turned back into the landmarks it was built from.
+    ``add_rollout`` raise on it -- a row cannot be turned back into the landmarks it was built from.  With ``per_agent=True`` its
+    ``rew`` / ``done`` planes are [cap, N] and ``sample_index`` / ``sample`` return them as [b, N]; that ring is filled by the one-launch
+    rollout's sink alone (``FusedActor.rollout(..., memory=ring)``, ``BatchedRollout.collect_one_launch``).
 The ring holds HARD one-hot actions as indices (what force_discrete_action / hard Gumbel-softmax produce); rows that
 are not one-hot per head, or whose lengths differ between agents, are rejected loudly instead of being squeezed
 through an argmax.  The object pickles (experiments/run.py:186-191 stores the memory in the test history): the
@@ -85,8 +87,8 @@ class ReplayBuffer(object):
             sr = dict(state_ring)
             if sr.get('scenario') not in ('simple_spread', 'simple_tag'):
                 raise ValueError("state_ring: scenario must be 'simple_spread' (local observation) or 'simple_tag'")
-            if (self.act_heads or (5,)) != (5,) or self.per_agent:
-                raise ValueError('a STATE ring is a plain single-head, shared-reward ring')
+            if (self.act_heads or (5,)) != (5,):
+                raise ValueError('a STATE ring is a single-head ring (shared-reward or per-agent)')
             if num_agents is None or obs_dim is None:
                 raise ValueError('a STATE ring needs num_agents and obs_dim at construction')
             self.state_ring = dict(scenario=sr['scenario'], num_landmarks=int(sr['num_landmarks']),

@@ -336,23 +336,14 @@ class BatchedRollout(object):
         (row or STATE ring); every other configuration ``env.step`` serves -- the full observation, L > N, landmark contact,
         ``dispatch=dict(force_generic=1)`` -- runs on the generic one-launch kernel with a plain row ring, rows of at most 64 numbers;
         agents that differ within a role need ``env.set_dispatch(policy_form=5)``.  Stores exactly what ``collect`` stores (statistics up
-        to float64 summation order).  A per-agent ``memory`` (the BiCNet tuple) is not served by the in-kernel ring sink: the chunk runs
-        with the statistics sink alone and its outputs go into the ring with ``memory.add_rollout`` -- two launches per chunk."""
+        to float64 summation order).  A per-agent ``memory`` (the BiCNet tuple: ``rew`` / ``done`` [cap, N]; row, STATE or two-head ring as
+        above) is the same single launch: every agent's lane stores its own reward where the shared ring takes the sum from agent 0's."""
         assert self._graph is None and hasattr(self.policy, 'rollout')
         stats = (self.episode_return, self.finished_return_sum, self.finished_episodes)
         done_steps = 0
-        per_agent = self._per_agent_memory()
-        obs0 = self.obs      # the observation the chunk starts from: self.obs, then the previous chunk's last obs
         while done_steps < num_steps:
             T = min(chunk, num_steps - done_steps)
-            if per_agent:
-                # two sets of output buffers in turn: obs0 is a view of the previous chunk's, which this chunk's launch must not overwrite
-                bufs = self.__dict__.setdefault('_pa_chunks', {})
-                flip = self._pa_flip = 1 - getattr(self, '_pa_flip', 0)
-                out = bufs[(T, flip)] = self.policy.rollout(self.env, T, bufs.get((T, flip)), memory=None, stats=stats)
-                self.memory.add_rollout(obs0.contiguous(), out)
-                obs0, self.last_chunk = out['obs'][T - 1], out
-            elif keep_outputs:
+            if keep_outputs:
                 if getattr(self, '_chunk_T', None) != T:
                     self._chunk_T, self.last_chunk = T, None
                 self.last_chunk = self.policy.rollout(self.env, T, self.last_chunk, memory=self.memory, stats=stats)

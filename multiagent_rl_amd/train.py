@@ -121,8 +121,9 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     third of the bytes -- and ``sample_index`` rebuilds the rows the learner trains on (bit-identical batches).  Envs only the generic
     one-launch rollout serves (the full observation, L > N, landmark contact on simple_spread, ``policy_form=5``) take ``ring='rows'``:
     their rollout refuses a STATE ring.  ``per_agent_transition=True`` (the BiCNet baseline, ``experiments/run_BIC.py:46,50``): the ring
-    holds per-agent ``rew`` / ``done`` planes ([cap, N]) and every chunk is the policy rollout followed by ``memory.add_rollout`` (two
-    launches); single-rank row rings only -- with ``gather`` or ``ring='state'`` it raises.  ``graph_update=True``: the ring this
+    holds per-agent ``rew`` / ``done`` planes ([cap, N]) and every chunk is one launch, as with a shared ring (the rollout's sink stores
+    every agent's own reward).  The ring built here is the single-rank row ring -- with ``gather`` or ``ring='state'`` it raises; a
+    per-agent STATE ring (``ReplayBuffer(per_agent=True, state_ring=...)``) comes in through ``memory=``.  ``graph_update=True``: the ring this
     function creates draws its batches from device cells (``ReplayBuffer(device_index='counter')``) and the learner's ``optimize`` is
     replaced, after construction, by a ``graph.GraphedUpdate`` (a learner that has installed one itself keeps it): a few eager updates,
     then one graph launch per update; the learner must be in the configuration that serves (``accelerate_trainer``'s four switches), or
