@@ -14,9 +14,10 @@ critic from the reference checkout on ``sys.path`` (``rls.agent.multiagent.ddpg_
 learner of ``examples/madr_learner.py`` stands in (the learner is not part of this repo's scope).  ``--critic attention`` gives
 it the reference's critic architecture (``multiagent_rl_amd.critic.CriticNetwork``); ``--critic bicnet`` is the BiCNet baseline: per-agent
 transitions (``train_batched(per_agent_transition=True)``), ``multiagent_rl_amd.critic.BiCNetCritic`` and the per-agent stand-in learner
-(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), single rank only -- where the other critics get a
-STATE ring (simple_spread with the local observation, simple_tag; not ``--policy-form 5``) the script builds the per-agent STATE ring itself
-and passes it as ``memory=``, the row ring otherwise or under ``--ring rows`` (the batches are bit-identical); ``--critic model`` is the
+(with ``--reference``: ``BIC_gumbel_fix.Trainer`` and ``ac_network_multi_gumbel_BIC``), any number of ranks -- where the other critics get a
+STATE ring (simple_spread with the local observation, simple_tag; not ``--policy-form 5``) a single rank builds the per-agent STATE ring itself
+and passes it as ``memory=``, the row ring otherwise or under ``--ring rows`` (the batches are bit-identical); with several ranks the ring is the
+gather's (``FullTransitionGather(per_agent=True)``: per-agent wire blocks, the same choice of ring); ``--critic model`` is the
 paper's own method, the model-learning variant: ``ModelActorNetwork`` / ``ModelCriticNetwork`` and ``madr_learner.ModelTrainer`` (with
 ``--reference``: ``model_ddpg_gumbel_fix.Trainer`` and ``ac_network_model_multi_gumbel``) on the shared-reward ring, any number of ranks.  ``--fused-targets`` runs its target networks'
 forwards on the HIP kernels (``accelerate_trainer(trainer, targets=True)``), ``--fused-optimizer`` runs each network's clip + Adam +
@@ -131,8 +132,6 @@ def main(argv=None):
     if args.fused_targets and args.critic not in ('attention', 'bicnet', 'model') and not args.reference:
         ap.error('--fused-targets needs --critic attention, bicnet or model (the HIP critics are the LSTM architectures)')
     bicnet, model = args.critic == 'bicnet', args.critic == 'model'
-    if bicnet and int(os.environ.get('WORLD_SIZE', '1')) > 1:
-        ap.error('--critic bicnet is single-rank: the multi-rank gather carries the shared reward only')
 
     os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')   # dmabuf IPC for multi-process GPU work (read at the first GPU call)
     import torch
@@ -229,7 +228,7 @@ def main(argv=None):
                          '(not --full-observation, not --policy-form 5)')
             state_ok = state_ok and args.ring != 'rows'
             memory = None
-            if bicnet and state_ok:
+            if bicnet and state_ok and world == 1:
                 # the per-agent STATE ring: train_batched(per_agent_transition=True) builds the row ring only, this one comes in as memory=
                 from multiagent_rl_amd.replay_buffer import ReplayBuffer
                 memory = ReplayBuffer(int(1e6), env.n, env.obs_dim, per_agent=True, device_index='counter' if args.graph_update else True,
@@ -245,9 +244,10 @@ def main(argv=None):
                 actor = actor.to(dev)
                 broadcast_actor(actor, src=0)                                  # same initial weights on every rank
                 # state-only blocks (simple_spread, simple_tag) land in a STATE ring on the learner rank (rows rebuilt when a batch is
-                # sampled: a third of the ring writes); simple_reference travels on compact-row blocks into its two-head row ring
+                # sampled: a third of the ring writes); simple_reference travels on compact-row blocks into its two-head row ring;
+                # --critic bicnet: per-agent wire blocks into the per-agent ring of the same kind
                 state_ring = state_ok
-                gather = FullTransitionGather(env, args.chunk, rank, world, dev, ring='state' if state_ring else 'rows')
+                gather = FullTransitionGather(env, args.chunk, rank, world, dev, ring='state' if state_ring else 'rows', per_agent=bicnet)
                 gather.prime()
             hist = train_batched(env, actor, critic, Trainer, scenario_name, action_type, cnt=cnt, out_dir=args.out_dir,
                                  chunk=args.chunk, max_updates_per_chunk=args.max_updates_per_chunk, gather=gather,

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 122 /* 0.1.22: the ring of pw_rollout_sink may be a per-agent ring (pw_replay_store.per_agent: rew / done [cap,N]) in every form of pw_policy_rollout -- the row ring and the STATE ring of the simple_spread / simple_tag forms, the row ring of the generic form, the two-head ring of simple_reference: every live lane stores its own reward, the value the launch writes to rew[t, env, a], and done = 0; a STATE ring may be per-agent (single head; pw_replay_gather / pw_replay_sample then return out_rew / out_done [b,N]).  The tail / packed / wire entry points keep refusing a per-agent ring.  No entry point changed.  0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 123 /* 0.1.23: + pw_replay_add_wire_agents / pw_replay_add_state_wire_agents / pw_replay_add_ref_wire_agents and pw_wire_agent_rew_bytes (per-agent wire blocks: the per-agent reward plane rew [T,B,N] f32 travels as a trailer behind a wire block of any format, at offset total_bytes, and the learner rank's append writes a per-agent ring -- row ring, STATE ring, simple_reference's two-head ring -- in one launch; the BiCNet baseline trains on several ranks).  No struct, layout or entry point changed: the plain wire entry points keep refusing a per-agent ring.  0.1.22: the ring of pw_rollout_sink may be a per-agent ring (pw_replay_store.per_agent: rew / done [cap,N]) in every form of pw_policy_rollout -- the row ring and the STATE ring of the simple_spread / simple_tag forms, the row ring of the generic form, the two-head ring of simple_reference: every live lane stores its own reward, the value the launch writes to rew[t, env, a], and done = 0; a STATE ring may be per-agent (single head; pw_replay_gather / pw_replay_sample then return out_rew / out_done [b,N]).  The tail / packed / wire entry points keep refusing a per-agent ring.  No entry point changed.  0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -247,7 +247,9 @@ size_t pw_algorithmic_bytes_per_env_step(const pw_handle *h);
  * pw_policy_rollout sink (0.1.22) takes the single-head ring on simple_spread / simple_tag and the two-head ring on simple_reference,
  * each with the shared reward or per-agent.  The tail / packed / wire entry points (pw_replay_add_tail, pw_replay_add_packed,
  * pw_replay_add_wire, pw_replay_add_state_wire, pw_replay_add_ref_wire) take the shared-reward ring only: their blocks carry the
- * shared reward (PW_EINVAL otherwise).
+ * shared reward (PW_EINVAL otherwise).  The per-agent ring's wire entry points (0.1.23) are pw_replay_add_wire_agents,
+ * pw_replay_add_state_wire_agents and pw_replay_add_ref_wire_agents: the same blocks with the per-agent reward plane behind them
+ * (pw_wire_agent_rew_bytes); they take the per-agent ring only (PW_EINVAL for a shared-reward ring).
  *   state_rows = 1 (0.1.6): a STATE ring.  obs / next_obs are [cap,N,4] f32 planes holding {vx, vy, px, py} of every agent (the
  *     first four columns of its observation row) and lm [cap,L,2] the landmarks of the transition's episode: 32N + 8L bytes per
  *     transition instead of 8ND (C2: 240 instead of 768) -- what the learner rank writes per gathered transition.  obs_dim stays D:
@@ -256,8 +258,9 @@ size_t pw_algorithmic_bytes_per_env_step(const pw_handle *h);
  *     with the local observation (D = 4 + 2L) or PW_SIMPLE_TAG (D = 4 + 2L + 2(N - 1) + 2(N - A), good agents' rows zero-padded).
  *     Filled by pw_replay_add_state_wire and by the pw_policy_rollout ring sink (which hold the state itself); the writers that are
  *     handed ROWS return PW_EINVAL (a row cannot be turned back into the landmarks it was built from).  Single-head rings only.  0.1.22: per_agent = 1 is served
- *     -- rew / done [cap,N], filled by the pw_policy_rollout sink alone (pw_replay_add_state_wire returns PW_EINVAL: the wire blocks
- *     carry the shared reward); pw_replay_gather / pw_replay_sample return out_rew / out_done [b,N] and the rows of the shared STATE ring. */
+ *     -- rew / done [cap,N], filled by the pw_policy_rollout sink and (0.1.23) by pw_replay_add_state_wire_agents, which reads the
+ *     per-agent reward plane behind the block (pw_replay_add_state_wire itself returns PW_EINVAL: the block carries the shared
+ *     reward); pw_replay_gather / pw_replay_sample return out_rew / out_done [b,N] and the rows of the shared STATE ring. */
 typedef struct pw_replay_store {
     float *obs, *next_obs, *rew, *done;
     uint8_t *act;
@@ -448,6 +451,31 @@ int pw_ref_wire_layout(int32_t T, int32_t B, int32_t max_episode_len, pw_ref_wir
 int pw_ref_wire_finalize(const pw_ref_wire *w, void *wire, const float *obs0, const float *obs, const float *final_obs,
                          const uint8_t *terminal, const int32_t *act, void *stream);
 int pw_replay_add_ref_wire(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire, void *stream);
+
+/* ---- per-agent wire blocks (0.1.23): the gather for a per-agent ring (pw_replay_store.per_agent; the BiCNet tuple) -------------------
+ * The three block structs above keep their bytes.  The per-agent reward travels as a TRAILER PLANE behind the block:
+ *   rew [T,B,N] f32         at offset w->total_bytes (a multiple of 256) of a block of any format; the rollout writes it in place
+ *                           (pw_step_io.rew pointing there), as it writes rew_shared into the block
+ * so a per-agent block is w->total_bytes + pw_wire_agent_rew_bytes(T, B, N) bytes: 4N more per env-step (state blocks: 21N + 5
+ * instead of 17N + 5).  The sender's calls are the ones above (layout, begin, finalize); nothing else is launched there. */
+/* bytes of the per-agent reward plane rew [T,B,N] f32 that follows a wire block of any format at offset
+ * w->total_bytes (a multiple of 256), rounded up to 256; 0 sizes are PW_EINVAL-style 0 */
+size_t pw_wire_agent_rew_bytes(int32_t T, int32_t B, int32_t N);
+/* Root: pw_replay_add_wire / pw_replay_add_state_wire / pw_replay_add_ref_wire for a PER-AGENT ring, one launch each.  Transition
+ * (t, e) goes to slot (start + t*B + e) % capacity; obs / next_obs / act (and a STATE ring's lm) are written exactly as the plain
+ * entry point writes them; st->rew[slot*N + a] = rew_agents[(t*B + e)*N + a] and st->done[slot*N + a] = 0 (these scenarios have no
+ * done callback: what the pw_policy_rollout sink stores).  rew_agents is a device pointer to [T,B,N] f32 -- wire + w->total_bytes
+ * in the layout above, or wherever a C host keeps the plane; the block's rew_shared plane is not read.  Served: the row ring from
+ * row blocks, the row ring and the STATE ring from state blocks, simple_reference's two-head ring from its compact rows.
+ * PW_EINVAL, nothing launched: a ring with per_agent == 0 (use the plain entry point), a null or misaligned rew_agents, and
+ * everything the plain entry point refuses (shape or scenario mismatch, a chunk larger than the ring, a two-head ring for a
+ * single-head block and the reverse). */
+int pw_replay_add_wire_agents(const pw_replay_store *st, int64_t start, const pw_chunk_wire *w, const void *wire,
+                              const float *rew_agents, void *stream);
+int pw_replay_add_state_wire_agents(const pw_replay_store *st, int64_t start, const pw_state_wire *w, const void *wire,
+                                    const float *rew_agents, void *stream);
+int pw_replay_add_ref_wire_agents(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire,
+                                  const float *rew_agents, void *stream);
 
 /* Episode bookkeeping of the rollout loop (experiments/run.py:55-65) over B envs in one launch:
  * episode_return[b] += rew_shared[b]; where terminal[b]: *finished_sum += return (double),

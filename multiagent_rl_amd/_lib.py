@@ -141,6 +141,10 @@ SIGNATURES = {
     'pw_ref_wire_layout': (C.c_int, [C.c_int32] * 3 + [C.POINTER(PwRefWire)]),
     'pw_ref_wire_finalize': (C.c_int, [C.POINTER(PwRefWire)] + [C.c_void_p] * 7),
     'pw_replay_add_ref_wire': (C.c_int, [C.POINTER(PwReplayStore), C.c_int64, C.POINTER(PwRefWire), C.c_void_p, C.c_void_p]),
+    'pw_wire_agent_rew_bytes': (C.c_size_t, [C.c_int32] * 3),
+    'pw_replay_add_wire_agents': (C.c_int, [C.POINTER(PwReplayStore), C.c_int64, C.POINTER(PwChunkWire)] + [C.c_void_p] * 3),
+    'pw_replay_add_state_wire_agents': (C.c_int, [C.POINTER(PwReplayStore), C.c_int64, C.POINTER(PwStateWire)] + [C.c_void_p] * 3),
+    'pw_replay_add_ref_wire_agents': (C.c_int, [C.POINTER(PwReplayStore), C.c_int64, C.POINTER(PwRefWire)] + [C.c_void_p] * 3),
     'pw_dense': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                           C.c_void_p]),
     'pw_actor_front_pack_floats': (C.c_size_t, [C.c_int32]),

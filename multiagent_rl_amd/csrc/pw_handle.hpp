@@ -99,7 +99,8 @@ int plain_ring_only(const pw_replay_store *st, const char *who)
 }
 
 // A state ring's own consistency (pw_replay_add_state_wire, pw_replay_gather, pw_replay_sample, the rollout sink).  Single-head; the
-// reward planes may be per-agent (0.1.22: filled by the rollout sink alone -- pw_replay_add_state_wire refuses that ring itself).
+// reward planes may be per-agent (0.1.22: filled by the rollout sink; 0.1.23: and by pw_replay_add_state_wire_agents -- pw_replay_add_state_wire
+// refuses that ring itself).
 int state_ring_ok(const pw_replay_store *st, const char *who)
 {
     if (st->act_heads > 1) return fail(PW_EINVAL, std::string(who) + ": a STATE ring is a single-head ring (two-head rings are row rings)");

@@ -418,35 +418,48 @@ __global__ void __launch_bounds__(256) pw_chunk_wire_finalize_kernel(const pw_ch
         p.act[i] = (uint8_t)act[i];
 }
 
+// Reward and done words of chunk cell te = t*B + e in ring slot `slot`, in every root-side append body below (in the manner of
+// sink_reward in pw_policy_shared.hpp, with the ring's kind a compile-time switch).  The shared ring (PW_WIRE_PA false) takes the block's
+// rew_shared[te] from the one thread per transition that `lead` names.  A per-agent ring (PW_WIRE_PA true: planes [cap,N], the BiCNet
+// tuple) takes agent a's word of the trailer plane PW_WIRE_REW = rew_agents [T,B,N] (include/pworld.h, pw_wire_agent_rew_bytes) from
+// the thread that stores agent a's action byte: the trailer read is contiguous in (t, e, a), the ring write contiguous in (slot, a),
+// and the block's rew_shared plane is not read.  done is 0: these scenarios have no done callback.  Statements, not a function: the
+// bodies they stand in are the kernels' own text, and the shared instantiations compile to the code they compiled to before.
+#define PW_WIRE_REWARD(N, a, lead)                                   \
+    do {                                                             \
+        if (PW_WIRE_PA) {                                            \
+            st.rew[slot * (N) + (a)] = PW_WIRE_REW[te * (N) + (a)];  \
+            st.done[slot * (N) + (a)] = 0.0f;                        \
+        } else if (lead) {                                           \
+            st.rew[slot] = p.rew_shared[te];                         \
+            st.done[slot] = 0.0f;                                    \
+        }                                                            \
+    } while (0)
+
 // Root side: the copy half of pw_replay_add_rollout_kernel reading a wire block.  V = floats per thread
 // (4 when N*D is a multiple of 4: 16-byte loads and stores; the planes are 256-B aligned, ring rows 16-B).
+// PA: the thread of columns [cV, cV + V) stores the action bytes of agents cV .. cV + V - 1 and, with them, those agents' reward / done
+// words: V consecutive words per lane, adjacent lanes adjacent, so the ceil(N / V) first lanes of a transition write its N words as one
+// contiguous run (and read the trailer the same way) -- no lane strides across another's cache line.
 template <int V>
 __global__ void __launch_bounds__(256) pw_replay_add_wire_kernel(const pw_replay_store st, const int64_t start,
                                                                  const pw_chunk_wire w, const void *wire)
 {
-    typedef float vec_t __attribute__((ext_vector_type(V)));
-    const WirePtrs p = wire_ptrs(w, const_cast<void *>(wire));
-    const int ND = w.N * w.D, N = w.N, NDV = ND / V;
-    const size_t per_step = (size_t)w.B * NDV, total = (size_t)w.T * per_step;
-    const vec_t *obs0 = reinterpret_cast<const vec_t *>(p.obs0), *obs = reinterpret_cast<const vec_t *>(p.obs);
-    const vec_t *fin = reinterpret_cast<const vec_t *>(p.final_rows);
-    vec_t *r_obs = reinterpret_cast<vec_t *>(st.obs), *r_next = reinterpret_cast<vec_t *>(st.next_obs);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t t = i / per_step, rem = i - t * per_step, e = rem / NDV, c = rem - e * NDV;
-        const size_t te = t * w.B + e;
-        const size_t slot = (size_t)((start + (int64_t)te) % st.capacity);
-        r_obs[slot * NDV + c] = t == 0 ? obs0[rem] : obs[i - per_step];
-        const unsigned fs = p.fin_slot[te];
-        r_next[slot * NDV + c] = fs != 0xFFu ? fin[(size_t)fs * per_step + rem] : obs[i];
-        for (int q = 0; q < V; ++q) {
-            const size_t cc = c * V + q;
-            if (cc < (size_t)N) st.act[slot * N + cc] = p.act[te * N + cc];
-        }
-        if (c == 0) {
-            st.rew[slot] = p.rew_shared[te];
-            st.done[slot] = 0.0f;
-        }
-    }
+#define PW_WIRE_PA false
+#define PW_WIRE_REW static_cast<const float *>(nullptr)
+#include "pw_kernels_replay_add_wire_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
+}
+template <int V>
+__global__ void __launch_bounds__(256) pw_replay_add_wire_agents_kernel(const pw_replay_store st, const int64_t start,
+                                                                        const pw_chunk_wire w, const void *wire, const float *rew_agents)
+{
+#define PW_WIRE_PA true
+#define PW_WIRE_REW rew_agents
+#include "pw_kernels_replay_add_wire_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
 }
 
 // ------------------------------------------------------------------------------------------
@@ -549,50 +562,21 @@ template <int V>
 __global__ void __launch_bounds__(256) pw_replay_add_state_wire_kernel(const pw_replay_store st, const int64_t start,
                                                                        const pw_state_wire w, const void *wire)
 {
-    typedef float vec_t __attribute__((ext_vector_type(V)));
-    const StateWirePtrs p = state_wire_ptrs(w, const_cast<void *>(wire));
-    const int N = w.N, L = w.L, CH = w.D / V;
-    const size_t BN = (size_t)w.B * N, per_step = BN * CH, total = (size_t)w.T * per_step;
-    vec_t *r_obs = reinterpret_cast<vec_t *>(st.obs), *r_next = reinterpret_cast<vec_t *>(st.next_obs);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t t = i / per_step, rem = i - t * per_step, ea = rem / CH, e = ea / N;
-        const int c = (int)(rem - ea * CH), a = (int)(ea - e * N);
-        const size_t te = t * w.B + e;
-        const unsigned epi = p.epi[te], k = epi & 0x7fu;
-        const float4 s_obs = t == 0 ? p.state0[ea] : p.state[(t - 1) * BN + ea];
-        const float4 s_next = (epi & 0x80u) ? p.final_state[(size_t)k * BN + ea] : p.state[t * BN + ea];
-        const float2 *lm = p.lm + ((size_t)k * w.B + e) * L;
-        vec_t o, n;
-        if (V == 4) {
-            if (c == 0) {
-                o[0] = s_obs.x; o[1] = s_obs.y; o[2] = s_obs.z; o[3] = s_obs.w;
-                n[0] = s_next.x; n[1] = s_next.y; n[2] = s_next.z; n[3] = s_next.w;
-            } else {
-                const float2 l0 = lm[2 * c - 2], l1 = lm[2 * c - 1];
-                o[0] = l0.x - s_obs.z; o[1] = l0.y - s_obs.w; o[2] = l1.x - s_obs.z; o[3] = l1.y - s_obs.w;
-                n[0] = l0.x - s_next.z; n[1] = l0.y - s_next.w; n[2] = l1.x - s_next.z; n[3] = l1.y - s_next.w;
-            }
-        } else {
-            if (c == 0) { o[0] = s_obs.x; o[1] = s_obs.y; n[0] = s_next.x; n[1] = s_next.y; }
-            else if (c == 1) { o[0] = s_obs.z; o[1] = s_obs.w; n[0] = s_next.z; n[1] = s_next.w; }
-            else {
-                const float2 l0 = lm[c - 2];
-                o[0] = l0.x - s_obs.z; o[1] = l0.y - s_obs.w;
-                n[0] = l0.x - s_next.z; n[1] = l0.y - s_next.w;
-            }
-        }
-        const size_t slot = (size_t)((start + (int64_t)te) % st.capacity);
-        const size_t at = (slot * N + a) * CH + c;
-        r_obs[at] = o;
-        r_next[at] = n;
-        if (c == 0) {
-            st.act[slot * N + a] = p.act[te * N + a];
-            if (a == 0) {
-                st.rew[slot] = p.rew_shared[te];
-                st.done[slot] = 0.0f;
-            }
-        }
-    }
+#define PW_WIRE_PA false
+#define PW_WIRE_REW static_cast<const float *>(nullptr)
+#include "pw_kernels_replay_add_state_wire_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
+}
+template <int V>
+__global__ void __launch_bounds__(256) pw_replay_add_state_wire_agents_kernel(const pw_replay_store st, const int64_t start,
+                                                                              const pw_state_wire w, const void *wire, const float *rew_agents)
+{
+#define PW_WIRE_PA true
+#define PW_WIRE_REW rew_agents
+#include "pw_kernels_replay_add_state_wire_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
 }
 
 
@@ -641,60 +625,45 @@ __device__ __forceinline__ float2 state_row_unit(const RowGeom &G, const int a, 
 __global__ void __launch_bounds__(256) pw_replay_add_state_wire_units_kernel(const pw_replay_store st, const int64_t start,
                                                                              const pw_state_wire w, const void *wire)
 {
-    const StateWirePtrs p = state_wire_ptrs(w, const_cast<void *>(wire));
-    const RowGeom G = {w.scenario, w.N, w.L, w.num_adversaries};
-    const int N = w.N, U = w.D / 2;
-    const size_t BN = (size_t)w.B * N, per_step = BN * U, total = (size_t)w.T * per_step;
-    float2 *r_obs = reinterpret_cast<float2 *>(st.obs), *r_next = reinterpret_cast<float2 *>(st.next_obs);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t t = i / per_step, rem = i - t * per_step, ea = rem / U, e = ea / N;
-        const int k = (int)(rem - ea * U), a = (int)(ea - e * N);
-        const size_t te = t * w.B + e;
-        const unsigned epi = p.epi[te], ke = epi & 0x7fu;
-        const float4 *s_obs = (t == 0 ? p.state0 : p.state + (t - 1) * BN) + e * N;
-        const float4 *s_next = ((epi & 0x80u) ? p.final_state + (size_t)ke * BN : p.state + t * BN) + e * N;
-        const float2 *lm = p.lm + ((size_t)ke * w.B + e) * w.L;
-        const size_t slot = (size_t)((start + (int64_t)te) % st.capacity);
-        const size_t at = (slot * N + a) * U + k;
-        r_obs[at] = state_row_unit(G, a, k, s_obs, lm);
-        r_next[at] = state_row_unit(G, a, k, s_next, lm);
-        if (k == 0) {
-            st.act[slot * N + a] = p.act[te * N + a];
-            if (a == 0) {
-                st.rew[slot] = p.rew_shared[te];
-                st.done[slot] = 0.0f;
-            }
-        }
-    }
+#define PW_WIRE_PA false
+#define PW_WIRE_REW static_cast<const float *>(nullptr)
+#include "pw_kernels_replay_add_state_wire_units_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
+}
+__global__ void __launch_bounds__(256) pw_replay_add_state_wire_units_agents_kernel(const pw_replay_store st, const int64_t start,
+                                                                                    const pw_state_wire w, const void *wire,
+                                                                                    const float *rew_agents)
+{
+#define PW_WIRE_PA true
+#define PW_WIRE_REW rew_agents
+#include "pw_kernels_replay_add_state_wire_units_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
 }
 
 // Root side, into a STATE ring (pw_replay_store.state_rows): the transition keeps what the block carries -- {vel, pos} of every agent
 // before and after the step (pre-reset where the step ended an episode) and the episode's landmarks; nothing is rebuilt here.
-// Thread = (step, env, agent): 2 x 16 B of state, the byte action, its share of the L landmarks; agent 0 the reward / done words.
+// Thread = (step, env, agent): 2 x 16 B of state, the byte action, its share of the L landmarks; agent 0 the reward / done words (PA:
+// every agent its own).
 __global__ void __launch_bounds__(256) pw_replay_add_state_wire_to_state_ring_kernel(const pw_replay_store st, const int64_t start,
                                                                                      const pw_state_wire w, const void *wire)
 {
-    const StateWirePtrs p = state_wire_ptrs(w, const_cast<void *>(wire));
-    const int N = w.N, L = w.L;
-    const size_t BN = (size_t)w.B * N, total = (size_t)w.T * BN;
-    float4 *r_s = reinterpret_cast<float4 *>(st.obs), *r_n = reinterpret_cast<float4 *>(st.next_obs);
-    float2 *r_lm = reinterpret_cast<float2 *>(st.lm);
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t t = i / BN, ea = i - t * BN, e = ea / N;
-        const int a = (int)(ea - e * N);
-        const size_t te = t * w.B + e;
-        const unsigned epi = p.epi[te], ke = epi & 0x7fu;
-        const size_t slot = (size_t)((start + (int64_t)te) % st.capacity);
-        r_s[slot * N + a] = t == 0 ? p.state0[ea] : p.state[(t - 1) * BN + ea];
-        r_n[slot * N + a] = (epi & 0x80u) ? p.final_state[(size_t)ke * BN + ea] : p.state[t * BN + ea];
-        const float2 *lm = p.lm + ((size_t)ke * w.B + e) * L;
-        for (int l = a; l < L; l += N) r_lm[slot * L + l] = lm[l];
-        st.act[slot * N + a] = p.act[te * N + a];
-        if (a == 0) {
-            st.rew[slot] = p.rew_shared[te];
-            st.done[slot] = 0.0f;
-        }
-    }
+#define PW_WIRE_PA false
+#define PW_WIRE_REW static_cast<const float *>(nullptr)
+#include "pw_kernels_replay_add_state_wire_to_state_ring_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
+}
+__global__ void __launch_bounds__(256) pw_replay_add_state_wire_to_state_ring_agents_kernel(const pw_replay_store st, const int64_t start,
+                                                                                            const pw_state_wire w, const void *wire,
+                                                                                            const float *rew_agents)
+{
+#define PW_WIRE_PA true
+#define PW_WIRE_REW rew_agents
+#include "pw_kernels_replay_add_state_wire_to_state_ring_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
 }
 
 // sample_index() on a STATE ring: thread = one unit of one agent's row pair of one sampled transition, REBUILT from the slot's states
@@ -806,41 +775,25 @@ __global__ void __launch_bounds__(256) pw_ref_wire_finalize_kernel(const pw_ref_
 }
 
 // Root: ReplayBuffer.add() of the block's T*B transitions into the two-head ring, rows rebuilt.  Thread = one column of one agent's
-// row pair (obs_t, next_obs_t).
+// row pair (obs_t, next_obs_t); columns 0 and 1 also store the agent's two action bytes, column 0 its reward / done words (PA) or, for
+// agent 0, the transition's.
 __global__ void __launch_bounds__(256) pw_replay_add_ref_wire_kernel(const pw_replay_store st, const int64_t start, const pw_ref_wire w,
                                                                      const void *wire)
 {
-    const RefWirePtrs p = ref_wire_ptrs(w, const_cast<void *>(wire));
-    const size_t BN = (size_t)w.B * kRefN, per_step = BN * kRefD, total = (size_t)w.T * per_step;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const size_t t = i / per_step, rem = i - t * per_step, ea = rem / kRefD, e = ea / kRefN;
-        const int c = (int)(rem - ea * kRefD), a = (int)(ea - e * kRefN);
-        const size_t te = t * w.B + e, other = e * kRefN + (1 - a);
-        const unsigned epi = p.epi[te], k = epi & 0x7fu;
-        const bool ended = (epi & 0x80u) != 0;
-        float o, n;
-        if (c < kRefHead) {
-            o = (t == 0 ? p.head0 : p.head + (t - 1) * BN * kRefHead)[ea * kRefHead + c];
-            n = (ended ? p.final_head + (size_t)k * BN * kRefHead : p.head + t * BN * kRefHead)[ea * kRefHead + c];
-        } else if (c < kRefHead + 3) {
-            o = n = (c - kRefHead) == (int)p.goal[(size_t)k * BN + ea] ? 0.75f : 0.25f;   // one episode: obs_t and next_obs_t share the goal
-        } else {
-            const int q = c - kRefHead - 3;
-            // what agent a sees of the other agent at step t: the symbol it sampled at step t - 1 (none right after a reset)
-            const unsigned prev = t == 0 ? p.comm0[ea] : ((p.epi[te - w.B] & 0x80u) ? 0xFFu : p.act[((t - 1) * BN + other) * 2 + 1]);
-            o = (unsigned)q == prev ? 1.0f : 0.0f;
-            n = q == (int)p.act[(t * BN + other) * 2 + 1] ? 1.0f : 0.0f;   // pre-reset or not: this step's symbol
-        }
-        const size_t slot = (size_t)((start + (int64_t)te) % st.capacity);
-        const size_t at = (slot * kRefN + a) * kRefD + c;
-        st.obs[at] = o;
-        st.next_obs[at] = n;
-        if (c < 2) st.act[(slot * kRefN + a) * 2 + c] = p.act[(t * BN + ea) * 2 + c];
-        if (c == 0 && a == 0) {
-            st.rew[slot] = p.rew_shared[te];
-            st.done[slot] = 0.0f;
-        }
-    }
+#define PW_WIRE_PA false
+#define PW_WIRE_REW static_cast<const float *>(nullptr)
+#include "pw_kernels_replay_add_ref_wire_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
+}
+__global__ void __launch_bounds__(256) pw_replay_add_ref_wire_agents_kernel(const pw_replay_store st, const int64_t start, const pw_ref_wire w,
+                                                                            const void *wire, const float *rew_agents)
+{
+#define PW_WIRE_PA true
+#define PW_WIRE_REW rew_agents
+#include "pw_kernels_replay_add_ref_wire_body.inc"
+#undef PW_WIRE_PA
+#undef PW_WIRE_REW
 }
 
 }  // namespace

@@ -115,6 +115,24 @@ int check_ref_wire(const pw_ref_wire *w, const void *wire)
     return PW_OK;
 }
 
+// The *_agents wire entry points (0.1.23) write per-agent rings only and read the reward from the trailer plane rew_agents [T,B,N].
+int agents_ring_only(const pw_replay_store *st, const float *rew_agents, const char *who, const char *plain)
+{
+    if (!st->per_agent)
+        return fail(PW_EINVAL, std::string(who) + ": a shared-reward ring (per_agent = 0) is filled by " + plain + " (this entry point writes rew / done [cap,N])");
+    if (!rew_agents || (reinterpret_cast<uintptr_t>(rew_agents) & 3))
+        return fail(PW_EINVAL, std::string(who) + ": rew_agents must be a 4-byte aligned device pointer to the per-agent reward plane [T,B,N]");
+    return PW_OK;
+}
+
+// Every refusal of an *_agents entry point names it (the checks it shares with the plain entry point do not know who asked).
+int named(const char *who, int rc)
+{
+    if (rc == PW_OK) return rc;
+    const std::string msg = pw_last_error();
+    return msg.find(who) == std::string::npos ? fail(rc, std::string(who) + ": " + msg) : rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -334,10 +352,17 @@ int pw_chunk_wire_finalize(const pw_chunk_wire *w, void *wire, const float *obs0
     return PW_OK;
 }
 
-int pw_replay_add_wire(const pw_replay_store *st, int64_t start, const pw_chunk_wire *w, const void *wire, void *stream)
+// pw_replay_add_wire (rew_agents == nullptr, who == nullptr) and pw_replay_add_wire_agents share every check but the ring's kind.
+static int add_wire(const pw_replay_store *st, int64_t start, const pw_chunk_wire *w, const void *wire, const float *rew_agents, const char *who,
+                    void *stream)
 {
     if (!st) return fail(PW_EINVAL, "null argument");
-    if (int rc = plain_ring_only(st, "pw_replay_add_wire")) return rc;
+    if (who) {
+        if (int rc = agents_ring_only(st, rew_agents, who, "pw_replay_add_wire")) return rc;
+        if (int rc = row_ring_only(st, who)) return rc;
+    } else if (int rc = plain_ring_only(st, "pw_replay_add_wire")) {
+        return rc;
+    }
     if (int rc = check_wire(w, wire)) return rc;
     if (st->num_agents != w->N || st->obs_dim != w->D) return fail(PW_EINVAL, "ring / wire shape mismatch");
     if (!ring_fits(st, (int64_t)w->T * w->B, start))
@@ -345,10 +370,31 @@ int pw_replay_add_wire(const pw_replay_store *st, int64_t start, const pw_chunk_
     const int ND = w->N * w->D;
     const bool vec = ND % 4 == 0 && ((reinterpret_cast<uintptr_t>(st->obs) | reinterpret_cast<uintptr_t>(st->next_obs)) & 15) == 0;
     const dim3 grid(grid_blocks((size_t)w->T * w->B * (vec ? ND / 4 : ND), 16384));
-    hipLaunchKernelGGL(vec ? pw_replay_add_wire_kernel<4> : pw_replay_add_wire_kernel<1>, grid, dim3(256), 0, static_cast<hipStream_t>(stream),
-                       *st, start, *w, wire);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (who)
+        hipLaunchKernelGGL(vec ? pw_replay_add_wire_agents_kernel<4> : pw_replay_add_wire_agents_kernel<1>, grid, dim3(256), 0, s, *st, start, *w, wire,
+                           rew_agents);
+    else
+        hipLaunchKernelGGL(vec ? pw_replay_add_wire_kernel<4> : pw_replay_add_wire_kernel<1>, grid, dim3(256), 0, s, *st, start, *w, wire);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
+}
+
+int pw_replay_add_wire(const pw_replay_store *st, int64_t start, const pw_chunk_wire *w, const void *wire, void *stream)
+{
+    return add_wire(st, start, w, wire, nullptr, nullptr, stream);
+}
+
+int pw_replay_add_wire_agents(const pw_replay_store *st, int64_t start, const pw_chunk_wire *w, const void *wire, const float *rew_agents,
+                              void *stream)
+{
+    return named("pw_replay_add_wire_agents", add_wire(st, start, w, wire, rew_agents, "pw_replay_add_wire_agents", stream));
+}
+
+size_t pw_wire_agent_rew_bytes(int32_t T, int32_t B, int32_t N)
+{
+    if (T < 1 || B < 1 || N < 1) return 0;
+    return align_up((size_t)T * B * N * sizeof(float), 256);
 }
 
 int pw_state_wire_layout_scn(int32_t scenario, int32_t T, int32_t B, int32_t N, int32_t L, int32_t num_adversaries,
@@ -404,9 +450,12 @@ int pw_state_wire_finalize(const pw_handle *h, const pw_state_wire *w, void *wir
     return PW_OK;
 }
 
-int pw_replay_add_state_wire(const pw_replay_store *st, int64_t start, const pw_state_wire *w, const void *wire, void *stream)
+static int add_state_wire(const pw_replay_store *st, int64_t start, const pw_state_wire *w, const void *wire, const float *rew_agents,
+                          const char *who, void *stream)
 {
     if (!st) return fail(PW_EINVAL, "null argument");
+    if (who)
+        if (int rc = agents_ring_only(st, rew_agents, who, "pw_replay_add_state_wire")) return rc;
     if (int rc = check_state_wire(w, wire)) return rc;
     if (st->num_agents != w->N || st->obs_dim != w->D) return fail(PW_EINVAL, "ring / wire shape mismatch");
     if (!ring_fits(st, (int64_t)w->T * w->B, start))
@@ -414,28 +463,51 @@ int pw_replay_add_state_wire(const pw_replay_store *st, int64_t start, const pw_
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t agents = (size_t)w->T * w->B * w->N;
     if (st->state_rows) {  // STATE ring: copy what the block carries; pw_replay_gather rebuilds the rows
-        if (st->per_agent)
+        if (!who && st->per_agent)
             return fail(PW_EINVAL, "pw_replay_add_state_wire: a per-agent STATE ring is filled by the pw_policy_rollout sink only (the wire blocks carry the shared reward)");
-        if (int rc = state_ring_ok(st, "pw_replay_add_state_wire")) return rc;
+        if (int rc = state_ring_ok(st, who ? who : "pw_replay_add_state_wire")) return rc;
         if (st->scenario != w->scenario || st->num_landmarks != w->L || st->num_adversaries != w->num_adversaries)
             return fail(PW_EINVAL, "STATE ring / wire scenario mismatch");
-        hipLaunchKernelGGL(pw_replay_add_state_wire_to_state_ring_kernel, dim3(grid_blocks(agents, 16384)), dim3(256), 0, s, *st, start, *w, wire);
+        const dim3 grid(grid_blocks(agents, 16384));
+        if (who)
+            hipLaunchKernelGGL(pw_replay_add_state_wire_to_state_ring_agents_kernel, grid, dim3(256), 0, s, *st, start, *w, wire, rew_agents);
+        else
+            hipLaunchKernelGGL(pw_replay_add_state_wire_to_state_ring_kernel, grid, dim3(256), 0, s, *st, start, *w, wire);
         PW_HIP_CHECK(hipGetLastError());
         return PW_OK;
     }
-    if (int rc = plain_ring_only(st, "pw_replay_add_state_wire")) return rc;
+    if (int rc = who ? row_ring_only(st, who) : plain_ring_only(st, "pw_replay_add_state_wire")) return rc;
     const uintptr_t al = reinterpret_cast<uintptr_t>(st->obs) | reinterpret_cast<uintptr_t>(st->next_obs);
     if (al & 7) return fail(PW_EINVAL, "ring observation planes must be 8-byte aligned");
     if (w->scenario != PW_SIMPLE_SPREAD) {  // simple_tag: 8-byte units (other agents' states feed every row)
-        hipLaunchKernelGGL(pw_replay_add_state_wire_units_kernel, dim3(grid_blocks(agents * (w->D / 2), 16384)), dim3(256), 0, s, *st, start, *w, wire);
+        const dim3 grid(grid_blocks(agents * (w->D / 2), 16384));
+        if (who)
+            hipLaunchKernelGGL(pw_replay_add_state_wire_units_agents_kernel, grid, dim3(256), 0, s, *st, start, *w, wire, rew_agents);
+        else
+            hipLaunchKernelGGL(pw_replay_add_state_wire_units_kernel, grid, dim3(256), 0, s, *st, start, *w, wire);
         PW_HIP_CHECK(hipGetLastError());
         return PW_OK;
     }
     const bool v4 = w->L % 2 == 0 && (al & 15) == 0;
     const dim3 grid(grid_blocks(agents * (v4 ? w->D / 4 : w->D / 2), 16384));
-    hipLaunchKernelGGL(v4 ? pw_replay_add_state_wire_kernel<4> : pw_replay_add_state_wire_kernel<2>, grid, dim3(256), 0, s, *st, start, *w, wire);
+    if (who)
+        hipLaunchKernelGGL(v4 ? pw_replay_add_state_wire_agents_kernel<4> : pw_replay_add_state_wire_agents_kernel<2>, grid, dim3(256), 0, s, *st, start,
+                           *w, wire, rew_agents);
+    else
+        hipLaunchKernelGGL(v4 ? pw_replay_add_state_wire_kernel<4> : pw_replay_add_state_wire_kernel<2>, grid, dim3(256), 0, s, *st, start, *w, wire);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
+}
+
+int pw_replay_add_state_wire(const pw_replay_store *st, int64_t start, const pw_state_wire *w, const void *wire, void *stream)
+{
+    return add_state_wire(st, start, w, wire, nullptr, nullptr, stream);
+}
+
+int pw_replay_add_state_wire_agents(const pw_replay_store *st, int64_t start, const pw_state_wire *w, const void *wire, const float *rew_agents,
+                                    void *stream)
+{
+    return named("pw_replay_add_state_wire_agents", add_state_wire(st, start, w, wire, rew_agents, "pw_replay_add_state_wire_agents", stream));
 }
 
 int pw_ref_wire_layout(int32_t T, int32_t B, int32_t max_episode_len, pw_ref_wire *out)
@@ -464,21 +536,39 @@ int pw_ref_wire_finalize(const pw_ref_wire *w, void *wire, const float *obs0, co
     return PW_OK;
 }
 
-int pw_replay_add_ref_wire(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire, void *stream)
+static int add_ref_wire(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire, const float *rew_agents, const char *who,
+                        void *stream)
 {
     if (!st) return fail(PW_EINVAL, "null argument");
+    if (who)
+        if (int rc = agents_ring_only(st, rew_agents, who, "pw_replay_add_ref_wire")) return rc;
     if (int rc = check_ref_wire(w, wire)) return rc;
-    if (st->per_agent)
+    if (!who && st->per_agent)
         return fail(PW_EINVAL, "pw_replay_add_ref_wire: a per-agent ring is not served (the compact-row blocks carry the shared reward only)");
     if (st->state_rows || st->act_heads != 2 || st->head_width[1] != PW_DIM_C || (st->head_width[0] != 0 && st->head_width[0] != 5))
-        return fail(PW_EINVAL, "pw_replay_add_ref_wire: the ring must be the two-head ring of simple_reference (act_heads = 2, head widths 5 | dim_c)");
+        return fail(PW_EINVAL, std::string(who ? who : "pw_replay_add_ref_wire") + ": the ring must be the two-head ring of simple_reference (act_heads = 2, head widths 5 | dim_c)");
     if (st->num_agents != kRefN || st->obs_dim != kRefD) return fail(PW_EINVAL, "ring / wire shape mismatch (simple_reference: N = 2, D = 21)");
     if (!ring_fits(st, (int64_t)w->T * w->B, start))
         return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");
-    const size_t total = (size_t)w->T * w->B * kRefN * kRefD;
-    hipLaunchKernelGGL(pw_replay_add_ref_wire_kernel, dim3(grid_blocks(total, 16384)), dim3(256), 0, static_cast<hipStream_t>(stream), *st, start, *w, wire);
+    const dim3 grid(grid_blocks((size_t)w->T * w->B * kRefN * kRefD, 16384));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (who)
+        hipLaunchKernelGGL(pw_replay_add_ref_wire_agents_kernel, grid, dim3(256), 0, s, *st, start, *w, wire, rew_agents);
+    else
+        hipLaunchKernelGGL(pw_replay_add_ref_wire_kernel, grid, dim3(256), 0, s, *st, start, *w, wire);
     PW_HIP_CHECK(hipGetLastError());
     return PW_OK;
+}
+
+int pw_replay_add_ref_wire(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire, void *stream)
+{
+    return add_ref_wire(st, start, w, wire, nullptr, nullptr, stream);
+}
+
+int pw_replay_add_ref_wire_agents(const pw_replay_store *st, int64_t start, const pw_ref_wire *w, const void *wire, const float *rew_agents,
+                                  void *stream)
+{
+    return named("pw_replay_add_ref_wire_agents", add_ref_wire(st, start, w, wire, rew_agents, "pw_replay_add_ref_wire_agents", stream));
 }
 
 }  // extern "C"

@@ -62,7 +62,8 @@ def broadcast_actor(actor, src=0, group=None, fused=None):
 
 
 class SampledTransitionGather(object):
-    """Call once per rollout chunk: ``gather(chunk_outputs, chunk_actions)``.
+    """Call once per rollout chunk: ``gather(chunk_outputs, chunk_actions)``.  Shared-reward only: the packed rows carry ``rew_shared``
+    and the ring is the plain ring; the per-agent tuple of the BiCNet baseline travels with ``FullTransitionGather(per_agent=True)``.
 
     chunk_outputs: dict of [T,B,...] tensors as ``BatchedParticleEnv.rollout`` fills them
     (needs obs, rew_shared, terminal and, with auto-reset, final_obs); chunk_actions [T,B,N] int32.
@@ -246,14 +247,15 @@ class _Wire(object):
     only their first columns travel), the axes ``side['act']`` has behind [T, B, N] (``act_tail``) and its typed ``fields``: name = the
     layout's offset member -> (shape, dtype), a letter being the gather's attribute of that name and F the layout's F (at least 0).
     ``layout`` fills a ``Struct``, ``finalize`` condenses a chunk into its block, ``ring`` gives the ReplayBuffer keyword arguments of the
-    learner rank's ring."""
+    learner rank's ring.  ``append_agents`` is ``append`` for a per-agent ring: it also takes the address of the per-agent reward plane
+    that follows the block (``pw_wire_agent_rew_bytes``)."""
     begin, keeps_obs, act_tail = None, True, ()
     ring = staticmethod(lambda g: {})
 
 
 class _RowsWire(_Wire):
     """``pw_chunk_wire``: the rows travel as the rollout wrote them (any scenario with one action head)."""
-    Struct, append, keeps_obs = _lib.PwChunkWire, 'pw_replay_add_wire', False
+    Struct, append, append_agents, keeps_obs = _lib.PwChunkWire, 'pw_replay_add_wire', 'pw_replay_add_wire_agents', False
     fields = dict(obs0=(('B', 'N', 'D'), _F32), obs=(('T', 'B', 'N', 'D'), _F32), final_rows=(('F', 'B', 'N', 'D'), _F32),
                   rew_shared=(('T', 'B'), _F32), act=(('T', 'B', 'N'), _U8), fin_slot=(('T', 'B'), _U8))
 
@@ -270,7 +272,7 @@ class _RowsWire(_Wire):
 
 class _StateWire(_Wire):
     """``pw_state_wire``: {vel, pos} per agent and step, the landmarks once per episode; the root rebuilds the rows."""
-    Struct, append, begin = _lib.PwStateWire, 'pw_replay_add_state_wire', 'pw_state_wire_begin'
+    Struct, append, append_agents, begin = _lib.PwStateWire, 'pw_replay_add_state_wire', 'pw_replay_add_state_wire_agents', 'pw_state_wire_begin'
     fields = dict(state0=(('B', 'N', 4), _F32), state=(('T', 'B', 'N', 4), _F32), final_state=(('F', 'B', 'N', 4), _F32),
                   lm=(('F+1', 'B', 'L', 2), _F32), ep0=(('B',), _I32), rew_shared=(('T', 'B'), _F32), act=(('T', 'B', 'N'), _U8),
                   epi=(('T', 'B'), _U8))
@@ -291,7 +293,7 @@ class _StateWire(_Wire):
 
 class _RefWire(_Wire):
     """``pw_ref_wire``: simple_reference's compact rows (the first 8 numbers, goal bytes per episode, both action heads as bytes)."""
-    Struct, append, act_tail = _lib.PwRefWire, 'pw_replay_add_ref_wire', (2,)
+    Struct, append, append_agents, act_tail = _lib.PwRefWire, 'pw_replay_add_ref_wire', 'pw_replay_add_ref_wire_agents', (2,)
     fields = dict(head0=(('B', 'N', 8), _F32), head=(('T', 'B', 'N', 8), _F32), final_head=(('F', 'B', 'N', 8), _F32),
                   goal=(('F+1', 'B', 'N'), _U8), comm0=(('B', 'N'), _U8), rew_shared=(('T', 'B'), _F32), act=(('T', 'B', 'N', 2), _U8),
                   epi=(('T', 'B'), _U8))
@@ -344,12 +346,19 @@ class FullTransitionGather(object):
     link at 2.8e8 env-steps/s per rank instead of 115 (of ~153).  In this mode ``outputs()`` also snapshots the chunk's
     start (state, landmarks, episode numbers) into the block: call it right before the chunk's rollout launch.
     ``wire='rows'`` keeps the row block (any scenario).
+
+    ``per_agent=True`` (the BiCNet baseline's tuple, experiments/run_BIC.py:46,50): every block is followed by a TRAILER PLANE, the
+    per-agent rewards ``rew`` [T, B, N] f32 at offset ``lay.total_bytes`` (``pw_wire_agent_rew_bytes``; the block structs keep their
+    bytes).  ``outputs()`` returns ``rew`` as a view into the trailer, so the rollout writes it in place as it writes ``rew_shared`` --
+    no launch and no copy more on the sender; the root appends with the format's ``*_agents`` entry point into a per-agent ring (row
+    ring, STATE ring with ``ring='state'``, simple_reference's two-head ring; ``rew`` / ``done`` [cap, N]).  4 N bytes more per env-step:
+    21 N + 5 for the state blocks (C2, T = 100: 114 + 24 = 138 B per env-step).
     """
 
     SLOTS = 3
 
     def __init__(self, env, T, rank, world, device, memory=None, group=None, capacity=int(1e6), wire='auto', overlap_ingest=True,
-                 ring='rows', transport='auto'):
+                 ring='rows', transport='auto', per_agent=False):
         self.rank, self.world, self.device, self.group = rank, world, torch.device(device), group
         if transport not in ('auto', 'direct', 'host'):
             raise ValueError("transport must be 'auto', 'direct' or 'host'")
@@ -387,8 +396,12 @@ class FullTransitionGather(object):
         if ring == 'state' and not self.state_wire:
             raise ValueError("ring='state' needs state-only wire blocks (a STATE ring is filled from them only)")
         self.ring_kind = ring
+        self.per_agent = bool(per_agent)
+        if memory is not None and bool(getattr(memory, 'per_agent', False)) != self.per_agent:
+            raise ValueError('FullTransitionGather(per_agent=%r): the ring passed as memory= is a %s ring' %
+                             (self.per_agent, 'per-agent' if getattr(memory, 'per_agent', False) else 'shared-reward'))
         self.lay = self._layout(self.format.Struct)
-        nbytes = self.lay.total_bytes
+        nbytes = self.block_bytes       # slots, receive buffers and pinned host buffers: the block and, per_agent, its trailer plane
         dev = self.device
         # THREE slots: chunk k's blocks travel (and, at the root, are appended) while chunk k + 1 rolls out into the next slot and
         # chunk k + 2 may already start in the third -- the root's ring append runs on its own stream beside the NEXT rollout
@@ -409,7 +422,7 @@ class FullTransitionGather(object):
         self.side = dict(final_obs=torch.empty(self.T, B, N, D, dtype=torch.float32, device=dev) if self.lay.F else None,
                          terminal=torch.zeros(self.T, B, dtype=torch.bool, device=dev),
                          act=torch.zeros((self.T, B, N) + self.format.act_tail, dtype=torch.int32, device=dev),
-                         rew=torch.empty(self.T, B, N, dtype=torch.float32, device=dev),
+                         rew=None if self.per_agent else torch.empty(self.T, B, N, dtype=torch.float32, device=dev),
                          done=torch.zeros(self.T, B, N, dtype=torch.bool, device=dev))
         if self.format.keeps_obs:   # the rows stay on the sender: only their first four (eight) columns travel
             self.side['obs'] = torch.empty(self.T, B, N, D, dtype=torch.float32, device=dev)
@@ -453,16 +466,33 @@ class FullTransitionGather(object):
         itemsize = torch.empty((), dtype=dtype).element_size()
         return block[off:off + n * itemsize].view(dtype).view(*shape)
 
+    @property
+    def trailer_bytes(self):
+        """Bytes of the per-agent reward plane behind every block (0 for a shared-reward gather)."""
+        if not getattr(self, 'per_agent', False):
+            return 0
+        return int(_lib.load().pw_wire_agent_rew_bytes(self.T, self.B, self.N))
+
+    @property
+    def block_bytes(self):
+        """What one slot holds and one transfer moves: the wire block and its trailer."""
+        return int(self.lay.total_bytes) + self.trailer_bytes
+
     def views(self, block):
-        """Typed views of one wire block (a uint8 tensor of ``lay.total_bytes``)."""
+        """Typed views of one wire block (a uint8 tensor of ``block_bytes``); a per-agent gather adds ``rew_agents`` [T, B, N], the
+        trailer plane behind the block."""
         lay, F = self.lay, max(self.lay.F, 0)
         dim = lambda x: x if isinstance(x, int) else F if x == 'F' else F + 1 if x == 'F+1' else getattr(self, x)  # noqa: E731
-        return {name: self._view(block, getattr(lay, name), tuple(dim(x) for x in shape), dtype)
-                for name, (shape, dtype) in self.format.fields.items()}
+        v = {name: self._view(block, getattr(lay, name), tuple(dim(x) for x in shape), dtype)
+             for name, (shape, dtype) in self.format.fields.items()}
+        if getattr(self, 'per_agent', False):
+            v['rew_agents'] = self._view(block, int(lay.total_bytes), (self.T, self.B, self.N), _F32)
+        return v
 
     def outputs(self, slot=None):
         """The [T, ...] output dict for this chunk's rollout launch (``FusedActor.rollout(env, T, out)`` /
-        ``BatchedParticleEnv.rollout``): obs and rew_shared are views INTO the wire block."""
+        ``BatchedParticleEnv.rollout``): obs and rew_shared are views INTO the wire block, and so is rew [T, B, N] of a per-agent gather
+        (the trailer plane)."""
         slot = self.exchanges % self.SLOTS if slot is None else slot
         if self._slot_free[slot] is not None:       # the side stream's appends of this slot's previous blocks have been issued:
             torch.cuda.current_stream(self.device).wait_event(self._slot_free[slot])   # nothing overwrites them before they ran
@@ -471,14 +501,15 @@ class FullTransitionGather(object):
         if self.format.begin:
             self._begin(self.wire[slot])
         out = dict(obs=self.side['obs'] if self.format.keeps_obs else v['obs'], rew_shared=v['rew_shared'],
-                   terminal=self.side['terminal'], act=self.side['act'], rew=self.side['rew'], done=self.side['done'])
+                   terminal=self.side['terminal'], act=self.side['act'], rew=v['rew_agents'] if getattr(self, 'per_agent', False) else self.side['rew'],
+                   done=self.side['done'])
         if self.side['final_obs'] is not None:
             out['final_obs'] = self.side['final_obs']
         return out
 
     @property
     def bytes_per_env_step(self):
-        return self.lay.total_bytes / float(self.T * self.B)
+        return self.block_bytes / float(self.T * self.B)
 
     @classmethod
     def root_receive_bytes(cls, world, block_bytes):
@@ -488,7 +519,8 @@ class FullTransitionGather(object):
     # -- overridable pieces (the CPU gloo test substitutes torch stand-ins for the two HIP launches)
     def _make_memory(self):
         from .replay_buffer import ReplayBuffer
-        return ReplayBuffer(self.capacity, self.N, self.D, device=self.device, device_index=True, **self.format.ring(self))
+        kw = dict(self.format.ring(self), per_agent=True) if getattr(self, 'per_agent', False) else self.format.ring(self)
+        return ReplayBuffer(self.capacity, self.N, self.D, device=self.device, device_index=True, **kw)
 
     def _begin(self, block):
         """State-only wire: the chunk's start (state, landmarks, episode numbers) from the env's bound state planes."""
@@ -500,7 +532,12 @@ class FullTransitionGather(object):
     def _ingest(self, block):
         m, n = self.memory, self.T * self.B
         start = m.claim(n, self.N, self.D, self.device)
-        check(getattr(_lib.load(), self.format.append)(C.byref(m._store), start, C.byref(self.lay), ptr(block), _lib.stream(self.device)))
+        if getattr(self, 'per_agent', False):   # the trailer plane's address: the per-agent rewards the sender's rollout wrote behind the block
+            trailer = C.c_void_p(block.data_ptr() + int(self.lay.total_bytes))
+            check(getattr(_lib.load(), self.format.append_agents)(C.byref(m._store), start, C.byref(self.lay), ptr(block), trailer,
+                                                                  _lib.stream(self.device)))
+        else:
+            check(getattr(_lib.load(), self.format.append)(C.byref(m._store), start, C.byref(self.lay), ptr(block), _lib.stream(self.device)))
         m._advance(n)
 
     # -- the exchange

@@ -122,8 +122,10 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     one-launch rollout serves (the full observation, L > N, landmark contact on simple_spread, ``policy_form=5``) take ``ring='rows'``:
     their rollout refuses a STATE ring.  ``per_agent_transition=True`` (the BiCNet baseline, ``experiments/run_BIC.py:46,50``): the ring
     holds per-agent ``rew`` / ``done`` planes ([cap, N]) and every chunk is one launch, as with a shared ring (the rollout's sink stores
-    every agent's own reward).  The ring built here is the single-rank row ring -- with ``gather`` or ``ring='state'`` it raises; a
-    per-agent STATE ring (``ReplayBuffer(per_agent=True, state_ring=...)``) comes in through ``memory=``.  ``graph_update=True``: the ring this
+    every agent's own reward).  The ring built here is the single-rank row ring -- with ``ring='state'`` it raises; a per-agent STATE ring
+    (``ReplayBuffer(per_agent=True, state_ring=...)``) comes in through ``memory=`` or, on several ranks, with the gather: ``gather`` must
+    then be a per-agent gather (``dist.FullTransitionGather(per_agent=True)``: per-agent wire blocks; its ``memory`` is the learner's ring,
+    row or STATE as the gather was built), any other gather raises -- as a per-agent gather does without ``per_agent_transition=True``.  ``graph_update=True``: the ring this
     function creates draws its batches from device cells (``ReplayBuffer(device_index='counter')``) and the learner's ``optimize`` is
     replaced, after construction, by a ``graph.GraphedUpdate`` (a learner that has installed one itself keeps it): a few eager updates,
     then one graph launch per update; the learner must be in the configuration that serves (``accelerate_trainer``'s four switches), or
@@ -134,9 +136,13 @@ def train_batched(env, actor, critic, Trainer, scenario_name, action_type='Discr
     cfg = _default_arglist if arglist is None else arglist
     if action_type not in ('Discrete', 'MultiDiscrete'):
         raise ValueError('action_type must be Discrete or MultiDiscrete, got %r' % (action_type,))
-    if per_agent_transition and gather is not None:
+    gather_per_agent = gather is not None and bool(getattr(gather, 'per_agent', False))
+    if per_agent_transition and gather is not None and not gather_per_agent:
         raise ValueError('per_agent_transition=True with gather=: the multi-rank gather carries the shared reward only (per-agent wire '
                          'blocks are not served)')
+    if gather_per_agent and not per_agent_transition:
+        raise ValueError('gather= is a per-agent gather (FullTransitionGather(per_agent=True): its ring holds rew / done [cap, N]) but '
+                         'per_agent_transition is not set: the learner would read the BiCNet tuple as a shared-reward batch')
     if per_agent_transition and ring == 'state':
         raise ValueError("per_agent_transition=True with ring='state': a STATE ring is a shared-reward ring (per-agent rewards are not served)")
     B, N = env.num_envs, env.n
