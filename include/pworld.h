@@ -303,7 +303,9 @@ int pw_replay_add_tail(const pw_replay_store *st, int64_t start, const int64_t *
  * fill its [cap,N] planes -- the bookkeeping stays on rew_shared); act [T,B,N] int32 ([T,B,N,2] for a two-head ring, st->act_heads = 2: the MultiDiscrete chunks
  * of pw_policy_rollout on simple_reference).  episode_return / finished_sum / finished_count / scratch
  * (all or none): the chunk's episode-return bookkeeping, as T pw_episode_stats calls up to float64 summation
- * order (fixed, so reproducible); scratch = pw_replay_add_rollout_scratch_bytes(B) device bytes, zeroed once. */
+ * order (fixed, so reproducible); scratch = pw_replay_add_rollout_scratch_bytes(B) device bytes, zeroed once.
+ * Like pw_replay_add and pw_replay_gather it refuses (PW_EINVAL) st->act_heads outside [0, 2] and a two-head ring whose
+ * head_width[0] < 0 or head_width[1] < 1: it used to take act_heads = 3 and store one index per agent where the gather reads two. */
 int pw_replay_add_rollout(const pw_replay_store *st, int64_t start, int32_t B, int32_t T, const float *obs0,
                           const pw_step_io *io, const int32_t *act, float *episode_return, double *finished_sum,
                           int64_t *finished_count, void *scratch, void *stream);

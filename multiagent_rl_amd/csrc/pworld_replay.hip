@@ -194,6 +194,9 @@ int pw_replay_add_rollout(const pw_replay_store *st, int64_t start, int32_t B, i
     if (B < 1 || T < 1 || !ring_fits(st, (int64_t)B * T, start))
         return fail(PW_EINVAL, "bad ring arguments (the chunk must fit the ring)");
     if (st->obs_dim < 5) return fail(PW_EINVAL, "obs_dim must be >= 5");
+    // as pw_replay_add / pw_replay_gather: the kernel stores one index per agent unless act_heads == 2, the gather reads two for any act_heads > 1
+    if (st->act_heads < 0 || st->act_heads > 2 || (st->act_heads == 2 && (st->head_width[0] < 0 || st->head_width[1] < 1)))
+        return fail(PW_EINVAL, "bad act_heads / head_width");
     if (st->act_heads == 2 && st->num_agents * st->obs_dim < 2 * st->num_agents) return fail(PW_EINVAL, "two-head ring: rows too short");
     if (episode_return && (!finished_sum || !finished_count || !scratch))
         return fail(PW_EINVAL, "bookkeeping needs episode_return, finished_sum, finished_count and scratch");
