@@ -35,6 +35,11 @@ the learner's own ``fused_wgrad`` switch, or ``accelerate_trainer(.., wgrad=True
 ``--fused-heads`` runs the ReLU on the actor's BiLSTM output and every output layer of the learner's networks with gradient on the HIP
 kernels (``multiagent_rl_amd.heads``: the learner's own ``fused_heads`` switch, or ``accelerate_trainer(.., heads=True)`` with
 ``--reference``; needs ``--fused-front``).
+``--ledger device`` takes the per-episode history from the HIP episode log (``train.EpisodeLog``: one launch per chunk; several ranks are
+merged in time order) instead of the torch pipeline of ``ChunkLedger`` (``--ledger host``, the default).  ``--test-only`` is the
+experiment's test phase (``run_test``, run.py:106-200) on the batched engine: ``train.evaluate_batched`` loads the
+``<scenario>_fin_<cnt>`` models a training run saved (``Models/`` under the working directory, the default ``--out-dir``), plays ``--episodes`` episodes without updating anything and
+writes ``test_history_<scenario>_<cnt>.pkl`` to ``--out-dir``; it needs none of the learner switches.
 With several ranks (torchrun) every rank rolls out its shard of the env batch (``env_id_base = rank * envs``) and the
 transitions of all ranks reach rank 0's ring through the RCCL full gather; rank 0 learns and broadcasts the actor.
 """
@@ -114,6 +119,12 @@ def main(argv=None):
                          "backward, on the HIP kernels (madr_learner's fused_heads switch; with --reference: "
                          'accelerate_trainer(.., heads=True)); needs --fused-front; off by default: the sums run in another order than '
                          'the stock GEMMs')
+    ap.add_argument('--ledger', default='host', choices=['host', 'device'],
+                    help='who makes the per-episode history: host = ChunkLedger (a torch pipeline per chunk), device = EpisodeLog (one HIP '
+                         'launch per chunk, float64 sums in a fixed order; several ranks merge in time order)')
+    ap.add_argument('--test-only', action='store_true',
+                    help="the test phase: load the <scenario>_fin_<cnt> models a training run saved (Models/), play --episodes episodes in launches of "
+                         'max_episode_len steps without any update and write test_history_<scenario>_<cnt>.pkl there')
     args = ap.parse_args(argv)
     if args.fused_heads and not args.fused_front:
         ap.error('--fused-heads needs --fused-front: the fused output layers are the last lines of the swapped forwards')
@@ -138,7 +149,7 @@ def main(argv=None):
     import torch.distributed as dist
     from multiagent_rl_amd import arglist, make_batched_env
     from multiagent_rl_amd.policy import ActorNetwork
-    from multiagent_rl_amd.train import dims_from_env, seed_everything, train_batched
+    from multiagent_rl_amd.train import dims_from_env, evaluate_batched, seed_everything, train_batched
     if args.reference and model:
         from rls.agent.multiagent.model_ddpg_gumbel_fix import Trainer
         from rls.model.ac_network_model_multi_gumbel import ActorNetwork, CriticNetwork
@@ -238,6 +249,13 @@ def main(argv=None):
             actor = ActorNetwork(input_dim=dim_obs, out_dim=dim_action)       # main.py:60-61
             n_act = sum(dim_action) if isinstance(dim_action, list) else dim_action
             critic = CriticNetwork(input_dim=dim_obs + n_act, out_dim=1)
+            if args.test_only:
+                # load_models reads <scenario>_fin_<cnt>_actor.pt / _critic.pt where save_models wrote them (Models/ under the working
+                # directory, the reference's place): model_prefix='' -- not arglist.appx -- names what the training run above saved
+                hist = evaluate_batched(env, actor, critic, Trainer, scenario_name, action_type, cnt=cnt, out_dir=args.out_dir,
+                                        model_prefix='', rank=rank, world=world, log=print if rank == 0 else (lambda *a: None))
+                results.append((scenario_name, cnt, hist['stats']))
+                continue
             gather = None
             if world > 1:
                 from multiagent_rl_amd.dist import FullTransitionGather, broadcast_actor
@@ -253,7 +271,7 @@ def main(argv=None):
                                  chunk=args.chunk, max_updates_per_chunk=args.max_updates_per_chunk, gather=gather,
                                  ring='state' if (gather is None and state_ok and not bicnet) else 'rows', memory=memory,
                                  rank=rank, world=world, log=print if rank == 0 else (lambda *a: None), per_agent_transition=bicnet,
-                                 graph_update=args.graph_update)
+                                 graph_update=args.graph_update, ledger=args.ledger)
             results.append((scenario_name, cnt, hist['stats']))
             if rank == 0:
                 s = hist['stats']

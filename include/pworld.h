@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define PW_VERSION 123 /* 0.1.23: + pw_replay_add_wire_agents / pw_replay_add_state_wire_agents / pw_replay_add_ref_wire_agents and pw_wire_agent_rew_bytes (per-agent wire blocks: the per-agent reward plane rew [T,B,N] f32 travels as a trailer behind a wire block of any format, at offset total_bytes, and the learner rank's append writes a per-agent ring -- row ring, STATE ring, simple_reference's two-head ring -- in one launch; the BiCNet baseline trains on several ranks).  No struct, layout or entry point changed: the plain wire entry points keep refusing a per-agent ring.  0.1.22: the ring of pw_rollout_sink may be a per-agent ring (pw_replay_store.per_agent: rew / done [cap,N]) in every form of pw_policy_rollout -- the row ring and the STATE ring of the simple_spread / simple_tag forms, the row ring of the generic form, the two-head ring of simple_reference: every live lane stores its own reward, the value the launch writes to rew[t, env, a], and done = 0; a STATE ring may be per-agent (single head; pw_replay_gather / pw_replay_sample then return out_rew / out_done [b,N]).  The tail / packed / wire entry points keep refusing a per-agent ring.  No entry point changed.  0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
+#define PW_VERSION 124 /* 0.1.24: + pw_episode_log_absorb / pw_episode_log_scratch_bytes and pw_episode_log (the per-episode, per-agent returns of a chunk as a log in device memory: one entry per finished episode in (end step, env) order, float64 sums in the order of the reference's loop, no floating-point atomic; translation unit pworld_episode_log.hip, kernels csrc/pw_kernels_episode_log.hpp).  No entry point changed.  0.1.23: + pw_replay_add_wire_agents / pw_replay_add_state_wire_agents / pw_replay_add_ref_wire_agents and pw_wire_agent_rew_bytes (per-agent wire blocks: the per-agent reward plane rew [T,B,N] f32 travels as a trailer behind a wire block of any format, at offset total_bytes, and the learner rank's append writes a per-agent ring -- row ring, STATE ring, simple_reference's two-head ring -- in one launch; the BiCNet baseline trains on several ranks).  No struct, layout or entry point changed: the plain wire entry points keep refusing a per-agent ring.  0.1.22: the ring of pw_rollout_sink may be a per-agent ring (pw_replay_store.per_agent: rew / done [cap,N]) in every form of pw_policy_rollout -- the row ring and the STATE ring of the simple_spread / simple_tag forms, the row ring of the generic form, the two-head ring of simple_reference: every live lane stores its own reward, the value the launch writes to rew[t, env, a], and done = 0; a STATE ring may be per-agent (single head; pw_replay_gather / pw_replay_sample then return out_rew / out_done [b,N]).  The tail / packed / wire entry points keep refusing a per-agent ring.  No entry point changed.  0.1.21: + pw_head_train_forward / pw_head_train_backward / pw_head_train_scratch_bytes (the output layers of the learner's networks with gradient: the ReLU on the actor's BiLSTM output and up to three heads as one launch forward and two backward; a head that received no gradient is passed as NULL and costs nothing; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_head.hip, kernels csrc/pw_kernels_head.hpp).  No entry point changed.  0.1.20: + pw_lstm_train_wgrad / pw_lstm_train_wgrad_scratch_bytes (the two recurrent-weight gradients dW_hh of the learner's LSTMs, dG^T against the output shifted by one step, read in place: two launches for both directions, summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_lstm_wgrad.hip, kernels csrc/pw_kernels_lstm_wgrad.hpp).  No entry point changed.  0.1.19: the forward ReLU of every network kernel (dense front, attention pooling, the no-gradient critics, every actor form, the one-launch policy rollouts) carries a NaN instead of replacing it by 0, as torch.relu does; every finite input gives the bits it gave before.  No entry point changed.  0.1.18: + pw_front_train_forward / pw_front_train_backward / pw_front_train_scratch_bytes (the dense front of the learner's networks with gradient: dense1, ReLU and the LSTM's input projection as one launch forward and two backward; the parameter gradients are summed across workgroups in a fixed order through a caller-provided scratch, without floating-point atomics; translation unit pworld_front.hip).  No entry point changed.  0.1.17: + pw_gumbel_st_forward / pw_gumbel_st_backward (the learner's hard and soft Gumbel-softmax sample with gradient, one launch each; the noise is the actor heads' Philox draw keyed (seed; step + a device cell, row)).  No entry point changed.  0.1.16: + pw_replay_sample (the batch draw on the device, with or without the gather, numbered and bounded by two device cells), pw_replay_draw_host, pw_adam_step_dev (Adam with the step count in device memory) and pw_adam_bias_scalars: what a captured update needs.  No entry point changed.  0.1.15: + pw_critic_forward_model (the model-learning variant's critic as one launch: no ReLU on the context, Q and the reward prediction from two heads summed in one order, the TD target from the launch's own Q).  0.1.14: + pw_attention_pool_forward / pw_attention_pool_backward (the attention block of the learner's critic with gradient: scores against the last step, softmax over the agent axis, weighted sum, ReLU; one launch each).  0.1.13: the statistics scratch of pw_policy_rollout (pw_rollout_sink.scratch) serves ANY sequence of launch forms on handles of equal num_envs: the ticket word no longer moves with the launch's grid (a launch with fewer workgroups than its predecessor on the same scratch -- pw_dispatch.policy_form changed, pw_actor_set_bf16x3, two handles behind one actor -- dropped its finished episodes).  No entry point changed.  0.1.12: + pw_lstm_train_forward / pw_lstm_train_backward (the recurrent part of a one-layer LSTM with gradient, one launch each, for the learner's passes).  0.1.11: + pw_critic_forward_steps (the BiCNet baseline's per-step critic and per-agent TD target as one launch); pw_replay_add_rollout serves per-agent rings (rew / done planes [cap,N] from io->rew / io->done).  0.1.10: pw_actor_fused and pw_actor_front take observation rows of up to 104 numbers (in_dim in [1, 104]; was 64): pw_actor_fused_kernel / pw_actor_front_kernel at S1C = 9 .. 13.  0.1.9: + the generic one-launch policy rollout (pw_dispatch.policy_form = 5, and automatically for the simple_spread / simple_tag handles the specialised forms refuse: full observation, L > N, landmark contact, force_generic) and pw_policy_generic_envs_per_workgroup.  0.1.8: + pw_adam_step / pw_soft_update (global-norm clip, Adam and the Polyak update of the target network as one launch).  0.1.7: + pw_critic_forward (the learner's critic forward and TD target as one launch).  0.1.6: + STATE rings (pw_replay_store.state_rows: the ring keeps {vel, pos} + the episode's landmarks, pw_replay_gather rebuilds the rows);
                           state-only wire blocks for simple_tag (pw_state_wire_layout_scn), compact-row wire blocks for simple_reference (pw_ref_wire_*); pw_replay_store and pw_state_wire grew (appended fields, zero = before);
                           PWORLD_POLICY_V2 no longer read.  0.1.5: + pw_state_wire_* / pw_replay_add_state_wire (state-only wire blocks); PW_ACTOR_BF16X3 environment switch removed; 0.1.4: + pw_set_actor_precision / pw_actor_set_bf16x3 (opt-in bf16x3 input projection); pw_actor_front_pack's
                           image grew a third section.  0.1.3: + pw_dispatch (kernel selection frozen in the handle; no environment reads at launch)
@@ -808,6 +808,41 @@ int pw_head_train_backward(const float *const *dOut, const float *X, int64_t row
 /* The bytes of scratch one pw_head_train_backward of this shape needs, whichever of its heads have a dOut (0 for a shape that is not
  * served). */
 size_t pw_head_train_scratch_bytes(int64_t rows, int32_t heads, const int32_t *n);
+
+/* ---- the episode log: per-episode, per-agent returns of a chunk (translation unit pworld_episode_log.hip) ------------------------------
+ * One launch sequence consumes the planes of one chunk, whoever produced them (pw_rollout, pw_policy_rollout, a step loop, the side
+ * buffers of a gather): rew [T,B,N] float32 and terminal [T,B] uint8, and appends one entry per finished episode to a log the caller
+ * owns (experiments/run.py:55-65, for B worlds stepped side by side).  All arrays, the two cells and the scratch are device memory.
+ *   Arithmetic: float64 accumulators, float32 rewards widened.  Per step, for env e: by_agent[a] += rew[t,e,a] for every agent, and
+ *   total += rew[t,e,0], then ... + rew[t,e,N-1], agents ascending -- total is a sum of its own, not the sum of the shares.  Where
+ *   terminal[t,e] is set the entry is stored and the env's carry becomes +0.0 by assignment: a NaN or Inf reward poisons the sums of
+ *   its own episode and nothing else.  No floating-point atomic: the results are a function of the inputs alone, bit for bit.
+ *   Order: entry k of a launch goes to slot *length + k, k = the number of set flags before (t, e) in row-major order of terminal
+ *   (by end step, then by env).
+ *   Capacity: an entry whose slot is >= capacity is not stored (nothing is written past the arrays); *length and carry advance as if it
+ *   had been: the caller sees *length > capacity.
+ *   Cells: *length += the chunk's finished episodes, *step_base += T, from the launch itself: no host value changes per chunk.
+ * PW_EINVAL, nothing launched: a wrong struct_size, a null pointer, a total / by_agent / end_step / carry / length / step_base that is
+ * not 8-byte aligned, an env or rew that is not 4-byte aligned, a scratch that is not 16-byte aligned, capacity < 1, T < 1, num_envs < 1,
+ * num_agents outside 1 .. PW_EPISODE_LOG_MAX_AGENTS, T * num_envs > 2^31 - 1 (the slot plane holds int32), num_envs * (num_agents + 1) >= 2^32
+ * (the walk's grid).  PW_EHIP (a launch the runtime refused): the cells may already have advanced; the log is invalid, discard it. */
+#define PW_EPISODE_LOG_MAX_AGENTS 96
+typedef struct pw_episode_log {
+    uint32_t struct_size;      /* = sizeof(pw_episode_log); checked */
+    int32_t  num_envs, num_agents;
+    int64_t  capacity;         /* entries */
+    double  *total;            /* [capacity]     return of the episode over all agents */
+    double  *by_agent;         /* [capacity, N]  each agent's share */
+    int64_t *end_step;         /* [capacity]     batched step index at which it ended (*step_base + t) */
+    int32_t *env;              /* [capacity]     env index within this handle / rank */
+    double  *carry;            /* [B, N + 1]     returns of the episodes in progress, column N = total; zeroed once by the caller */
+    int64_t *length;           /* device cell: episodes finished so far (keeps counting past capacity) */
+    int64_t *step_base;        /* device cell: batched steps absorbed so far; the launch adds T */
+    void    *scratch;          /* pw_episode_log_scratch_bytes(T, B) bytes; contents need not survive between launches */
+} pw_episode_log;
+/* The bytes of scratch one pw_episode_log_absorb of T steps over B envs needs (0 for a shape that is not served). */
+size_t pw_episode_log_scratch_bytes(int32_t T, int32_t B);
+int pw_episode_log_absorb(const pw_episode_log *log, const float *rew, const uint8_t *terminal, int32_t T, void *stream);
 
 #ifdef __cplusplus
 }

@@ -93,6 +93,15 @@ class PwRefWire(C.Structure):
                [(n, C.c_size_t) for n in ('head0', 'head', 'final_head', 'goal', 'comm0', 'rew_shared', 'act', 'epi', 'total_bytes')]
 
 
+class PwEpisodeLog(C.Structure):
+    """pw_episode_log: the caller-owned log pw_episode_log_absorb appends to (include/pworld.h); every pointer is device memory."""
+    _fields_ = [('struct_size', C.c_uint32), ('num_envs', C.c_int32), ('num_agents', C.c_int32), ('capacity', C.c_int64)] + \
+               [(n, C.c_void_p) for n in ('total', 'by_agent', 'end_step', 'env', 'carry', 'length', 'step_base', 'scratch')]
+
+
+PW_EPISODE_LOG_MAX_AGENTS = 96
+
+
 # name -> (restype, argtypes): every symbol include/pworld.h declares
 SIGNATURES = {
     'pw_version': (C.c_int, []),
@@ -206,6 +215,8 @@ SIGNATURES = {
                                          C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,
                                          C.c_size_t, C.c_void_p]),
     'pw_head_train_scratch_bytes': (C.c_size_t, [C.c_int64, C.c_int32, C.POINTER(C.c_int32)]),
+    'pw_episode_log_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
+    'pw_episode_log_absorb': (C.c_int, [C.POINTER(PwEpisodeLog), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 

@@ -12,7 +12,8 @@ SRCS = [os.path.join(HERE, 'csrc', 'pworld.hip'), os.path.join(HERE, 'csrc', 'pw
         os.path.join(HERE, 'csrc', 'pworld_replay.hip'), os.path.join(HERE, 'csrc', 'pworld_lstm.hip'),
         os.path.join(HERE, 'csrc', 'pworld_attention.hip'), os.path.join(HERE, 'csrc', 'pworld_optim_dev.hip'),
         os.path.join(HERE, 'csrc', 'pworld_sample.hip'), os.path.join(HERE, 'csrc', 'pworld_front.hip'),
-        os.path.join(HERE, 'csrc', 'pworld_lstm_wgrad.hip'), os.path.join(HERE, 'csrc', 'pworld_head.hip')]
+        os.path.join(HERE, 'csrc', 'pworld_lstm_wgrad.hip'), os.path.join(HERE, 'csrc', 'pworld_head.hip'),
+        os.path.join(HERE, 'csrc', 'pworld_episode_log.hip')]
 OUT = os.path.join(HERE, 'libpworld.so')
 OBJ_DIR = os.path.join(HERE, 'csrc', '_obj')  # git-ignored (*.o); objects are kept so that one unit rebuilds alone
 DEPS = [os.path.join(HERE, 'csrc', f) for f in sorted(os.listdir(os.path.join(HERE, 'csrc'))) if f.endswith(('.hip', '.hpp', '.inc'))] + \
@@ -63,7 +64,7 @@ def _stale(obj):
 def unit_sources(unit):
     """Every file translation unit `unit` ('pworld' = environment, 'pworld_policy' = actor and policy rollouts,
     'pworld_policy_generic' = the generic one-launch policy rollout, 'pworld_critic' = the learner's critic forward, 'pworld_optim' = clip + Adam + soft update, 'pworld_replay' = replay ring /
-    wire blocks, 'pworld_lstm' = the learner's LSTM recurrence with gradient, 'pworld_attention' = the critic's attention block with gradient, 'pworld_optim_dev' = Adam with the step count in device memory, 'pworld_sample' = the learner's Gumbel-softmax sample with gradient, 'pworld_front' = the learner's dense front (dense1, ReLU, gate projection) with gradient, 'pworld_lstm_wgrad' = the recurrent-weight gradients of the learner's LSTMs, 'pworld_head' = the learner's output layers (ReLU and every head) with gradient) is compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
+    wire blocks, 'pworld_lstm' = the learner's LSTM recurrence with gradient, 'pworld_attention' = the critic's attention block with gradient, 'pworld_optim_dev' = Adam with the step count in device memory, 'pworld_sample' = the learner's Gumbel-softmax sample with gradient, 'pworld_front' = the learner's dense front (dense1, ReLU, gate projection) with gradient, 'pworld_lstm_wgrad' = the recurrent-weight gradients of the learner's LSTMs, 'pworld_head' = the learner's output layers (ReLU and every head) with gradient, 'pworld_episode_log' = the per-episode returns of a chunk as a device-side log) is compiled from: the .hip file, the quoted includes it reaches under csrc/, and the two public headers.  Found by reading the
     sources (no compiler, no recorded paths), so it gives the same answer in any copy of the tree."""
     import re
     csrc = os.path.join(HERE, 'csrc')
